@@ -11,7 +11,11 @@ One "step" = one epoch of the reference loop /root/reference/arxiv_pyg/gnn.py:33
 (config 2: 3-layer GCN student, hidden 256, G-CRD with the run_gcn.sh:140-145 hyper-parameters
 beta=0.1, nce_T=0.075, max_samples=16384, proj_dim=256).  Inputs are resident in HBM before timing.
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying also
+A plain run sets up, warms up, times the --steps epochs, writes the last timed epoch's outputs if --dump-outputs DIR is
+given (DIR/<name>.npy: losses, accuracies, eval logits, parameters after the step; float32 / float64, at most 64 MB) and
+prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (milliseconds of one timed epoch) and the
+configuration.  With --full the line also carries the secondary measurements and checks, each taken after the timed region:
+  "timing":       (extra fields) device clocks under load, read-then-launch blocks; "repeat_blocks_*": further timed blocks
   "roofline":     the SpMM aggregate kernel (K=256 GCN layer) timed with HIP events on its launch stream; with the epoch
                   replayed as a hipGraph (default) the timed region has no per-kernel events, so the brackets are taken on
                   --probe-epochs EAGER epochs of the same problem right after it (over the timed region itself with --graph off);
@@ -20,6 +24,8 @@ Rank 0 prints ONE JSON line (contract in the task statement) carrying also
                   achieved = 6 S^2 P flops per step / their time
   "cpu_baseline": the CPU oracle (pure-PyTorch restatement of the reference path) timed on the host cores
                   on the SAME synthetic inputs, a bounded sample of epochs (rank 0, N=1 only).
+  "parity", "reference_loop", "eager", "phases_ms": the full-size check against the CPU oracle, the reference's own loop
+                  through dropin/, the eager probe epochs.
 """
 from __future__ import annotations
 
@@ -50,6 +56,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="timed epochs (default: a timed region of ~1.4 s)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary measurements and checks after the timed region (repeat blocks, device clocks, per-kernel "
+                         "roofline probes, full-size parity, the reference loop, the CPU baseline); without it a run does set-up, "
+                         "warm-up, the timed steps, --dump-outputs and the result line only.  The options below that tune those "
+                         "measurements (--cpu-epochs, --no-parity, --reference-epochs, --repeat-blocks, --probe-epochs, ...) act with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed epoch computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all; single-GPU path)")
     ap.add_argument("--scale", type=float, default=1.0, help="graph size multiplier (1.0 = ogbn-arxiv shape)")
     ap.add_argument("--max-samples", type=int, default=HP["max_samples"])
     ap.add_argument("--gnn", default="gcn", choices=["gcn", "sage"])
@@ -830,6 +844,74 @@ def spawn_ranks(n: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def snapshot_outputs(losses, accs, logits, modules) -> dict:
+    """What the last timed epoch handed its caller, as host arrays: the three losses, the three accuracies, the eval logits
+    and every floating-point parameter / buffer of the model and heads after the step.  Logits beyond the 64 MB budget are
+    cut to a fixed seeded sample of rows (``logits_rows`` names them), the same rows for the same arguments."""
+    arrays = {"losses": np.asarray([float(v) for v in losses], dtype=np.float64),
+              "accs": np.asarray([float(a) for a in accs], dtype=np.float64)}
+    for prefix, m in modules:
+        if m is None:
+            continue
+        for k, v in m.state_dict().items():
+            if v.is_floating_point():
+                arrays[f"{prefix}.{k}"] = v.detach().float().cpu().numpy()
+    rest = sum(a.nbytes for a in arrays.values())
+    out = logits.detach().float().cpu().numpy()
+    if rest + out.nbytes > DUMP_LIMIT_BYTES:
+        n_rows = int((DUMP_LIMIT_BYTES - rest) // (out.shape[1] * 4 + 8))
+        rows = np.sort(np.random.default_rng(0).choice(out.shape[0], n_rows, replace=False))
+        arrays["logits_rows"] = rows.astype(np.float64)
+        out = out[rows]
+    arrays["logits"] = out
+    return arrays
+
+
+def write_outputs(dirname: str, arrays: dict) -> None:
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
+def headline(args, d, hp, ops, elapsed, losses, accs, graph_note, timing) -> dict:
+    """The result line of every single-GPU run: the headline figure and what it was measured on (--full adds the rest)."""
+    return dict(
+        metric="training epochs/sec, ogbn-arxiv 3-layer GCN student + G-CRD, 1/2/4/8 MI355X",
+        value=round(args.steps / elapsed, 3), unit="epochs/s", n_gpus=1, steps=args.steps, warmup=args.warmup,
+        ms_per_step=round(1e3 * elapsed / args.steps, 3), higher_is_better=True, scaling="strong", vs_baseline=None,
+        dtype="f32", data="synthetic",
+        arithmetic=("fp32 tensors, fp32 accumulation everywhere; GEMM / G-CRD products formed on the bf16 matrix pipe as the six exact "
+                    "partial products of a three-way bf16 split of each fp32 operand (error vs float64 not above the f32-input MFMA's: "
+                    "tests/test_gpu_parity.py::test_split_pipeline_error_is_not_above_the_f32_mfma_pipeline; DESIGN.md 3.2); "
+                    "EGNN_GEMM_PIPE=f32 pins them to v_mfma_f32_32x32x2_f32")
+                   if not os.environ.get("EGNN_GEMM_PIPE", "").startswith("f") else "fp32 tensors and accumulation; products on the f32-input MFMA",
+        config=dict(workload=f"ogbn-arxiv-shaped synthetic graph (N={d.num_nodes}, nnz_sym={d.adj_t.nnz()}), "
+                             f"3-layer {args.gnn.upper()}-256 student + {args.training}"
+                             f"{' (G-CRD)' if args.training == 'nce' else ''} loss (max_samples={hp['max_samples']}, "
+                             f"proj_dim={hp['proj_dim']}, nce_T={hp['nce_T']}, beta={hp['beta']}"
+                             f"{', kernel=' + hp['kernel'] if args.training in ('gpw', 'lpw') else ''}), full-graph train step + eval per epoch",
+                    gemm_backend=ops.gemm_backend(), partitioning="single GPU",
+                    spmm_schedule=getattr(ops, "_SPMM_SCHEDULE", "classes"),
+                    gcn_operand_order="aggregate on the narrower side of W (layer 1: (A x) W; same product as A (x W))",
+                    adam="fused",
+                    memoise_first_layer_aggregation=os.environ.get("EGNN_GCN_MEMOISE_AX", "0") == "1",
+                    cache_constant_row_gathers=os.environ.get("EGNN_CACHE_CONST_ROWS", "0") == "1"),
+        launch=graph_note,
+        last_losses=[round(float(v), 5) for v in losses], last_accs=[round(float(a), 4) for a in accs],
+        timing=timing,
+    )
+
+
+def finish(args, out: dict, dumped) -> None:
+    """Writes the --dump-outputs arrays (taken right after the timed steps), then prints the result line."""
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -872,6 +954,8 @@ def main():
     if args.graph is None:
         args.graph = "auto" if sharded_path else "on"
     if world > 1 or args.force_sharded or args.workload == "mag":
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is implemented for the single-GPU path only")
         if "MASTER_PORT" not in os.environ:
             # one process started by hand (--force-sharded / --workload mag): any free port (a fixed one can collide with the lingering
             # socket of a run that has just ended; one run of a back-to-back series produced no line)
@@ -971,13 +1055,8 @@ def main():
         elapsed, (losses, accs) = block(args.steps)        # THE timed region: exactly K epochs
         gpu_ms = sorted(a.elapsed_time(b) for a, b in graphed.replay_events)
         graphed.replay_events = None
-        # the contract's block is the one above; further blocks of the same length show the spread of the measurement
-        n_blocks = args.repeat_blocks if args.repeat_blocks >= 0 else max(4, min(50, int(np.ceil(2.0 / max(elapsed, 1e-3)))))
-        for _ in range(n_blocks):
-            block_ms.append(block(args.steps)[0] * 1e3 / args.steps)
-        clocks = {}
-        block(args.steps, mid=lambda: clocks.update(gpu_clock_state(device) or {}))    # (not one of the reported blocks)
-        sync_ms = [block(args.steps, sync_reads=True)[0] * 1e3 / args.steps for _ in range(2)]
+        if args.dump_outputs:
+            dumped = snapshot_outputs(losses, accs, graphed.out, (("model", model), ("student_proj", sp), ("teacher_proj", tp)))
         timing = dict(
             gpu_ms_per_replay=round(float(np.median(gpu_ms)), 4), gpu_ms_per_replay_min_max=[round(gpu_ms[0], 4), round(gpu_ms[-1], 4)],
             host_gap_ms_per_step=round(1e3 * elapsed / args.steps - float(np.median(gpu_ms)), 4),
@@ -985,10 +1064,20 @@ def main():
             loop="step_async: replay k is launched before the values of epoch k-1 are read (K replays, K host reads of 3 losses + 3 "
                  "accuracies inside the timed region; same replays / draws / values as the read-then-launch loop: "
                  "test_graphed_epoch_step_async_hands_out_the_same_values_one_call_later)",
-            ms_per_step_read_then_launch=[round(v, 3) for v in sync_ms],
             settle_before_warmup=dict(settle, why="untimed replays of the timed program for --settle-seconds in front of the --warmup steps: the device "
-                                                  "leaves set-up in a low clock state and its replay time keeps falling for ~2-3 s of load"),
-            device_clocks_under_load=clocks)
+                                                  "leaves set-up in a low clock state and its replay time keeps falling for ~2-3 s of load"))
+    if graphed is not None and args.full:
+        # the contract's block is the one above; further blocks of the same length show the spread of the measurement
+        n_blocks = args.repeat_blocks if args.repeat_blocks >= 0 else max(4, min(50, int(np.ceil(2.0 / max(elapsed, 1e-3)))))
+        for _ in range(n_blocks):
+            block_ms.append(block(args.steps)[0] * 1e3 / args.steps)
+        clocks = {}
+        block(args.steps, mid=lambda: clocks.update(gpu_clock_state(device) or {}))    # (not one of the reported blocks)
+        sync_ms = [block(args.steps, sync_reads=True)[0] * 1e3 / args.steps for _ in range(2)]
+        timing.update(ms_per_step_read_then_launch=[round(v, 3) for v in sync_ms], device_clocks_under_load=clocks)
+    if graphed is not None and not args.full:
+        finish(args, headline(args, d, hp, ops, elapsed, losses, accs, graph_note, timing), dumped if args.dump_outputs else None)
+        return
     # per-kernel brackets (HIP events on the launch stream) need eager launches: with a graph the timed region above has no
     # per-kernel events, so the roofline objects are measured on `probe_epochs` eager epochs of the same problem right after
     # it; without a graph they are measured over the timed region itself
@@ -1007,7 +1096,7 @@ def main():
             l2 = PM.train_step(model, d.x, d.adj_t, d.y, d.split_idx["train"], opt, args.training, hp,
                                d.teacher_out_feat, d.teacher_logits, sp, tp, edge_index)
             ev[1].record()
-            _, a2 = PM.evaluate(model, d.x, d.adj_t, d.y, d.split_idx)
+            o2, a2 = PM.evaluate(model, d.x, d.adj_t, d.y, d.split_idx)
             ev[2].record()
             ev[2].synchronize()
             train_ms += ev[0].elapsed_time(ev[1])
@@ -1021,6 +1110,11 @@ def main():
         gemm_probe.active = False
     if graphed is None:
         elapsed, losses, accs = eager_elapsed, l2, a2
+        if args.dump_outputs:
+            dumped = snapshot_outputs(losses, accs, o2, (("model", model), ("student_proj", sp), ("teacher_proj", tp)))
+        if not args.full:
+            finish(args, headline(args, d, hp, ops, elapsed, losses, accs, graph_note, timing), dumped if args.dump_outputs else None)
+            return
     K = MODEL["hidden"]
     roof = probe.summary(K)
     roofline = None
@@ -1135,35 +1229,13 @@ def main():
     ref_loop = reference_loop(args, d, device, hp, epochs=args.reference_epochs) if args.reference_epochs > 0 else None
     cpu = cpu_baseline(args, data, hp) if args.cpu_epochs > 0 else None
 
-    out = dict(
-        metric="training epochs/sec, ogbn-arxiv 3-layer GCN student + G-CRD, 1/2/4/8 MI355X",
-        value=round(args.steps / elapsed, 3), unit="epochs/s", n_gpus=1, steps=args.steps, warmup=args.warmup,
-        ms_per_step=round(1e3 * elapsed / args.steps, 3), higher_is_better=True, scaling="strong", vs_baseline=None,
-        dtype="f32", data="synthetic",
-        arithmetic=("fp32 tensors, fp32 accumulation everywhere; GEMM / G-CRD products formed on the bf16 matrix pipe as the six exact "
-                    "partial products of a three-way bf16 split of each fp32 operand (error vs float64 not above the f32-input MFMA's: "
-                    "tests/test_gpu_parity.py::test_split_pipeline_error_is_not_above_the_f32_mfma_pipeline; DESIGN.md 3.2); "
-                    "EGNN_GEMM_PIPE=f32 pins them to v_mfma_f32_32x32x2_f32")
-                   if not os.environ.get("EGNN_GEMM_PIPE", "").startswith("f") else "fp32 tensors and accumulation; products on the f32-input MFMA",
-        config=dict(workload=f"ogbn-arxiv-shaped synthetic graph (N={d.num_nodes}, nnz_sym={d.adj_t.nnz()}), "
-                             f"3-layer {args.gnn.upper()}-256 student + {args.training}"
-                             f"{' (G-CRD)' if args.training == 'nce' else ''} loss (max_samples={hp['max_samples']}, "
-                             f"proj_dim={hp['proj_dim']}, nce_T={hp['nce_T']}, beta={hp['beta']}"
-                             f"{', kernel=' + hp['kernel'] if args.training in ('gpw', 'lpw') else ''}), full-graph train step + eval per epoch",
-                    gemm_backend=ops.gemm_backend(), partitioning="single GPU",
-                    spmm_schedule=getattr(ops, "_SPMM_SCHEDULE", "classes"),
-                    gcn_operand_order="aggregate on the narrower side of W (layer 1: (A x) W; same product as A (x W))",
-                    adam="fused",
-                    memoise_first_layer_aggregation=os.environ.get("EGNN_GCN_MEMOISE_AX", "0") == "1",
-                    cache_constant_row_gathers=os.environ.get("EGNN_CACHE_CONST_ROWS", "0") == "1"),
+    out = headline(args, d, hp, ops, elapsed, losses, accs, graph_note, timing)
+    out.update(
         roofline=roofline, roofline_local=roofline_local, roofline_mfma=roofline_mfma, roofline_gemm=roofline_gemm, roofline_edges=roofline_edges, roofline_gsp=roofline_gsp, cpu_baseline=cpu, parity=parity,
-        launch=graph_note,
         eager=dict(epochs_per_s=round(n_probe / eager_elapsed, 3), epochs=n_probe,
                    note="eager launches with per-kernel event brackets (where the roofline objects are measured)"),
         phases_ms=dict(train_step=round(train_ms / max(1, n_probe), 3), eval=round(eval_ms / max(1, n_probe), 3)),
-        last_losses=[round(float(v), 5) for v in losses], last_accs=[round(float(a), 4) for a in accs],
         reference_loop=ref_loop,
-        timing=timing,
         repeat_blocks_ms_per_step=[round(v, 3) for v in block_ms],   # further blocks of `steps` replays after the contract's block
         repeat_blocks_median_ms_per_step=(round(float(np.median(block_ms)), 3) if block_ms else None),
     )
@@ -1171,7 +1243,7 @@ def main():
         out["speedup_vs_cpu_baseline"] = round(out["value"] / cpu["value"], 1)
     if ref_loop and "epochs_per_s" in ref_loop:
         ref_loop["fraction_of_package_loop"] = round(ref_loop["epochs_per_s"] / out["value"], 4)
-    print(json.dumps(out), flush=True)
+    finish(args, out, dumped if args.dump_outputs else None)
     if parity is not None and not parity["ok"]:
         raise SystemExit("bench.py: full-size parity against the CPU oracle FAILED (see the 'parity' object of the JSON line)")
 

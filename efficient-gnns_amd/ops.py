@@ -1046,6 +1046,8 @@ class _BnAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, mean, var, eps, relu, p, seed, batch_stats, pick=None):
+        if not x.is_cuda:    # (the kernels take device pointers: a host tensor must never reach a launch)
+            raise RuntimeError(f"bn_act: the HIP kernels need a GPU tensor, got one on {x.device}")
         x = _rowmajor(x)
         n, C = x.shape
         seed_dev = _DROPOUT_SEED_DEV if p > 0 else None

@@ -1,7 +1,8 @@
-"""The reference's OWN ``arxiv_pyg/gnn.py`` (train()/test(), GCN/SAGE classes) running unchanged on top of
-``efficient-gnns_amd/dropin``.  The file is read from /root/reference in the build container and, on the GPU box (where
-/root/reference is absent), from the verbatim copy ``__graft_entry__.build()`` stages under the git-ignored
-``oracle/_ref/`` (shipped with the tree, never committed)."""
+"""A PyG training script runs unchanged on top of ``efficient-gnns_amd/dropin``: ``tests/dropin_scripts/arxiv_train.py``
+(GCN / SAGE classes, ``train()`` / ``test()``) and ``arxiv_train_kd_and_aux.py`` (loss = KD + beta * aux), written against the
+PyG / torch-sparse API in the shape of the reference's arxiv training scripts, import ``torch_geometric`` / ``torch_sparse`` /
+``criterion`` from the drop-in layer and are checked against the package's own ``train_step`` / ``evaluate`` (GPU) and the
+oracle (CPU host layer)."""
 import argparse
 import importlib.util
 import os
@@ -14,14 +15,11 @@ import torch
 
 from conftest import ROOT
 
-def _ref_script(name):
-    cands = (f"/root/reference/arxiv_pyg/{name}", os.path.join(ROOT, "oracle", "_ref", "arxiv_pyg", name))
-    return next((p for p in cands if os.path.exists(p)), cands[0])
-
-
-REF = _ref_script("gnn.py")
-REF_KD_AUX = _ref_script("gnn_kd_and_aux.py")     # the second caller of the same operators: loss = KD + beta * aux
+SCRIPTS = os.path.join(ROOT, "tests", "dropin_scripts")
+REF = os.path.join(SCRIPTS, "arxiv_train.py")
+REF_KD_AUX = os.path.join(SCRIPTS, "arxiv_train_kd_and_aux.py")
 DROPIN = os.path.join(ROOT, "efficient-gnns_amd", "dropin")
+_SCRIPT_MODULES = ("arxiv_train",)
 _SHIMMED = ("criterion", "torch_geometric", "torch_geometric.nn", "torch_geometric.utils", "torch_geometric.transforms", "torch_sparse")
 
 
@@ -33,7 +31,6 @@ def _load_accel():
 
 
 def _load_reference_gnn(path=None):
-    sys.dont_write_bytecode = True   # never leave __pycache__ inside the read-only reference tree
     for name in ("ogb", "ogb.nodeproppred", "torch.utils.tensorboard", "logger"):
         sys.modules.setdefault(name, types.ModuleType(name))
     sys.modules["ogb.nodeproppred"].PygNodePropPredDataset = None
@@ -41,7 +38,9 @@ def _load_reference_gnn(path=None):
     sys.modules["torch.utils.tensorboard"].SummaryWriter = object
     sys.modules["logger"].Logger = object
     sys.path.insert(0, DROPIN)
-    for stale in _SHIMMED:
+    if SCRIPTS not in sys.path:
+        sys.path.insert(0, SCRIPTS)      # (the kd-and-aux script imports its models from arxiv_train.py)
+    for stale in _SHIMMED + _SCRIPT_MODULES:
         sys.modules.pop(stale, None)
     spec = importlib.util.spec_from_file_location("ref_gnn_dropin", path or REF)
     mod = importlib.util.module_from_spec(spec)
@@ -88,19 +87,17 @@ class _Evaluator:
 @pytest.mark.parametrize("mode", ["nce", "kd", "lpw", "gpw"])
 @pytest.mark.parametrize("script,accel_mode", [("gnn", "plain"), ("gnn", "lazy"), ("gnn", "eager"), ("kd_and_aux", "plain"), ("kd_and_aux", "lazy")])
 def test_reference_train_loop_runs_unchanged_on_the_new_operators(gnn, mode, script, accel_mode):
-    """arxiv_pyg/gnn.py's own GCN / SAGE classes, train() and test() (gnn.py:20,23-85,102-218), imported unchanged
+    """The script's GCN / SAGE classes, train() and test() (tests/dropin_scripts/arxiv_train.py), imported unchanged
     through efficient-gnns_amd/dropin and executed on the GPU kernels: three optimisation steps and the eval logits equal
     the package's own train_step / evaluate from the same initial weights and the same NumPy draw (dropout 0: the
     reference's F.dropout and the fused kernel's mask are equal only in distribution).
-    ``script`` = kd_and_aux: arxiv_pyg/gnn_kd_and_aux.py's train() (:100-181, loss = KD + beta * aux) against
+    ``script`` = kd_and_aux: arxiv_train_kd_and_aux.py's train() (loss = KD + beta * aux) against
     ``train_step(kd_and_aux=True)``.  ``accel_mode``: plain = torch's own BatchNorm1d / Linear (launch.py --plain-torch-modules);
     eager = dropin/accel.py with one launch per torch call; lazy = accel's default: BatchNorm1d.forward returns a deferred activation
     that absorbs F.relu / F.dropout and is formed by its consumer (efficient_gnns_amd/lazy.py)."""
     path = REF if script == "gnn" else REF_KD_AUX
-    assert os.path.exists(path), (f"the reference's {os.path.basename(path)} is neither under /root/reference nor staged under oracle/_ref/ "
-                                  "(run __graft_entry__.build() in the build container before shipping the tree)")
     if script == "kd_and_aux" and mode == "kd":
-        pytest.skip("gnn_kd_and_aux.py's kd branch is gnn.py's")
+        pytest.skip("the kd-and-aux script's kd branch is arxiv_train.py's")
     import efficient_gnns_amd.data as D
     import efficient_gnns_amd.models as PM
     from efficient_gnns_amd.utils import subgraph
@@ -109,7 +106,7 @@ def test_reference_train_loop_runs_unchanged_on_the_new_operators(gnn, mode, scr
     if accel_mode != "plain":
         accel = _load_accel()
         accel.LAZY = accel_mode == "lazy"
-        accel._BIG_GATHER = accel._MIN_GATHER_ROWS = 1       # (this 3 387-node problem: let the deferred constant gather of gnn.py:155 take part)
+        accel._BIG_GATHER = accel._MIN_GATHER_ROWS = 1       # (this 3 387-node problem: let the script's deferred constant teacher gather take part)
         accel.enable()
     try:
         dev = torch.device("cuda")
@@ -123,7 +120,7 @@ def test_reference_train_loop_runs_unchanged_on_the_new_operators(gnn, mode, scr
         args = argparse.Namespace(training=mode, **{k: hp[k] for k in ("alpha", "kd_T", "beta", "nce_T", "max_samples", "kernel")})
         torch.manual_seed(0)
         model = (ref.GCN if gnn == "gcn" else ref.SAGE)(d.num_features, H, d.num_classes, 3, 0.0).to(dev)
-        # projection heads exactly as gnn.py:296-306 builds them
+        # projection heads as a PyG script builds them: Linear + BatchNorm1d + ReLU
         sp = torch.nn.Sequential(torch.nn.Linear(H, Pj), torch.nn.BatchNorm1d(Pj), torch.nn.ReLU()).to(dev)
         tp = torch.nn.Sequential(torch.nn.Linear(750, Pj), torch.nn.BatchNorm1d(Pj), torch.nn.ReLU()).to(dev)
         mine = (PM.GCN if gnn == "gcn" else PM.SAGE)(d.num_features, H, d.num_classes, 3, 0.0).to(dev)
@@ -136,7 +133,7 @@ def test_reference_train_loop_runs_unchanged_on_the_new_operators(gnn, mode, scr
             return torch.optim.Adam([{"params": m.parameters()}, {"params": a.parameters()}, {"params": b.parameters()}], lr=0.01)
         tf, tl = d.teacher_out_feat.to(dev), d.teacher_logits.to(dev)
         edge_index = None
-        if mode == "lpw":   # gnn.py:274: the train-induced subgraph
+        if mode == "lpw":   # the train-induced subgraph
             edge_index = subgraph(train_idx, torch.stack(data.adj_t.coo()[:2]), relabel_nodes=True, num_nodes=d.num_nodes)[0]
         out0, accs0 = ref.test(model, data, split_idx, _Evaluator())
         mout0, maccs0 = PM.evaluate(mine, data.x, data.adj_t, data.y, split_idx)
@@ -162,7 +159,7 @@ def test_reference_train_loop_runs_unchanged_on_the_new_operators(gnn, mode, scr
         assert out.shape == (d.num_nodes, d.num_classes) and all(0 <= a <= 1 for a in accs)
         if accel_mode == "lazy":     # the deferred form is what ran: out_feat of the script's model is the deferred object, formed by now
             from efficient_gnns_amd.lazy import LazyBnAct, LazyFold, LazyRows
-            # gnn.py:155 `teacher_out_feat[train_idx]`: a row gather of a large constant leaf inside a grad-enabled region is deferred ...
+            # the script's `teacher_out_feat[train_idx]`: a row gather of a large constant leaf inside a grad-enabled region is deferred ...
             picked = tf[train_idx]
             assert isinstance(picked, LazyRows) and picked._const and torch.equal(picked._egnn_materialise(), torch.Tensor.index_select(tf, 0, train_idx))
             with torch.no_grad():                          # ... and nothing else is: no_grad regions, tensors in autograd, other index kinds
@@ -183,7 +180,9 @@ def test_reference_train_loop_runs_unchanged_on_the_new_operators(gnn, mode, scr
             accel.disable()
         if DROPIN in sys.path:
             sys.path.remove(DROPIN)
-        for stale in _SHIMMED + ("ref_gnn_dropin",):
+        if SCRIPTS in sys.path:
+            sys.path.remove(SCRIPTS)
+        for stale in _SHIMMED + _SCRIPT_MODULES + ("ref_gnn_dropin",):
             sys.modules.pop(stale, None)
 
 
@@ -239,10 +238,9 @@ def _host_layer_worker(q, gnn, mode):
     q.put((losses, out0.numpy(), list(accs0), {k: v.numpy() for k, v in init.items()}))
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference tree is only present in the build container")
 @pytest.mark.parametrize("gnn,mode", [("gcn", "nce"), ("sage", "kd"), ("sage", "nce"), ("gcn", "supervised")])
 def test_reference_train_loop_drives_the_host_layer_on_cpu(gnn, mode):
-    """arxiv_pyg/gnn.py's own GCN / train() / test(), imported unchanged through efficient-gnns_amd/dropin, running on the
+    """The script's GCN / SAGE / train() / test(), imported unchanged through efficient-gnns_amd/dropin, running on the
     package's host layer (GCNConv, SparseTensor, criterion) with the kernels swapped for oracle stand-ins in a child
     process: the losses of three steps and the initial eval equal the oracle's train_step / evaluate."""
     import torch.multiprocessing as mp

@@ -2,7 +2,7 @@
 # Secondary BASELINE.json configs (parity-test cases; timed here for DESIGN.md, not the headline line)
 mkdir -p gpurun_out
 for cfg in "sage lpw" "gcn gpw" "gcn kd" "sage nce" "gcn supervised"; do set -- $cfg
-echo "== $1 $2"; timeout 600 python bench.py --gnn $1 --training $2 --steps 10 --warmup 3 --cpu-epochs 0 2>&1 | tail -1 | python -c "
+echo "== $1 $2"; timeout 600 python bench.py --full --gnn $1 --training $2 --steps 10 --warmup 3 --cpu-epochs 0 2>&1 | tail -1 | python -c "
 import json,sys
 l=sys.stdin.readline()
 try:

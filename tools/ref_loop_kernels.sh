@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/$1; shift; mkdir -p $O
 rm -rf /tmp/profr
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/profr -o rk -- python $R/bench.py --steps 2 --warmup 2 --cpu-epochs 0 --no-parity --probe-epochs 0 --no-local-roofline --repeat-blocks 0 --reference-epochs 6 "$@" > $O/run_ref.log 2>&1); echo "rc=$?"
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/profr -o rk -- python $R/bench.py --full --steps 2 --warmup 2 --cpu-epochs 0 --no-parity --probe-epochs 0 --no-local-roofline --repeat-blocks 0 --reference-epochs 6 "$@" > $O/run_ref.log 2>&1); echo "rc=$?"
 grep '^{' $O/run_ref.log | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print(json.dumps(d.get('reference_loop')))"
 python3 - $(find /tmp/profr -name "*kernel_trace.csv" | head -1) $O/ref_epoch.txt <<'PY'
 import csv, sys, re, collections
