@@ -19,6 +19,7 @@ Everything else (local aggregation, GEMMs, losses) is the single-GPU kernel path
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import time
@@ -29,6 +30,7 @@ import torch.distributed as dist
 from torch import Tensor, nn
 
 from . import _lib, ops
+from .models import ReplayedEpoch
 from .sparse import SparseTensor
 
 
@@ -1386,7 +1388,7 @@ def sharded_evaluate(model, prob: ShardedProblem):
     return out, accs
 
 
-class ShardedGraphedEpoch:
+class ShardedGraphedEpoch(ReplayedEpoch):
     """One epoch of the sharded run (train step + eval on this rank's shard, collectives included) captured ONCE as a hipGraph
     and replayed -- the sharded counterpart of ``models.GraphedEpoch``: the ~250 launches and ~25 collectives of an epoch are
     enqueued by one call.  RCCL collectives are stream operations and are captured like kernels (all ranks capture and replay
@@ -1397,6 +1399,10 @@ class ShardedGraphedEpoch:
     that one step with eager launches and dynamic shapes -- every rank sees the same draw and takes the same branch.
     Host randomness as in the eager step: one np.random.choice per step, a fresh dropout seed per replay; one device->host
     read per epoch."""
+
+    # thread-local capture mode: the process group's watchdog thread polls the events of the warm-up collectives; in the
+    # default (global) mode a call from ANY thread invalidates the capture (seen: abort in capture_end)
+    capture_error_mode = "thread_local"
 
     @staticmethod
     def capturable(world: int, mode: str) -> bool:
@@ -1412,93 +1418,58 @@ class ShardedGraphedEpoch:
         self._args = (model, prob, optimizer, mode, hp, student_proj, teacher_proj)
         dev = prob.x.device
         S = hp.get("max_samples", 0) if mode in ("nce", "gpw") else 0
-        self.n_pick = min(S, prob.n_train_global) if S else 0
+        n_pick = min(S, prob.n_train_global) if S else 0
         # one rank owns the whole sample: a static [S] id buffer does (the single-GPU GraphedEpoch's way); several ranks: StaticSample
         self.static = None
-        if self.n_pick and (prob.world > 1 if static_sample is None else static_sample):
-            self.static = StaticSample(prob, self.n_pick)
+        if n_pick and (prob.world > 1 if static_sample is None else static_sample):
+            self.static = StaticSample(prob, n_pick)
             self.static.external = True
         self._overflow = None            # the draw of the NEXT step when it does not fit the static capacity
-        self._pick_dev = torch.zeros(max(self.n_pick, 1), dtype=torch.int64, device=dev)
-        self._pick_host = torch.zeros(max(self.n_pick, 1), dtype=torch.int64).pin_memory()
-        self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        super().__init__(dev, n_pick, 6, torch.float32)     # values of an epoch: 3 losses, 3 global hit counts
 
         def body():
             rep = sharded_train_step_tensors(model, prob, optimizer, mode, hp, student_proj, teacher_proj)
             _, correct = sharded_evaluate_tensors(model, prob)
             return rep, correct
         self._body = body
-        from . import _cache
-        # cached structures the captured launches read through raw pointers stay alive with this object (_cache.pinning)
-        with self._installed(), _cache.pinning() as self._pinned:
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for i in range(warmup):
-                    self._refresh(require_fit=True)
-                    if i == warmup - 1:   # no long torch reduction may be captured (their memset node: _audit.py); same check on every rank
-                        from ._audit import CaptureAudit
-                        with CaptureAudit() as audit:
-                            body()
-                        audit.check("ShardedGraphedEpoch")
-                    else:
-                        body()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            torch.cuda.synchronize(dev)
-            self.graph = torch.cuda.CUDAGraph(keep_graph=True)
-            self._refresh(require_fit=True)
-            torch.cuda.synchronize(dev)
-            # thread-local capture mode: the process group's watchdog thread polls the events of the warm-up collectives; in the
-            # default (global) mode a call from ANY thread invalidates the capture (seen: abort in capture_end)
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.rep, self.correct = body()
-            # structural guard on every capture (_audit.check_captured_graph): no memset / host node next to the kernels and RCCL's nodes
-            from ._audit import LongReductionInCapture, check_captured_graph, graph_node_kinds
-            try:
-                self.node_kinds = check_captured_graph(self.graph, "ShardedGraphedEpoch", kernels_only=False)
-            except LongReductionInCapture as e:
-                # One rank over RCCL has been observed (kernel + memcpy nodes only) and is held to that.  What RCCL itself puts into a
-                # captured collective with SEVERAL ranks has never been observed (no multi-GPU box in any round): there a violation is
-                # reported, not fatal -- the operator-name audit above still refuses long torch reductions on every rank count.
-                if prob.world == 1:
-                    raise
-                import warnings
-                warnings.warn(f"{e}  (world_size {prob.world}: reported only; RCCL's own graph nodes cannot be told apart here)")
-                self.node_kinds = graph_node_kinds(self.graph)
-            self.graph.instantiate()
-            torch.cuda.synchronize(dev)
-        self._refresh()
+        self.rep, self.correct = self._capture(body, dev, warmup)
 
-    class _Install:
-        """The capture hooks (static sample buffers, device-side dropout seed) for the duration of a block."""
+    def _check_graph(self):
+        # structural guard on every capture (_audit.check_captured_graph): no memset / host node next to the kernels and RCCL's nodes
+        from ._audit import LongReductionInCapture, check_captured_graph, graph_node_kinds
+        try:
+            return check_captured_graph(self.graph, "ShardedGraphedEpoch", kernels_only=False)
+        except LongReductionInCapture as e:
+            # One rank over RCCL has been observed (kernel + memcpy nodes only) and is held to that.  What RCCL itself puts into a
+            # captured collective with SEVERAL ranks has never been observed (no multi-GPU box in any round): there a violation is
+            # reported, not fatal -- the operator-name audit still refuses long torch reductions on every rank count.
+            if self.prob.world == 1:
+                raise
+            import warnings
+            warnings.warn(f"{e}  (world_size {self.prob.world}: reported only; RCCL's own graph nodes cannot be told apart here)")
+            return graph_node_kinds(self.graph)
 
-        def __init__(self, owner):
-            self.o = owner
-
-        def __enter__(self):
-            o, prob = self.o, self.o.prob
-            self.prev = (prob.sample_hook, prob.static_sample, ops._DROPOUT_SEED_DEV)
-            if o.static is not None:
-                prob.sample_hook, prob.static_sample = None, o.static
-            else:
-                prob.sample_hook = lambda S_: (o._pick_dev[:o.n_pick], [o.n_pick])     # one rank owns the whole sample
-            ops._DROPOUT_SEED_DEV = o._seed_dev
-
-        def __exit__(self, *exc):
-            self.o.prob.sample_hook, self.o.prob.static_sample, ops._DROPOUT_SEED_DEV = self.prev
-
+    @contextlib.contextmanager
     def _installed(self):
-        return ShardedGraphedEpoch._Install(self)
+        """The capture hooks (static sample buffers, device-side dropout seed) for the duration of a block."""
+        prob = self.prob
+        prev = (prob.sample_hook, prob.static_sample, ops._DROPOUT_SEED_DEV)
+        if self.static is not None:
+            prob.sample_hook, prob.static_sample = None, self.static
+        else:
+            prob.sample_hook = lambda S_: (self._pick_dev[:self.n_pick], [self.n_pick])     # one rank owns the whole sample
+        ops._DROPOUT_SEED_DEV = self._seed_dev
+        try:
+            yield
+        finally:
+            prob.sample_hook, prob.static_sample, ops._DROPOUT_SEED_DEV = prev
 
-    def _draw(self, require_fit: bool = False):
-        if getattr(self, "_uploaded", None) is not None:
-            self._uploaded.synchronize()     # the previous upload has left the pinned buffers (microseconds: it sits in front of the replay)
+    def _draw_pick(self, require_fit):
         self._overflow = None
         if self.static is not None:
             pick = self.static.draw()
             while not self.static.fill(pick):
-                if not require_fit:          # a replay cannot take this draw: step() runs it with eager launches
+                if not require_fit:          # a replay cannot take this draw: the step runs it with eager launches
                     self._overflow = pick
                     break
                 pick = self.static.draw()    # warm-up / capture only need SOME sample that fits (their results are discarded)
@@ -1506,89 +1477,34 @@ class ShardedGraphedEpoch:
             ntr = self.prob.n_train_global
             pick = np.random.choice(ntr, self.n_pick, replace=False) if self.n_pick < ntr else np.arange(ntr)
             self._pick_host.copy_(self.prob.train_localpos[torch.from_numpy(pick)])       # one rank: every picked row is local
-        self._seed_host.random_()
-        self._seed_host.bitwise_and_(0x3FFFFFFFFFFFFFFF)
 
-    def _upload(self):
+    def _upload_pick(self):
         if self.static is not None:
             if self._overflow is None:
                 self.static.upload()
         elif self.n_pick:
             self._pick_dev.copy_(self._pick_host, non_blocking=True)
-        self._seed_dev.copy_(self._seed_host, non_blocking=True)
-        # the copies above are only stream-ordered: the host must not rewrite the pinned staging buffers before the DMA has read them
-        self._uploaded = torch.cuda.Event()
-        self._uploaded.record()
 
-    def _refresh(self, require_fit: bool = False):
-        self._draw(require_fit)
-        self._upload()
-
-    def redraw(self):
-        """Discard the randomness prepared for the next step and draw it again (after re-seeding NumPy / torch)."""
-        torch.cuda.current_stream().synchronize()
-        self._refresh()
-
-    def _eager_step(self, pick):
-        """The step whose draw does not fit the static capacity: same program with dynamic shapes and eager launches."""
-        prev = (self.prob.sample_hook, self.prob.static_sample, ops._DROPOUT_SEED_DEV)
-        self.prob.sample_hook, self.prob.static_sample, ops._DROPOUT_SEED_DEV = None, None, self._seed_dev
-        self.prob._forced_pick = pick
+    def _launch(self):
+        """Enqueue one epoch: the replay, or -- a draw that does not fit the static capacity -- the same program with dynamic shapes
+        and eager launches; returns the device tensor of its (3 losses, 3 hit counts)."""
+        if self._overflow is None:
+            self.graph.replay()
+            return torch.cat([self.rep, self.correct])
+        prob = self.prob
+        prev = (prob.sample_hook, prob.static_sample, ops._DROPOUT_SEED_DEV)
+        prob.sample_hook, prob.static_sample, ops._DROPOUT_SEED_DEV = None, None, self._seed_dev
+        prob._forced_pick = self._overflow
         try:
             rep, correct = self._body()
         finally:
-            self.prob.sample_hook, self.prob.static_sample, ops._DROPOUT_SEED_DEV = prev
-        return rep, correct
+            prob.sample_hook, prob.static_sample, ops._DROPOUT_SEED_DEV = prev
+        return torch.cat([rep, correct])
 
-    def _launch(self):
-        """Enqueue one epoch (the replay, or -- a draw that does not fit the static capacity -- the same program with eager launches);
-        returns the device tensors holding its (losses, hit counts)."""
-        if self._overflow is not None:
-            return self._eager_step(self._overflow)
-        self.graph.replay()
-        return self.rep, self.correct
-
-    def _decode(self, vals):
+    def _decode(self, host_vals):
+        vals = host_vals.tolist()
         accs = tuple(vals[3 + i] / max(1, self.prob.split_sizes[k]) for i, k in enumerate(("train", "valid", "test")))
         return finish_losses(vals[:3], self.mode, self.hp), accs
-
-    def step(self):
-        """Replay one epoch; returns ((loss, loss_cls, loss_aux), (train, valid, test accuracies))."""
-        if getattr(self, "_pending", None) is not None:
-            raise RuntimeError("ShardedGraphedEpoch.step() after step_async(): call drain() first (an epoch's values are still in flight)")
-        rep, correct = self._launch()
-        self._draw()                                              # the next step's host draw overlaps the replay
-        vals = torch.cat([rep, correct]).tolist()                 # one device->host read per epoch
-        self._upload()
-        return self._decode(vals)
-
-    # the loop without an idle GPU between epochs (models.GraphedEpoch.step_async on shards): epoch k is launched -- collectives included --
-    # before the host reads the values of epoch k - 1; same replays, same draws in the same order on every rank
-    def step_async(self):
-        """Launch one epoch and return the values of the PREVIOUS ``step_async`` epoch (None on the first call); ``drain()`` hands out
-        the last one."""
-        if getattr(self, "_res_host", None) is None:
-            self._res_host = [torch.zeros(6, dtype=torch.float32).pin_memory() for _ in range(2)]
-            self._res_done, self._pending, self._k = [None, None], None, 0
-        slot = self._k & 1
-        self._k += 1
-        rep, correct = self._launch()
-        self._res_host[slot].copy_(torch.cat([rep, correct]).to(torch.float32), non_blocking=True)
-        done = torch.cuda.Event()
-        done.record()
-        self._res_done[slot] = done
-        self._draw()
-        self._upload()
-        prev, self._pending = self._pending, slot
-        return None if prev is None else self._values(prev)
-
-    def _values(self, slot):
-        self._res_done[slot].synchronize()
-        return self._decode(self._res_host[slot].tolist())
-
-    def drain(self):
-        prev, self._pending = getattr(self, "_pending", None), None
-        return None if prev is None else self._values(prev)
 
 
 # ------------------------------------------------------------------------------------------------

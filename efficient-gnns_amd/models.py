@@ -7,6 +7,7 @@ signatures, ``convs`` / ``bns`` state_dict keys, ``.out_feat`` side channel); ``
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -307,7 +308,146 @@ def evaluate(model, x, adj_t, y, split_idx):
     return out, tuple(accs.tolist())
 
 
-class GraphedEpoch:
+class ReplayedEpoch:
+    """An epoch captured ONCE as a hipGraph and replayed, with the per-step host randomness staged around the replays -- the part
+    ``GraphedEpoch`` (one GPU) and ``dist.ShardedGraphedEpoch`` (a rank's shard) share.  The host draws of a step (the criterion's
+    row sample, the dropout seed) go to pinned staging buffers and are uploaded stream-ordered into static device buffers the
+    captured kernels read; the epoch's values are read back once per epoch.  A subclass supplies the capture hooks
+    (``_installed``), the pick (``_draw_pick`` / ``_upload_pick``), the launch (``_launch``: the device tensor of the epoch's
+    values), their decoding (``_decode``) and the structural graph check (``_check_graph``)."""
+
+    capture_error_mode = "global"      # torch.cuda.graph's default
+
+    def __init__(self, dev, n_pick: int, res_numel: int, res_dtype):
+        self.n_pick = n_pick
+        self._pick_dev = torch.zeros(max(n_pick, 1), dtype=torch.int64, device=dev)
+        self._pick_host = torch.zeros(max(n_pick, 1), dtype=torch.int64).pin_memory()
+        self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        self._uploaded = None             # event behind the last upload of the staging buffers
+        # step_async: two pinned host slots for the epoch's values (shape and dtype of the ``_launch`` result)
+        self._res_host = [torch.zeros(res_numel, dtype=res_dtype).pin_memory() for _ in range(2)]
+        self._res_done = [None, None]
+        self._pending = None              # slot of the epoch whose values have not been handed out yet
+        self._k = 0
+        self.replay_events = None         # set to a list to collect (start, end) HIP events around every launch of step_async (bench.py)
+
+    def _capture(self, body, dev, warmup):
+        """Warm-up, capture and instantiation of ``body``; returns what the captured ``body`` returned (its static outputs)."""
+        from ._audit import CaptureAudit
+        what = type(self).__name__
+        # every cached structure the captured launches read through raw pointers (edge plans, composed edge lists, inverse row maps,
+        # normalised adjacencies) stays alive with this object, whatever the caches evict later (_cache.pinning)
+        with _cache.pinning() as self._pinned:
+            # warm-up on a side stream (allocator, optimizer state, cached structures), as graph capture requires
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side), self._installed():
+                for i in range(warmup):
+                    self._refresh(require_fit=True)
+                    if i == warmup - 1:
+                        # the step about to be captured must not contain a long torch reduction (see _audit.py: their semaphore memset
+                        # node was seen not to take effect in replays -- outputs silently stale)
+                        with CaptureAudit() as audit:
+                            body()
+                        audit.check(what)
+                    else:
+                        body()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            torch.cuda.synchronize(dev)
+            # The graph is KEPT after capture and read back through the HIP runtime before it is instantiated (``_check_graph``): a
+            # memset / memcpy / host node is what an ATen operator with hidden scratch traffic leaves behind (the semaphore memset of
+            # a long reduction, sort / index_add_ / bincount scratch, zero_() on some paths) -- the class of node that was seen not to
+            # take effect in replays (_audit.py).  Structural and always on: it also catches operators CaptureAudit's name list does
+            # not know.
+            self.graph = torch.cuda.CUDAGraph(keep_graph=True)
+            with self._installed():
+                self._refresh(require_fit=True)
+                torch.cuda.synchronize(dev)
+                with torch.cuda.graph(self.graph, capture_error_mode=self.capture_error_mode):
+                    outs = body()
+            self.node_kinds = self._check_graph()
+            self.graph.instantiate()
+            torch.cuda.synchronize(dev)
+            self._refresh()                                    # randomness of the first replay
+        return outs
+
+    def _draw(self, require_fit: bool = False):
+        """The per-step host randomness (the reference's one ``np.random.choice`` per step, the dropout seed), drawn into
+        pinned staging buffers.  ``require_fit``: warm-up / capture (see dist.ShardedGraphedEpoch._draw_pick)."""
+        if self._uploaded is not None:
+            self._uploaded.synchronize()     # the previous upload has read the pinned buffers (it sits in front of the replay: microseconds)
+        self._draw_pick(require_fit)
+        self._seed_host.random_()
+        self._seed_host.bitwise_and_(0x3FFFFFFFFFFFFFFF)
+
+    def _upload(self):
+        """Staging buffers -> the static device buffers the captured kernels read (stream-ordered: after the last replay)."""
+        self._upload_pick()
+        self._seed_dev.copy_(self._seed_host, non_blocking=True)
+        # only stream-ordered: ``_draw`` must not rewrite the pinned buffers before the DMA has read them
+        self._uploaded = torch.cuda.Event()
+        self._uploaded.record()
+
+    def _refresh(self, require_fit: bool = False):
+        self._draw(require_fit)
+        self._upload()
+
+    def redraw(self):
+        """Discard the randomness prepared for the next replay and draw it again (after re-seeding NumPy / torch)."""
+        torch.cuda.current_stream().synchronize()
+        self._refresh()
+
+    def step(self):
+        """Replay one epoch; returns ((loss, loss_cls, loss_aux), (train, valid, test accuracies) | None).  The host draw for
+        the NEXT step (np.random.choice of 16 384 of 90 941 rows costs ~1 ms) runs while this replay executes."""
+        if self._pending is not None:
+            raise RuntimeError(f"{type(self).__name__}.step() after step_async(): call drain() first (an epoch's values are still in flight)")
+        res = self._launch()
+        self._draw()                                            # overlapped with the replay; uploaded after the read below
+        vals = self._decode(res.cpu())                          # one device->host read per epoch
+        self._upload()
+        return vals
+
+    # -- the loop without an idle GPU between epochs --------------------------------------------------------------------------------
+    # ``step()`` reads the epoch's values right after its replay: the GPU idles from the end of replay k until the host has woken up,
+    # uploaded the next draw and launched replay k + 1 (measured on the headline workload: 0.3-0.4 ms of a 7.2 ms epoch).  Nothing in
+    # replay k + 1 depends on the VALUES of epoch k (the row sample and the dropout seed are host draws; gnn.py:333-340 only logs the
+    # losses and accuracies), so ``step_async()`` launches replay k first and reads the values of epoch k - 1 afterwards: same
+    # replays, same draws in the same order, every epoch's values still read by the host -- one call later.
+    def _values(self, slot):
+        self._res_done[slot].synchronize()
+        return self._decode(self._res_host[slot])
+
+    def step_async(self):
+        """Launch one epoch and return the values of the PREVIOUS ``step_async`` epoch (None on the first call): the randomness of this
+        replay was drawn during the previous one and is uploaded stream-ordered in front of it; its values travel to a pinned host
+        slot behind it.  ``drain()`` hands out the values of the last epoch launched."""
+        slot = self._k & 1
+        self._k += 1
+        if self.replay_events is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        res = self._launch()
+        if self.replay_events is not None:
+            e1.record()
+            self.replay_events.append((e0, e1))
+        self._res_host[slot].copy_(res, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self._res_done[slot] = done
+        self._draw()                      # host draw of the NEXT epoch, overlapped with this replay
+        self._upload()                    # stream-ordered behind this replay: the static buffers change after it has read them
+        prev, self._pending = self._pending, slot
+        return None if prev is None else self._values(prev)
+
+    def drain(self):
+        """Values of the last epoch launched by ``step_async`` (None if they were handed out already)."""
+        prev, self._pending = self._pending, None
+        return None if prev is None else self._values(prev)
+
+
+class GraphedEpoch(ReplayedEpoch):
     """One epoch of the reference loop (gnn.py:333-340: ``train()`` then ``test()``) captured ONCE as a hipGraph and
     replayed: the ~180 kernel launches of an epoch are enqueued by one call, the GPU never waits for the host between
     them.  Same kernels, same arithmetic, same RNG coupling as ``train_step`` + ``evaluate``:
@@ -325,17 +465,12 @@ class GraphedEpoch:
         self.mode, self.hp = mode, hp
         self.n_train = train_idx.numel()
         S = hp.get("max_samples", 0) if mode in ("nce", "gpw") else 0
-        self.n_pick = S if 0 < S < self.n_train else 0
         dev = x.device
-        self._pick_dev = torch.zeros(max(self.n_pick, 1), dtype=torch.int64, device=dev)
-        self._pick_host = torch.zeros(max(self.n_pick, 1), dtype=torch.int64).pin_memory()
-        self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
-        args = (model, x, adj_t, y, train_idx, optimizer, mode, hp, teacher_out_feat, teacher_logits, student_proj, teacher_proj,
-                edge_index, kd_and_aux)
-
         # the epoch's six scalars side by side in ONE 40-byte device buffer (three float32 losses at byte 0, three float64 accuracies at
         # byte 16), written by the kernels that produce them: one device->host copy per epoch, no gather launch
+        super().__init__(dev, S if 0 < S < self.n_train else 0, 40, torch.uint8)
+        args = (model, x, adj_t, y, train_idx, optimizer, mode, hp, teacher_out_feat, teacher_logits, student_proj, teacher_proj,
+                edge_index, kd_and_aux)
         self._res_bytes = torch.zeros(40, dtype=torch.uint8, device=dev)
         res_losses, res_accs = self._res_bytes[:12].view(torch.float32), self._res_bytes[16:].view(torch.float64)
 
@@ -346,163 +481,45 @@ class GraphedEpoch:
             out, accs = evaluate_tensors(model, x, adj_t, y, split_idx, accs_out=res_accs)
             return losses, out, accs
         self._body = body
-        # every cached structure the captured launches read through raw pointers (edge plans, composed edge lists, inverse row maps,
-        # normalised adjacencies) stays alive with this object, whatever the caches evict later (_cache.pinning)
-        self._pin_ctx = _cache.pinning()
-        self._pinned = self._pin_ctx.__enter__()
-        try:
-            self._capture(body, dev, warmup)
-        finally:
-            self._pin_ctx.__exit__(None, None, None)
+        self.losses, self.out, self.accs = self._capture(body, dev, warmup)
 
-    def _capture(self, body, dev, warmup):
-        # warm-up on a side stream (allocator, optimizer state, cached structures), as graph capture requires
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side), self._installed():
-            for i in range(warmup):
-                self._refresh()
-                if i == warmup - 1:
-                    # the step about to be captured must not contain a long torch reduction (see _audit.py: their semaphore memset
-                    # node was seen not to take effect in replays -- outputs silently stale)
-                    from ._audit import CaptureAudit
-                    with CaptureAudit() as audit:
-                        body()
-                    audit.check("GraphedEpoch")
-                else:
-                    body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        # The graph is KEPT after capture and read back through the HIP runtime before it is instantiated: the shipped epochs are chains
-        # of kernel nodes only.  A memset / memcpy / host node is what an ATen operator with hidden scratch traffic leaves behind (the
-        # semaphore memset of a long reduction, sort / index_add_ / bincount scratch, zero_() on some paths) -- the class of node that was
-        # seen not to take effect in replays (_audit.py).  Structural and always on: it also catches operators CaptureAudit's name
-        # list does not know.
+    def _check_graph(self):
+        # the single-GPU epoch is a chain of kernel nodes only
         from ._audit import check_captured_graph
-        self.graph = torch.cuda.CUDAGraph(keep_graph=True)
-        with self._installed():
-            self._refresh()
-            torch.cuda.synchronize(dev)
-            with torch.cuda.graph(self.graph):
-                self.losses, self.out, self.accs = body()
-        self.node_kinds = check_captured_graph(self.graph, "GraphedEpoch", kernels_only=True)
-        self.graph.instantiate()
-        torch.cuda.synchronize(dev)
-        self._refresh()                                        # randomness of the first replay
+        return check_captured_graph(self.graph, "GraphedEpoch", kernels_only=True)
 
-    class _Install:
-        def __init__(self, owner):
-            self.o = owner
-
-        def __enter__(self):
-            self.prev = (C._ROW_SAMPLER, ops._DROPOUT_SEED_DEV)
-            o = self.o
-
-            def sampler(n, S, device):
-                if S >= n:
-                    return None
-                if n != o.n_train or S != o.n_pick:
-                    raise RuntimeError(f"GraphedEpoch was captured for {o.n_pick} of {o.n_train} rows, the criterion asks for {S} of {n}")
-                return o._pick_dev
-            C._ROW_SAMPLER = sampler
-            ops._DROPOUT_SEED_DEV = o._seed_dev
-
-        def __exit__(self, *exc):
-            C._ROW_SAMPLER, ops._DROPOUT_SEED_DEV = self.prev
-
+    @contextlib.contextmanager
     def _installed(self):
-        return GraphedEpoch._Install(self)
+        prev = (C._ROW_SAMPLER, ops._DROPOUT_SEED_DEV)
 
-    def _draw(self):
-        """The per-step host randomness (the reference's one ``np.random.choice`` per step, the dropout seed), drawn into
-        pinned staging buffers."""
-        import numpy as np
-        if getattr(self, "_uploaded", None) is not None:
-            self._uploaded.synchronize()     # the previous upload has read the pinned buffers (it sits in front of the replay: microseconds)
+        def sampler(n, S, device):
+            if S >= n:
+                return None
+            if n != self.n_train or S != self.n_pick:
+                raise RuntimeError(f"GraphedEpoch was captured for {self.n_pick} of {self.n_train} rows, the criterion asks for {S} of {n}")
+            return self._pick_dev
+        C._ROW_SAMPLER, ops._DROPOUT_SEED_DEV = sampler, self._seed_dev
+        try:
+            yield
+        finally:
+            C._ROW_SAMPLER, ops._DROPOUT_SEED_DEV = prev
+
+    def _draw_pick(self, require_fit):
         if self.n_pick:
+            import numpy as np
             self._pick_host.copy_(torch.from_numpy(np.random.choice(self.n_train, self.n_pick, replace=False)))
-        self._seed_host.random_()
-        self._seed_host.bitwise_and_(0x3FFFFFFFFFFFFFFF)
 
-    def _upload(self):
-        """Staging buffers -> the static device buffers the captured kernels read (stream-ordered: after the last replay)."""
+    def _upload_pick(self):
         if self.n_pick:
             self._pick_dev.copy_(self._pick_host, non_blocking=True)
-        self._seed_dev.copy_(self._seed_host, non_blocking=True)
-        # only stream-ordered: ``_draw`` must not rewrite the pinned buffers before the DMA has read them
-        self._uploaded = torch.cuda.Event()
-        self._uploaded.record()
 
-    def _refresh(self):
-        self._draw()
-        self._upload()
-
-    def redraw(self):
-        """Discard the randomness prepared for the next replay and draw it again (after re-seeding NumPy / torch)."""
-        torch.cuda.current_stream().synchronize()
-        self._refresh()
-
-    # -- the loop without an idle GPU between epochs --------------------------------------------------------------------------------
-    # ``step()`` reads the epoch's values right after its replay: the GPU idles from the end of replay k until the host has woken up,
-    # uploaded the next draw and launched replay k + 1 (measured on the headline workload: 0.3-0.4 ms of a 7.2 ms epoch).  Nothing in
-    # replay k + 1 depends on the VALUES of epoch k (the row sample and the dropout seed are host draws; gnn.py:333-340 only logs the
-    # losses and accuracies), so ``step_async()`` launches replay k first and reads the values of epoch k - 1 afterwards: same
-    # replays, same draws in the same order, every epoch's values still read by the host -- one call later.
-    def _slots(self):
-        if getattr(self, "_res_host", None) is None:
-            self._res_host = [torch.zeros(40, dtype=torch.uint8).pin_memory() for _ in range(2)]
-            self._res_done = [None, None]
-            self._pending = None          # slot of the epoch whose values have not been handed out yet
-            self._k = 0
-            self.replay_events = None     # set to a list to collect (start, end) HIP events around every replay (bench.py)
-        return self._res_host
+    def _launch(self):
+        self.graph.replay()
+        return self._res_bytes
 
     def _decode(self, host_bytes):
         losses = tuple(host_bytes[:12].view(torch.float32).tolist())
         return (losses, None) if self.accs is None else (losses, tuple(host_bytes[16:].view(torch.float64).tolist()))
-
-    def _values(self, slot):
-        self._res_done[slot].synchronize()
-        return self._decode(self._res_host[slot])
-
-    def step_async(self):
-        """Launch one epoch and return the values of the PREVIOUS ``step_async`` epoch (None on the first call): the randomness of this
-        replay was drawn during the previous one and is uploaded stream-ordered in front of it; its losses / accuracies travel to a
-        pinned host slot behind it.  ``drain()`` hands out the values of the last epoch launched."""
-        self._slots()
-        slot = self._k & 1
-        self._k += 1
-        if self.replay_events is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        self.graph.replay()
-        if self.replay_events is not None:
-            e1.record()
-            self.replay_events.append((e0, e1))
-        self._res_host[slot].copy_(self._res_bytes, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record()
-        self._res_done[slot] = done
-        self._draw()                      # host draw of the NEXT epoch, overlapped with this replay
-        self._upload()                    # stream-ordered behind this replay: the static buffers change after it has read them
-        prev, self._pending = self._pending, slot
-        return None if prev is None else self._values(prev)
-
-    def drain(self):
-        """Values of the last epoch launched by ``step_async`` (None if they were handed out already)."""
-        prev, self._pending = getattr(self, "_pending", None), None
-        return None if prev is None else self._values(prev)
-
-    def step(self):
-        """Replay one epoch; returns ((loss, loss_cls, loss_aux), (train, valid, test accuracies) | None).  The host draw for
-        the NEXT step (np.random.choice of 16 384 of 90 941 rows costs ~1 ms) runs while this replay executes."""
-        if getattr(self, "_pending", None) is not None:
-            raise RuntimeError("GraphedEpoch.step() after step_async(): call drain() first (an epoch's values are still in flight)")
-        self.graph.replay()
-        self._draw()                                            # overlapped with the replay; uploaded after the read below
-        vals = self._decode(self._res_bytes.cpu())              # one device->host read per epoch
-        self._upload()
-        return vals
 
 
 class GAT(nn.Module):

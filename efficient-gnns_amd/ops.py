@@ -1040,34 +1040,48 @@ def _bn_shape_ok(x: Tensor) -> bool:
     return x.is_cuda and C % 4 == 0 and C <= 1024 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
 
 
+def _bn_act_fwd(x, gamma, beta, mean, var, eps, relu, p, seed, seed_dev, pick=None) -> Tensor:
+    """y = drop(relu(bn(x))) with the given statistics: every row, or only the rows ``pick`` (egnn_bn_act_rows_fwd_f32).  An empty
+    result (a shard without rows, an empty ``pick``) launches nothing."""
+    n, C = x.shape
+    y = torch.empty(n if pick is None else pick.numel(), C, dtype=torch.float32, device=x.device)
+    if y.shape[0] == 0:
+        return y
+    if pick is None:
+        rc = _lib.load().egnn_bn_act_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), float(eps), _lib.ptr(gamma),
+                                             _lib.ptr(beta), int(relu), float(p), int(seed), _lib.ptr(seed_dev), _lib.ptr(y), y.stride(0),
+                                             _lib.stream())
+        _lib.check(rc, "egnn_bn_act_fwd_f32")
+    else:
+        rc = _lib.load().egnn_bn_act_rows_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), pick.numel(), _lib.ptr(mean), _lib.ptr(var),
+                                                  float(eps), _lib.ptr(gamma), _lib.ptr(beta), int(relu), float(p), int(seed),
+                                                  _lib.ptr(seed_dev), _lib.ptr(y), y.stride(0), _lib.stream())
+        _lib.check(rc, "egnn_bn_act_rows_fwd_f32")
+    return y
+
+
 class _BnAct(torch.autograd.Function):
-    """``pick`` (int64 [S], unique row ids) = form only the output rows ``pick``: y[i] = act(bn(x[pick[i]])) -- the statistics still span
-    all rows of x, and so does dx (egnn_bn_act_rows_*_f32)."""
+    """y = drop(relu(bn(x))) with the statistics (mean, var) taken by the caller.  ``pick`` (int64 [S], unique row ids) = form only the
+    output rows ``pick``: y[i] = act(bn(x[pick[i]])) -- the statistics still span all rows of x, and so does dx (egnn_bn_act_rows_*_f32).
+    ``sync`` = None: statistics of this tensor alone.  ``sync`` = (total rows [1] on the device, group): statistics of the rows of ALL
+    ranks (``_sync_stats``; node-range shards, where ``pick`` may hold no row of this shard) -- the backward all-reduces
+    [sum d, sum d*xhat] between its reduce half and its apply half; the parameter gradients stay this shard's local sums."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, mean, var, eps, relu, p, seed, batch_stats, pick=None):
+    def forward(ctx, x, gamma, beta, mean, var, eps, relu, p, seed, batch_stats, pick=None, sync=None):
         if not x.is_cuda:    # (the kernels take device pointers: a host tensor must never reach a launch)
             raise RuntimeError(f"bn_act: the HIP kernels need a GPU tensor, got one on {x.device}")
         x = _rowmajor(x)
-        n, C = x.shape
-        seed_dev = _DROPOUT_SEED_DEV if p > 0 else None
-        if pick is None:
-            y = torch.empty(n, C, dtype=torch.float32, device=x.device)
-            rc = _lib.load().egnn_bn_act_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), float(eps), _lib.ptr(gamma),
-                                                 _lib.ptr(beta), int(relu), float(p), int(seed), _lib.ptr(seed_dev), _lib.ptr(y), y.stride(0),
-                                                 _lib.stream())
-            _lib.check(rc, "egnn_bn_act_fwd_f32")
-        else:
-            if pick.dtype != torch.int64 or pick.dim() != 1 or not pick.is_contiguous() or pick.numel() > n or pick.numel() == 0:
-                raise ValueError("bn_act: `pick` must be a non-empty contiguous 1-D int64 tensor of unique row ids")
-            y = torch.empty(pick.numel(), C, dtype=torch.float32, device=x.device)
-            rc = _lib.load().egnn_bn_act_rows_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), pick.numel(), _lib.ptr(mean), _lib.ptr(var),
-                                                      float(eps), _lib.ptr(gamma), _lib.ptr(beta), int(relu), float(p), int(seed),
-                                                      _lib.ptr(seed_dev), _lib.ptr(y), y.stride(0), _lib.stream())
-            _lib.check(rc, "egnn_bn_act_rows_fwd_f32")
+        n = x.shape[0]
+        if pick is not None and (pick.dtype != torch.int64 or pick.dim() != 1 or not pick.is_contiguous() or pick.numel() > n
+                                 or (sync is None and pick.numel() == 0)):
+            raise ValueError("bn_act: `pick` must be a non-empty contiguous 1-D int64 tensor of unique row ids" if sync is None else
+                             "sync_bn_act: `pick` must be a contiguous 1-D int64 tensor of unique row ids")
+        seed_dev = _DROPOUT_SEED_DEV if p > 0 else None     # the per-step seed of a replayed graph (fresh masks in every replay)
+        y = _bn_act_fwd(x, gamma, beta, mean, var, eps, relu, p, seed, seed_dev, pick)
         ctx.save_for_backward(x, gamma, beta, mean, var, *([] if pick is None else [pick]))
         ctx.cfg = (float(eps), int(relu), float(p), int(seed), int(batch_stats))
-        ctx.seed_dev = seed_dev
+        ctx.seed_dev, ctx.sync = seed_dev, sync
         return y
 
     @staticmethod
@@ -1078,29 +1092,73 @@ class _BnAct(torch.autograd.Function):
         gy = _rowmajor(gy)
         n, C = x.shape
         lib, dev = _lib.load(), x.device
-        dx = torch.empty_like(x)
-        dgamma = torch.empty(C, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(C, dtype=torch.float32, device=dev)
+        if ctx.sync is None:
+            # statistics of this tensor alone: one backward launch, no collective between its halves
+            dx = torch.empty_like(x)
+            dgamma = torch.empty(C, dtype=torch.float32, device=dev)
+            dbeta = torch.empty(C, dtype=torch.float32, device=dev)
+            nws = lib.egnn_bn_ws_floats(C)
+            ws = torch.empty(nws, dtype=torch.float32, device=dev)
+            # the producer of x usually added a bias (GCNConv / nn.Linear in front of the BatchNorm): its gradient is the column
+            # sum of dx, formed in the same pass (ops.colsum picks the tag up)
+            cs = torch.empty(C, dtype=torch.float32, device=dev) if batch_stats else None
+            if pick is None:
+                rc = lib.egnn_bn_act_bwd_colsum_f32(_lib.ptr(x), x.stride(0), _lib.ptr(gy), gy.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), eps,
+                                                    _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev), batch_stats,
+                                                    _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dx), dx.stride(0), _lib.ptr(cs), _lib.ptr(ws), nws,
+                                                    _lib.stream())
+                _lib.check(rc, "egnn_bn_act_bwd_colsum_f32")
+            else:
+                rc = lib.egnn_bn_act_rows_bwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), pick.numel(), _lib.ptr(gy), gy.stride(0),
+                                                  _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed,
+                                                  _lib.ptr(ctx.seed_dev), batch_stats, _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dx), dx.stride(0),
+                                                  _lib.ptr(cs), _lib.ptr(ws), nws, _lib.stream())
+                _lib.check(rc, "egnn_bn_act_rows_bwd_f32")
+            if cs is not None:
+                dx._egnn_colsum = (cs, dx._version)
+            return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None
+        # all ranks: reduce half, ONE all-reduce of [sum d | sum d*xhat], apply half
+        import torch.distributed as dist
+        total, group = ctx.sync
+        n_red = n if pick is None else pick.numel()                  # rows that carry a gradient
+        sums = torch.empty(2 * C, dtype=torch.float32, device=dev)   # [dbeta | dgamma] of this shard
         nws = lib.egnn_bn_ws_floats(C)
-        ws = torch.empty(nws, dtype=torch.float32, device=dev)
-        # the producer of x usually added a bias (GCNConv / nn.Linear in front of the BatchNorm): its gradient is the column
-        # sum of dx, formed in the same pass (ops.colsum picks the tag up)
-        cs = torch.empty(C, dtype=torch.float32, device=dev) if batch_stats else None
-        if pick is None:
-            rc = lib.egnn_bn_act_bwd_colsum_f32(_lib.ptr(x), x.stride(0), _lib.ptr(gy), gy.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), eps,
-                                                _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev), batch_stats,
-                                                _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dx), dx.stride(0), _lib.ptr(cs), _lib.ptr(ws), nws,
-                                                _lib.stream())
-            _lib.check(rc, "egnn_bn_act_bwd_colsum_f32")
+        ws = torch.empty(nws, dtype=torch.float32, device=dev) if n > 0 else None
+        if n_red > 0 and pick is None:
+            rc = lib.egnn_bn_act_bwd_reduce_f32(_lib.ptr(x), x.stride(0), _lib.ptr(gy), gy.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var),
+                                                eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev), _lib.ptr(sums[C:]),
+                                                _lib.ptr(sums), _lib.ptr(ws), nws, _lib.stream())
+            _lib.check(rc, "egnn_bn_act_bwd_reduce_f32")
+        elif n_red > 0:
+            rc = lib.egnn_bn_act_rows_bwd_reduce_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), n_red, _lib.ptr(gy), gy.stride(0),
+                                                     _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed,
+                                                     _lib.ptr(ctx.seed_dev), _lib.ptr(sums[C:]), _lib.ptr(sums), _lib.ptr(ws), nws, _lib.stream())
+            _lib.check(rc, "egnn_bn_act_rows_bwd_reduce_f32")
         else:
-            rc = lib.egnn_bn_act_rows_bwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), pick.numel(), _lib.ptr(gy), gy.stride(0),
-                                              _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed,
-                                              _lib.ptr(ctx.seed_dev), batch_stats, _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dx), dx.stride(0),
-                                              _lib.ptr(cs), _lib.ptr(ws), nws, _lib.stream())
-            _lib.check(rc, "egnn_bn_act_rows_bwd_f32")
-        if cs is not None:
+            sums.zero_()
+        local = sums                                                 # parameter grads stay local (the flat all-reduce sums them)
+        if dist.get_world_size(group) > 1:
+            sums = sums.clone()
+            dist.all_reduce(sums, group=group)
+        scaled = sums / total                                        # scaled on the device (no host read of the row count)
+        dx = torch.empty_like(x)
+        if n > 0:
+            # the column sums of dx (bias gradient of the conv / Linear in front) come out of the same pass (ops.colsum picks the tag up)
+            cs = torch.empty(C, dtype=torch.float32, device=dev)
+            if pick is None:
+                rc = lib.egnn_bn_act_bwd_apply_colsum_f32(_lib.ptr(x), x.stride(0), _lib.ptr(gy), gy.stride(0), n, C, _lib.ptr(mean),
+                                                          _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev),
+                                                          _lib.ptr(scaled), _lib.ptr(scaled[C:]), 1.0, _lib.ptr(dx), dx.stride(0), _lib.ptr(cs),
+                                                          _lib.ptr(ws), nws, _lib.stream())
+                _lib.check(rc, "egnn_bn_act_bwd_apply_colsum_f32")
+            else:
+                rc = lib.egnn_bn_act_rows_bwd_apply_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), n_red, _lib.ptr(gy), gy.stride(0),
+                                                        _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed,
+                                                        _lib.ptr(ctx.seed_dev), _lib.ptr(scaled), _lib.ptr(scaled[C:]), 1.0, _lib.ptr(local),
+                                                        _lib.ptr(dx), dx.stride(0), _lib.ptr(cs), _lib.ptr(ws), nws, _lib.stream())
+                _lib.check(rc, "egnn_bn_act_rows_bwd_apply_f32")
             dx._egnn_colsum = (cs, dx._version)
-        return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
+        return dx, local[C:], local[:C], None, None, None, None, None, None, None, None, None
 
 
 def _bn_prepare(x: Tensor, bn, p: float, training: bool):
@@ -1171,38 +1229,40 @@ def _inverse_rows(idx: Tensor, n: int) -> Tensor:
     return _INV_ROWS.get((idx,), (n,), build)
 
 
+def _bn_act_linear_fwd(x, w, gamma, beta, mean, var, eps, relu, p, seed, seed_dev):
+    """(h, h @ w) for h = drop(relu(bn(x))) with the given statistics: one pass over x, h stored and multiplied by w while its pieces
+    are in registers (egnn_bn_act_linear_fwd_f32); where that kernel refuses the shape (EGNN_EALIGN), ``_bn_act_fwd`` + ``gemm_raw``.
+    A shard without rows launches nothing."""
+    n, C = x.shape
+    if n > 0 and w.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0:
+        h = torch.empty(n, C, dtype=torch.float32, device=x.device)
+        xw = torch.empty(n, w.shape[1], dtype=torch.float32, device=x.device)
+        rc = _lib.load().egnn_bn_act_linear_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), float(eps), _lib.ptr(gamma),
+                                                    _lib.ptr(beta), int(relu), float(p), int(seed), _lib.ptr(seed_dev), _lib.ptr(w), w.stride(0), 0,
+                                                    w.shape[1], _lib.ptr(h), h.stride(0), _lib.ptr(xw), xw.stride(0), _lib.stream())
+        if rc != _lib.EGNN_EALIGN:
+            _lib.check(rc, "egnn_bn_act_linear_fwd_f32")
+            return h, xw
+    h = _bn_act_fwd(x, gamma, beta, mean, var, eps, relu, p, seed, seed_dev)
+    return h, (gemm_raw(h, w, False, False) if n > 0 else torch.empty(0, w.shape[1], dtype=torch.float32, device=x.device))
+
+
 class _BnActLinear(torch.autograd.Function):
     """(h, h @ w) with h = drop(relu(bn(x))) and a NARROW w [C, Ks] (the class count): the student's last hidden layer feeding its
     output conv (gnn.py:47-52).  h also carries the gradient tap of ``grad_tap`` (the projection head's row-compact input gradient).
     Backward: dh = G w^T + tap rows (+ any dense gradient of h) is formed in MFMA tiles and goes through the BatchNorm backward
-    without being stored (egnn_skinny_dx_bn_bwd_f32): one pass over [n, C] instead of four."""
+    without being stored (egnn_skinny_dx_bn_bwd_f32): one pass over [n, C] instead of four.  ``sync``: as in ``_BnAct`` (all-rank
+    statistics; the backward's reduce and apply halves around ONE all-reduce, see ``_tail_backward``)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, mean, var, eps, relu, p, seed, batch_stats, w, box):
+    def forward(ctx, x, gamma, beta, mean, var, eps, relu, p, seed, batch_stats, w, box, sync=None):
         x = _rowmajor(x)
-        n, C = x.shape
-        h = torch.empty(n, C, dtype=torch.float32, device=x.device)
-        seed_dev = _DROPOUT_SEED_DEV if p > 0 else None
         w = _rowmajor(w)
-        lib = _lib.load()
-        rc = _lib.EGNN_EALIGN
-        if w.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0:
-            # one pass over x: h is stored and multiplied by w while its pieces are in registers
-            xw = torch.empty(n, w.shape[1], dtype=torch.float32, device=x.device)
-            rc = lib.egnn_bn_act_linear_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), float(eps), _lib.ptr(gamma),
-                                                _lib.ptr(beta), int(relu), float(p), int(seed), _lib.ptr(seed_dev), _lib.ptr(w), w.stride(0), 0,
-                                                w.shape[1], _lib.ptr(h), h.stride(0), _lib.ptr(xw), xw.stride(0), _lib.stream())
-            if rc != _lib.EGNN_EALIGN:
-                _lib.check(rc, "egnn_bn_act_linear_fwd_f32")
-        if rc == _lib.EGNN_EALIGN:
-            rc = lib.egnn_bn_act_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), float(eps), _lib.ptr(gamma),
-                                         _lib.ptr(beta), int(relu), float(p), int(seed), _lib.ptr(seed_dev), _lib.ptr(h), h.stride(0),
-                                         _lib.stream())
-            _lib.check(rc, "egnn_bn_act_fwd_f32")
-            xw = gemm_raw(h, w, False, False)
+        seed_dev = _DROPOUT_SEED_DEV if p > 0 else None
+        h, xw = _bn_act_linear_fwd(x, w, gamma, beta, mean, var, eps, relu, p, seed, seed_dev)
         ctx.save_for_backward(x, gamma, beta, mean, var, h, w)
         ctx.cfg = (float(eps), int(relu), float(p), int(seed), int(batch_stats))
-        ctx.seed_dev, ctx.box, ctx.w_index = seed_dev, box, 10
+        ctx.seed_dev, ctx.box, ctx.w_index, ctx.sync = seed_dev, box, 10, sync
         ctx.set_materialize_grads(False)
         return h, xw
 
@@ -1210,8 +1270,8 @@ class _BnActLinear(torch.autograd.Function):
     def backward(ctx, g_h, g_xw):
         x, gamma, beta, mean, var, h, w = ctx.saved_tensors
         eps, relu, p, seed, batch_stats = ctx.cfg
-        dx, dgamma, dbeta, gw = _tail_backward(ctx, g_h, g_xw, x, gamma, beta, mean, var, h, w, eps, relu, p, seed, batch_stats, None)
-        return dx, dgamma, dbeta, None, None, None, None, None, None, None, gw, None
+        dx, dgamma, dbeta, gw = _tail_backward(ctx, g_h, g_xw, x, gamma, beta, mean, var, h, w, eps, relu, p, seed, batch_stats, ctx.sync)
+        return dx, dgamma, dbeta, None, None, None, None, None, None, None, gw, None, None
 
 
 def _tail_backward(ctx, g_h, g_xw, x, gamma, beta, mean, var, h, w, eps, relu, p, seed, batch_stats, sync):
@@ -1378,152 +1438,33 @@ def _sync_stats(x: Tensor, group):
     return mean, var, total
 
 
-class _SyncBnAct(torch.autograd.Function):
-    """Two small collectives per direction: the per-shard (n, mean, var) triples are all-gathered and merged (``_sync_stats``); the
-    backward all-reduces [sum d, sum d*xhat].  ``pick`` (unique int64 row ids, may be empty): only those output rows are formed
-    (egnn_bn_act_rows_fwd_f32) -- the statistics, and dx, still span every row of every rank (the projection heads under a sampled
-    criterion, gnn.py:296-306 -> criterion.py:62-65,134-137)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps, relu, p, seed, group, pick=None):
-        x = _rowmajor(x)
-        n, C = x.shape
-        lib, dev = _lib.load(), x.device
-        mean, var, total = _sync_stats(x, group)
-        seed_dev = _DROPOUT_SEED_DEV if p > 0 else None     # the per-step seed of a replayed graph (fresh masks in every replay)
-        if pick is None:
-            y = torch.empty(n, C, dtype=torch.float32, device=dev)
-            if n > 0:
-                rc = lib.egnn_bn_act_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), float(eps), _lib.ptr(gamma),
-                                             _lib.ptr(beta), int(relu), float(p), int(seed), _lib.ptr(seed_dev), _lib.ptr(y), y.stride(0), _lib.stream())
-                _lib.check(rc, "egnn_bn_act_fwd_f32")
-        else:
-            if pick.dtype != torch.int64 or pick.dim() != 1 or not pick.is_contiguous() or pick.numel() > n:
-                raise ValueError("sync_bn_act: `pick` must be a contiguous 1-D int64 tensor of unique row ids")
-            y = torch.empty(pick.numel(), C, dtype=torch.float32, device=dev)
-            if pick.numel() > 0:
-                rc = lib.egnn_bn_act_rows_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), pick.numel(), _lib.ptr(mean), _lib.ptr(var),
-                                                  float(eps), _lib.ptr(gamma), _lib.ptr(beta), int(relu), float(p), int(seed), _lib.ptr(seed_dev),
-                                                  _lib.ptr(y), y.stride(0), _lib.stream())
-                _lib.check(rc, "egnn_bn_act_rows_fwd_f32")
-        ctx.save_for_backward(x, gamma, beta, mean, var, total, *([] if pick is None else [pick]))
-        ctx.cfg = (float(eps), int(relu), float(p), int(seed), group)
-        ctx.seed_dev = seed_dev
-        ctx.mark_non_differentiable(mean, var, total)
-        return y, mean, var, total
-
-    @staticmethod
-    def backward(ctx, gy, _gm, _gv, _gt):
-        import torch.distributed as dist
-        x, gamma, beta, mean, var, total = ctx.saved_tensors[:6]
-        pick = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
-        eps, relu, p, seed, group = ctx.cfg
-        gy = _rowmajor(gy)
-        n, C = x.shape
-        lib, dev = _lib.load(), x.device
-        n_red = n if pick is None else pick.numel()                  # rows that carry a gradient
-        sums = torch.empty(2 * C, dtype=torch.float32, device=dev)   # [dbeta | dgamma] of this shard
-        nws = lib.egnn_bn_ws_floats(C)
-        ws = torch.empty(nws, dtype=torch.float32, device=dev) if n > 0 else None
-        if n_red > 0 and pick is None:
-            rc = lib.egnn_bn_act_bwd_reduce_f32(_lib.ptr(x), x.stride(0), _lib.ptr(gy), gy.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var),
-                                                eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev), _lib.ptr(sums[C:]),
-                                                _lib.ptr(sums), _lib.ptr(ws), nws, _lib.stream())
-            _lib.check(rc, "egnn_bn_act_bwd_reduce_f32")
-        elif n_red > 0:
-            rc = lib.egnn_bn_act_rows_bwd_reduce_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), n_red, _lib.ptr(gy), gy.stride(0),
-                                                     _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed,
-                                                     _lib.ptr(ctx.seed_dev), _lib.ptr(sums[C:]), _lib.ptr(sums), _lib.ptr(ws), nws, _lib.stream())
-            _lib.check(rc, "egnn_bn_act_rows_bwd_reduce_f32")
-        else:
-            sums.zero_()
-        local = sums                                                 # parameter grads stay local (the flat all-reduce sums them)
-        if dist.get_world_size(group) > 1:
-            sums = sums.clone()
-            dist.all_reduce(sums, group=group)
-        scaled = sums / total                                        # scaled on the device (no host read of the row count)
-        dx = torch.empty_like(x)
-        if n > 0:
-            # the column sums of dx (bias gradient of the conv / Linear in front) come out of the same pass (ops.colsum picks the tag up)
-            cs = torch.empty(C, dtype=torch.float32, device=dev)
-            if pick is None:
-                rc = lib.egnn_bn_act_bwd_apply_colsum_f32(_lib.ptr(x), x.stride(0), _lib.ptr(gy), gy.stride(0), n, C, _lib.ptr(mean),
-                                                          _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev),
-                                                          _lib.ptr(scaled), _lib.ptr(scaled[C:]), 1.0, _lib.ptr(dx), dx.stride(0), _lib.ptr(cs),
-                                                          _lib.ptr(ws), nws, _lib.stream())
-                _lib.check(rc, "egnn_bn_act_bwd_apply_colsum_f32")
-            else:
-                rc = lib.egnn_bn_act_rows_bwd_apply_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), n_red, _lib.ptr(gy), gy.stride(0),
-                                                        _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed,
-                                                        _lib.ptr(ctx.seed_dev), _lib.ptr(scaled), _lib.ptr(scaled[C:]), 1.0, _lib.ptr(local),
-                                                        _lib.ptr(dx), dx.stride(0), _lib.ptr(cs), _lib.ptr(ws), nws, _lib.stream())
-                _lib.check(rc, "egnn_bn_act_rows_bwd_apply_f32")
-            dx._egnn_colsum = (cs, dx._version)
-        return dx, local[C:], local[:C], None, None, None, None, None, None
-
-
 def sync_bn_act(x: Tensor, bn, relu: bool, p: float, training: bool, group=None, pick: Tensor | None = None):
     """Training-mode dropout(relu(bn(x))) with all-rank statistics; returns (y, mean, biased var, total rows) so that the
     module can update its running statistics.  ``bn`` needs weight / bias / eps (dist.SyncBatchNorm1d).  ``pick``: only those rows of
-    the result (see _SyncBnAct)."""
+    the result (unique int64 row ids, may be empty; the statistics, and dx, still span every row of every rank -- the projection
+    heads under a sampled criterion, gnn.py:296-306 -> criterion.py:62-65,134-137).  Two small collectives per direction: the
+    statistics all-gather (``_sync_stats``) and the backward's all-reduce (``_BnAct``)."""
     drop = p if (training and p > 0) else 0.0
     seed = _draw_dropout_seed() if drop > 0 else 0
-    return _SyncBnAct.apply(x, bn.weight, bn.bias, bn.eps, relu, drop, seed, group, pick)
-
-
-class _SyncBnActLinear(torch.autograd.Function):
-    """``_BnActLinear`` with all-rank batch statistics: (h, h @ w, mean, var, total) for h = drop(relu(bn(x))) on a node-range shard.
-    Forward: statistics all-gather, then the one-pass tail kernel; backward: the tail's reduce half, ONE all-reduce of
-    [sum d | sum d xhat], the apply half (egnn_skinny_dx_bn_bwd_reduce_f32 / egnn_bn_bwd_apply_stored_f32)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps, relu, p, seed, w, box, group):
-        x = _rowmajor(x)
-        n, C = x.shape
-        lib, dev = _lib.load(), x.device
-        mean, var, total = _sync_stats(x, group)
-        seed_dev = _DROPOUT_SEED_DEV if p > 0 else None
-        w = _rowmajor(w)
-        h = torch.empty(n, C, dtype=torch.float32, device=dev)
-        xw = torch.empty(n, w.shape[1], dtype=torch.float32, device=dev)
-        if n > 0:
-            rc = _lib.EGNN_EALIGN
-            if w.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0:
-                rc = lib.egnn_bn_act_linear_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), float(eps), _lib.ptr(gamma),
-                                                    _lib.ptr(beta), int(relu), float(p), int(seed), _lib.ptr(seed_dev), _lib.ptr(w), w.stride(0), 0,
-                                                    w.shape[1], _lib.ptr(h), h.stride(0), _lib.ptr(xw), xw.stride(0), _lib.stream())
-                if rc != _lib.EGNN_EALIGN:
-                    _lib.check(rc, "egnn_bn_act_linear_fwd_f32")
-            if rc == _lib.EGNN_EALIGN:
-                _lib.check(lib.egnn_bn_act_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), float(eps), _lib.ptr(gamma),
-                                                   _lib.ptr(beta), int(relu), float(p), int(seed), _lib.ptr(seed_dev), _lib.ptr(h), h.stride(0),
-                                                   _lib.stream()), "egnn_bn_act_fwd_f32")
-                xw = gemm_raw(h, w, False, False)
-        ctx.save_for_backward(x, gamma, beta, mean, var, h, w, total)
-        ctx.cfg = (float(eps), int(relu), float(p), int(seed), group)
-        ctx.seed_dev, ctx.box, ctx.w_index = seed_dev, box, 7
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(mean, var, total)
-        return h, xw, mean, var, total
-
-    @staticmethod
-    def backward(ctx, g_h, g_xw, _gm, _gv, _gt):
-        x, gamma, beta, mean, var, h, w, total = ctx.saved_tensors
-        eps, relu, p, seed, group = ctx.cfg
-        dx, dgamma, dbeta, gw = _tail_backward(ctx, g_h, g_xw, x, gamma, beta, mean, var, h, w, eps, relu, p, seed, 1, (total, group))
-        return dx, dgamma, dbeta, None, None, None, None, gw, None, None
+    x = _rowmajor(x)
+    mean, var, total = _sync_stats(x, group)
+    y = _BnAct.apply(x, bn.weight, bn.bias, mean, var, bn.eps, relu, drop, seed, True, pick, (total, group))
+    return y, mean, var, total
 
 
 def sync_bn_act_linear(x: Tensor, bn, w: Tensor, relu: bool, p: float, training: bool, group=None):
     """(h, h @ w, mean, var, total) -- ``bn_act_linear`` with all-rank statistics (dist.SyncBatchNorm1d.fused_act_linear); None when
-    the fused kernels do not take the shape."""
+    the fused kernels do not take the shape.  Forward: statistics all-gather, then the one-pass tail kernel; backward: the tail's
+    reduce half, ONE all-reduce of [sum d | sum d xhat], the apply half."""
     if not (training and torch.is_grad_enabled() and x.is_cuda and x.dim() == 2 and w.dim() == 2 and w.shape[0] == x.shape[1]
             and w.shape[1] <= 64 and x.shape[1] % 64 == 0 and _bn_shape_ok(_rowmajor(x))):
         return None
     drop = p if p > 0 else 0.0
     seed = _draw_dropout_seed() if drop > 0 else 0
+    x = _rowmajor(x)
+    mean, var, total = _sync_stats(x, group)
     box = _TapBox()
-    h, xw, mean, var, total = _SyncBnActLinear.apply(x, bn.weight, bn.bias, bn.eps, relu, drop, seed, w, box, group)
+    h, xw = _BnActLinear.apply(x, bn.weight, bn.bias, mean, var, bn.eps, relu, drop, seed, True, w, box, (total, group))
     h._egnn_tap = box
     return h, xw, mean, var, total
 
