@@ -523,8 +523,8 @@ class GraphedEpoch(ReplayedEpoch):
 
 
 class GAT(nn.Module):
-    """The PPI GAT teacher (/root/reference/ppi_pyg/gnn.py:86-117), run frozen inside the student step (:208-209):
-    GATConv + linear skip per layer, ELU, dropout; the last layer averages its heads.  Inference only (nn.GATConv)."""
+    """The PPI GAT model (/root/reference/ppi_pyg/gnn.py:86-117, ``--gnn gat``), run frozen inside the student step (:208-209)
+    or trained: GATConv + linear skip per layer, ELU, dropout; the last layer averages its heads."""
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, dropout, heads=4):
         super().__init__()
@@ -632,9 +632,9 @@ def teacher_evaluate(model, graph, feat, labels, train_idx, val_idx, test_idx, n
 
 
 class TeacherNet(nn.Module):
-    """The PPI teacher checkpointed by the reference (/root/reference/ppi_pyg/gnn.py:23-47): 4 x 256 GAT layers with
-    linear skips, ELU, a 6-head averaging output layer; ``out_feat`` = second hidden.  Same attribute names (state_dict
-    keys ``conv1.*``, ``lin1.*``, ...) so that the reference's ``checkpoint.pt`` loads."""
+    """The PPI teacher checkpointed by the reference (/root/reference/ppi_pyg/gnn.py:23-47, trained by ppi_pyg/train_teacher.py):
+    4 x 256 GAT layers with linear skips, ELU, a 6-head averaging output layer; ``out_feat`` = second hidden.  Same attribute
+    names (state_dict keys ``conv1.*``, ``lin1.*``, ...) so that the reference's ``checkpoint.pt`` loads."""
 
     def __init__(self, in_channels, out_channels):
         super().__init__()
@@ -655,6 +655,39 @@ class TeacherNet(nn.Module):
         x = F.elu(self.conv2(x, edge_index) + ops.linear(x, self.lin2.weight, self.lin2.bias))
         self.out_feat = x
         return self.conv3(x, edge_index) + ops.linear(x, self.lin3.weight, self.lin3.bias)
+
+
+class StudentNet(nn.Module):
+    """The PPI GAT student (/root/reference/ppi_pyg/gnn.py:50-83, ``--gnn student``; the GAT-5L of the paper's PPI table): five
+    GATConv layers of 2 heads x 68 with linear skips and ELU, the last one averaging its heads; ``out_feat`` = fourth hidden.
+    Same attribute names (``conv1..5``, ``lin1..5``) and so the same state_dict keys as the reference."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.conv1 = GATConv(in_channels, 68, heads=2)
+        self.lin1 = nn.Linear(in_channels, 2 * 68)
+        self.conv2 = GATConv(2 * 68, 68, heads=2)
+        self.lin2 = nn.Linear(2 * 68, 2 * 68)
+        self.conv3 = GATConv(2 * 68, 68, heads=2)
+        self.lin3 = nn.Linear(2 * 68, 2 * 68)
+        self.conv4 = GATConv(2 * 68, 68, heads=2)
+        self.lin4 = nn.Linear(2 * 68, 2 * 68)
+        self.conv5 = GATConv(2 * 68, out_channels, heads=2, concat=False)
+        self.lin5 = nn.Linear(2 * 68, out_channels)
+        self.out_feat = None
+
+    def reset_parameters(self):
+        for k in range(1, 6):
+            getattr(self, f"conv{k}").reset_parameters()
+        for k in range(1, 6):
+            getattr(self, f"lin{k}").reset_parameters()
+
+    def forward(self, x, edge_index):
+        for k in range(1, 5):
+            conv, lin = getattr(self, f"conv{k}"), getattr(self, f"lin{k}")
+            x = F.elu(conv(x, edge_index) + ops.linear(x, lin.weight, lin.bias))
+        self.out_feat = x
+        return self.conv5(x, edge_index) + ops.linear(x, self.lin5.weight, self.lin5.bias)
 
 
 class RGCN(nn.Module):
@@ -721,11 +754,22 @@ class RGCN(nn.Module):
         return x_dict
 
 
-def ppi_train_epoch(model, teacher_model, graphs, optimizer, mode, hp):
-    """One PPI epoch (/root/reference/ppi_pyg/gnn.py:185-274): one optimisation step per batch graph; in ``kd`` mode the
-    frozen teacher's forward runs inside every step (:208-209).  ``graphs``: objects with x / edge_index / y.
+PPI_MODES = ("supervised", "kd", "fitnet", "at", "gpw", "lpw", "nce")
+
+
+def ppi_train_epoch(model, teacher_model, graphs, optimizer, mode, hp, student_proj=None, teacher_proj=None):
+    """One PPI epoch (/root/reference/ppi_pyg/gnn.py:185-274): one optimisation step per batch graph; in every mode but
+    ``supervised`` the frozen teacher's forward runs inside every step (:208-209).  ``graphs``: objects with x / edge_index / y.
+    ``fitnet`` / ``nce`` pass ``model.out_feat`` and ``teacher_model.out_feat`` through ``student_proj`` / ``teacher_proj``
+    (Linear + BatchNorm1d + ReLU, gnn.py:355-366: ``make_projection``); ``at`` / ``gpw`` / ``lpw`` compare them directly.
+    ``hp``: alpha / kd_T (kd), beta, kernel (gpw / lpw), max_samples (gpw / nce), nce_T (nce).
     Returns the epoch means (loss, loss_cls, loss_aux) like the reference."""
+    if mode not in PPI_MODES:
+        raise NotImplementedError(mode)
     model.train()
+    for m in (student_proj, teacher_proj):
+        if m is not None:
+            m.train()
     if teacher_model is not None:
         teacher_model.eval()
     tot = [0.0, 0.0, 0.0]
@@ -734,12 +778,26 @@ def ppi_train_epoch(model, teacher_model, graphs, optimizer, mode, hp):
         if mode == "supervised":
             loss = F.binary_cross_entropy_with_logits(out, g.y)
             loss_cls, loss_aux = loss, loss * 0
-        elif mode == "kd":
+        else:
             with torch.no_grad():
                 teacher_out = teacher_model(g.x, g.edge_index)
-            loss, loss_cls, loss_aux = C.ppi_kd_criterion(out, g.y, teacher_out, hp["alpha"], hp["kd_T"])
-        else:
-            raise NotImplementedError(mode)
+                teacher_out_feat = teacher_model.out_feat
+            if mode == "kd":
+                loss, loss_cls, loss_aux = C.ppi_kd_criterion(out, g.y, teacher_out, hp["alpha"], hp["kd_T"])
+            elif mode == "fitnet":
+                loss, loss_cls, loss_aux = C.ppi_fitnet_criterion(out, g.y, student_proj(model.out_feat),
+                                                                  teacher_proj(teacher_out_feat), hp["beta"])
+            elif mode == "at":
+                loss, loss_cls, loss_aux = C.ppi_at_criterion(out, g.y, model.out_feat, teacher_out_feat, hp["beta"])
+            elif mode == "gpw":
+                loss, loss_cls, loss_aux = C.ppi_gpw_criterion(out, g.y, model.out_feat, teacher_out_feat, hp["kernel"], hp["beta"],
+                                                               hp["max_samples"])
+            elif mode == "lpw":
+                loss, loss_cls, loss_aux = C.ppi_lpw_criterion(out, g.y, model.out_feat, teacher_out_feat, g.edge_index, hp["kernel"],
+                                                               hp["beta"])
+            else:   # nce
+                loss, loss_cls, loss_aux = C.ppi_nce_criterion(out, g.y, student_proj(model.out_feat), teacher_proj(teacher_out_feat),
+                                                               hp["beta"], hp["nce_T"], hp["max_samples"])
         optimizer.zero_grad()
         loss.backward()
         optimizer.step()

@@ -199,14 +199,17 @@ _GAT_STRUCT_CACHE = _TensorKeyedCache(capacity=64)
 
 
 class GATConv(nn.Module):
-    """PyG <=1.7 ``GATConv`` for INFERENCE: the frozen GAT teacher that the PPI / MAG train loops run inside every student
-    step (/root/reference/ppi_pyg/gnn.py:86-117,208-209).  Same parameters and ``state_dict`` keys as PyG 1.6/1.7
-    (``lin_l.weight`` shared with ``lin_r``, ``att_l`` / ``att_r`` [1,H,C], ``bias``).
+    """PyG <=1.7 ``GATConv``: the frozen GAT teacher that the PPI / MAG train loops run inside every student step
+    (/root/reference/ppi_pyg/gnn.py:86-117,208-209), and the layer of the PPI GAT student and teacher in training
+    (gnn.py:50-83 ``StudentNet``, :23-47 ``TeacherNet``, ppi_pyg/train_teacher.py).  Same parameters and ``state_dict`` keys as
+    PyG 1.6/1.7 (``lin_l.weight`` shared with ``lin_r``, ``att_l`` / ``att_r`` [1,H,C], ``bias``).
 
     Forward on the gfx950 kernels: x W on the fp32 MFMA, the 2H attention logits per node as one more small GEMM
     (block-diagonal ``att``), scores + LeakyReLU + per-target softmax fused in ``egnn_gat_attention_fwd_f32`` (no [E,H]
     gathers or scatter-softmax temporaries), one valued SpMM per head written straight into its column block.
-    Training the teacher is out of scope: a call that would need gradients raises."""
+    In training mode with autograd on, the attention + aggregation is one autograd node (``ops_edge.gat_attention``) whose
+    backward runs in three HIP launches for all heads (csrc/gat.hip).  In eval mode a call that would need gradients raises:
+    the eval forward is the frozen teacher's."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True, negative_slope: float = 0.2,
                  dropout: float = 0.0, add_self_loops: bool = True, bias: bool = True, **_):
@@ -250,8 +253,10 @@ class GATConv(nn.Module):
     def forward(self, x: Tensor, edge_index) -> Tensor:
         x = _lib.real(x)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("GATConv runs the frozen teacher (torch.no_grad() / requires_grad_(False)); "
-                                      "teacher training is out of scope")
+            if not self.training:
+                raise NotImplementedError("GATConv in eval mode runs the frozen teacher (torch.no_grad() / requires_grad_(False)); "
+                                          "train it in training mode (.train())")
+            return self._forward_train(x, edge_index)
         _lib.require_gpu(x)
         n, H, C = x.shape[0], self.heads, self.out_channels
         xl = ops.linear(x, self.lin_l.weight)                                   # [n, H*C]
@@ -276,6 +281,23 @@ class GATConv(nn.Module):
             ops.spmm_raw(adj.set_value(att[h]), xl[:, h * C:(h + 1) * C], "sum", out=out[:, h * C:(h + 1) * C])
         if not self.concat:
             out = out.view(n, H, C).mean(dim=1)
+        return ops.add_bias(out, self.bias)
+
+    def _forward_train(self, x: Tensor, edge_index) -> Tensor:
+        """The differentiable forward (training mode, autograd on): x W^T through ``ops.linear``, attention + aggregation through
+        ``ops_edge.gat_attention`` (HIP backward, csrc/gat.hip), the bias through ``ops.add_bias``.  Attention dropout draws its
+        mask with torch's RNG as one ``torch.rand(heads, nnz)`` per call (kept where >= p, scaled by 1 / (1 - p)), on the
+        entries of the cached structure."""
+        from .ops_edge import gat_attention
+        _lib.require_gpu(x)
+        n = x.shape[0]
+        xl = ops.linear(x, self.lin_l.weight)                                   # [n, H*C]
+        adj = self._structure(edge_index, n)
+        mult = None
+        if self.dropout > 0:
+            keep = torch.rand(self.heads, adj.nnz(), dtype=torch.float32, device=x.device) >= self.dropout
+            mult = keep.to(torch.float32).mul_(1.0 / (1.0 - self.dropout) if self.dropout < 1 else 0.0)
+        out = gat_attention(xl, self.att_l, self.att_r, adj, self.heads, self.concat, self.negative_slope, mult)
         return ops.add_bias(out, self.bias)
 
     def __repr__(self):

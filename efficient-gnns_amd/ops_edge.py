@@ -202,3 +202,86 @@ def lsp_loss(feat: Tensor, teacher_feat: Tensor, edge_index: Tensor, kernel: str
     sim_s = _EdgeSim.apply(feat, plan, kernel)
     sim_t = _EdgeSim.apply(teacher_feat, plan, kernel)
     return _LspLoss.apply(sim_s, sim_t, plan.ptr_b, 1 if criterion == "mse" else 0)
+
+
+# ------------------------------------------------------------------------------------------------
+# GAT attention + aggregation of one GATConv with its backward (csrc/edge_softmax.hip forward, csrc/gat.hip backward)
+# ------------------------------------------------------------------------------------------------
+class _GATAttention(torch.autograd.Function):
+    """out[i,h,:] = sum_e att[h,e] mult[h,e] xl[col e,h,:] (heads concatenated, or averaged), att = the per-target softmax of
+    leaky_relu(<xl[col e,h], att_l[h]> + <xl[i,h], att_r[h]>).  Gradients for xl, att_l and att_r in three launches for all heads
+    (egnn_gat_attention_bwd_f32, egnn_gat_aggregate_bwd_f32 = source-side kernel + finalize); the averaged heads' 1/H is folded
+    into the kernels.  ``adj``: the layer's cached structure (CSR by target, value-less); the backward reads its transposed
+    structure, formed here in the forward, so nothing in the backward waits for the host."""
+
+    @staticmethod
+    def forward(ctx, xl, att_l, att_r, adj, H, C, concat, slope, mult):
+        n = xl.shape[0]
+        xl = xl.contiguous()
+        blk = torch.zeros(H * C, 2 * H, dtype=torch.float32, device=xl.device)
+        rows = torch.arange(H * C, device=xl.device)
+        blk[rows, rows // C] = att_l.reshape(-1)
+        blk[rows, H + rows // C] = att_r.reshape(-1)
+        alpha = ops.matmul(xl, blk)                                             # [n, 2H]: alpha_src | alpha_dst
+        a_src, a_dst = alpha[:, :H].contiguous(), alpha[:, H:].contiguous()
+        rowptr, col, _ = adj.csr()
+        nnz = adj.nnz()
+        lib = _lib.load()
+        att = torch.empty(H, nnz, dtype=torch.float32, device=xl.device)
+        _lib.check(lib.egnn_gat_attention_fwd_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(a_src), _lib.ptr(a_dst), n, nnz, H,
+                                                  float(slope), _lib.ptr(att), _lib.stream()), "egnn_gat_attention_fwd_f32")
+        vals = att if mult is None else att * mult
+        out = torch.empty(n, H * C, dtype=torch.float32, device=xl.device)
+        for h in range(H):
+            ops.spmm_raw(adj.set_value(vals[h]), xl[:, h * C:(h + 1) * C], "sum", out=out[:, h * C:(h + 1) * C])
+        if not concat:
+            out = out.view(n, H, C).mean(dim=1)
+        adj._transpose_meta()
+        adj.t()
+        ctx.adj, ctx.H, ctx.C, ctx.concat, ctx.slope = adj, H, C, concat, float(slope)
+        ctx.save_for_backward(xl, a_src, a_dst, att, mult, att_l, att_r)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xl, a_src, a_dst, att, mult, att_l, att_r = ctx.saved_tensors
+        adj, H, C = ctx.adj, ctx.H, ctx.C
+        g = g.contiguous()
+        n, nnz, HC = xl.shape[0], adj.nnz(), H * C
+        ld_go, go_hs, go_scale = (HC, C, 1.0) if ctx.concat else (C, 0, 1.0 / H)
+        rowptr, col, _ = adj.csr()
+        colptr, perm = adj._transpose_meta()
+        t_col = adj.t()._col
+        lib = _lib.load()
+        d_raw = torch.empty(H, nnz, dtype=torch.float32, device=xl.device)
+        d_adst = torch.empty(n, H, dtype=torch.float32, device=xl.device)
+        _lib.check(lib.egnn_gat_attention_bwd_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(a_src), _lib.ptr(a_dst), _lib.ptr(att),
+                                                  _lib.ptr(mult), _lib.ptr(xl), HC, _lib.ptr(g), ld_go, go_hs, go_scale, n, nnz, H, C,
+                                                  ctx.slope, _lib.ptr(d_raw), _lib.ptr(d_adst), _lib.stream()),
+                   "egnn_gat_attention_bwd_f32")
+        dxl = torch.empty(n, HC, dtype=torch.float32, device=xl.device)
+        d_att = torch.empty(2, HC, dtype=torch.float32, device=xl.device)
+        nws = lib.egnn_gat_aggregate_bwd_ws_floats(n, H, C)
+        ws = torch.empty(nws, dtype=torch.float32, device=xl.device)
+        _lib.check(lib.egnn_gat_aggregate_bwd_f32(_lib.ptr(colptr), _lib.ptr(t_col), _lib.ptr(perm), _lib.ptr(att), _lib.ptr(mult),
+                                                  _lib.ptr(d_raw), _lib.ptr(g), ld_go, go_hs, go_scale, _lib.ptr(xl), HC,
+                                                  _lib.ptr(att_l), _lib.ptr(att_r), _lib.ptr(d_adst), n, nnz, H, C, _lib.ptr(dxl), HC,
+                                                  _lib.ptr(d_att), _lib.ptr(ws), nws, _lib.stream()),
+                   "egnn_gat_aggregate_bwd_f32")
+        return dxl, d_att[0].view(1, H, C), d_att[1].view(1, H, C), None, None, None, None, None, None
+
+
+def gat_attention(xl: Tensor, att_l: Tensor, att_r: Tensor, adj: SparseTensor, heads: int, concat: bool, negative_slope: float,
+                  mult: Tensor | None = None) -> Tensor:
+    """Differentiable attention + aggregation of one GATConv (``xl`` = x W^T [n, heads*C]); ``mult`` [heads, nnz]: the
+    attention-dropout multiplier (mask / (1 - p)) or None.  Returns [n, heads*C] (concat) or [n, C] (heads averaged)."""
+    _lib.require_gpu(xl)
+    H = heads
+    C = xl.shape[1] // H
+    if xl.shape[1] != H * C or att_l.numel() != H * C or att_r.numel() != H * C:
+        raise ValueError("gat_attention: xl [n, heads*C], att_l / att_r [1, heads, C]")
+    if H * C > 2048:
+        raise ValueError("gat_attention: heads * out_channels > 2048 is not supported by the backward (egnn_gat_aggregate_bwd_f32)")
+    if mult is not None:
+        mult = mult.contiguous()
+    return _GATAttention.apply(xl, att_l.contiguous(), att_r.contiguous(), adj, H, C, concat, negative_slope, mult)

@@ -419,10 +419,39 @@ int egnn_colsum_f32(const float* x, int64_t ld, int64_t n, int64_t C, float* out
  *   s[e,h]   = leaky_relu(alpha_src[col[e],h] + alpha_dst[row(e),h], negative_slope)          (u_add_v SDDMM)
  *   att[h,e] = exp(s - max over the row's entries) / (sum exp(..) + 1e-16)                     (edge softmax per target)
  * rowptr / col: CSR by target, int64; alpha_src [n_src,H], alpha_dst [n_rows,H] row-major; att is HEAD-major [H,nnz]
- * so that head h's values are a contiguous per-entry array for egnn_spmm_csr_*_f32 (u_mul_e_sum).  Forward only
- * (the teacher is frozen inside the student step; teacher training is out of scope). */
+ * so that head h's values are a contiguous per-entry array for egnn_spmm_csr_*_f32 (u_mul_e_sum).  Backward:
+ * egnn_gat_attention_bwd_f32 + egnn_gat_aggregate_bwd_f32 below. */
 int egnn_gat_attention_fwd_f32(const int64_t* rowptr, const int64_t* col, const float* alpha_src, const float* alpha_dst,
                                int64_t n_rows, int64_t nnz, int H, float negative_slope, float* att, void* stream);
+
+/* Backward of the GAT attention + aggregation of one GATConv in training (the PPI GAT student and teacher,
+ * /root/reference/ppi_pyg/gnn.py:50-83 StudentNet, :23-47 TeacherNet trained by ppi_pyg/train_teacher.py; each step's
+ * loss.backward() at gnn.py:262).  Forward per head h: att = egnn_gat_attention_fwd_f32, out[i,h,:] = sum_e att[h,e] mult[h,e]
+ * xl[col e,h,:].  go[i,h,:] = go_scale * go_ptr[i * ld_go + h * go_head_stride + c]: the per-head output gradient (concatenated
+ * heads: stride C, scale 1; averaged heads: stride 0, scale 1/H).  mult [H,nnz] nullable: the attention-dropout multiplier
+ * (mask / (1 - p)).  csrc/gat.hip; deterministic (fixed summation orders, no atomics).
+ *
+ * Target side (one wavefront per target row, all heads in one launch):
+ *   g_e = mult_e <go[i,h,:], xl[col e,h,:]>,  d_raw[h,e] = att_e (g_e - sum_row att g) * (s_e > 0 ? 1 : negative_slope),
+ *   d_alpha_dst[i,h] = sum_row d_raw  (s_e recomputed from alpha_src / alpha_dst as the forward formed it).
+ * xl [n, ld_xl >= H*C] row-major; d_raw [H,nnz]; d_alpha_dst [n_rows,H]. */
+int egnn_gat_attention_bwd_f32(const int64_t* rowptr, const int64_t* col, const float* alpha_src, const float* alpha_dst,
+                               const float* att, const float* mult, const float* xl, int64_t ld_xl, const float* go,
+                               int64_t ld_go, int64_t go_head_stride, float go_scale, int64_t n_rows, int64_t nnz, int H,
+                               int C, float negative_slope, float* d_raw, float* d_alpha_dst, void* stream);
+/* Source side over the transposed structure (colptr [n_src+1], t_col / perm [nnz]: entry q of source column j is CSR entry
+ * perm[q] of target row t_col[q]; SparseTensor._transpose_meta), one wavefront per source row, all heads in one launch:
+ *   d_a_src[j,h] = sum_q d_raw[h,perm q]
+ *   dxl[j,h,:]   = go_scale sum_q att[h,perm q] mult[h,perm q] go[t_col q,h,:] + d_a_src[j,h] att_l[h,:] + d_alpha_dst[j,h] att_r[h,:]
+ * att_r and d_alpha_dst nullable together (a layer without a target-side attention vector).  d_att [2,H*C] nullable:
+ * d_att[0] = sum_j xl[j,h,:] d_a_src[j,h] (= d att_l), d_att[1] the same with d_alpha_dst (= d att_r), as per-block partials in
+ * ws (egnn_gat_aggregate_bwd_ws_floats(n_src, H, C) floats) + a fixed-order finalize (a second launch); needs H*C <= 2048. */
+size_t egnn_gat_aggregate_bwd_ws_floats(int64_t n_src, int H, int C);
+int egnn_gat_aggregate_bwd_f32(const int64_t* colptr, const int64_t* t_col, const int64_t* perm, const float* att,
+                               const float* mult, const float* d_raw, const float* go, int64_t ld_go, int64_t go_head_stride,
+                               float go_scale, const float* xl, int64_t ld_xl, const float* att_l, const float* att_r,
+                               const float* d_alpha_dst, int64_t n_src, int64_t nnz, int H, int C, float* dxl, int64_t ld_dxl,
+                               float* d_att, float* ws, size_t ws_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused BatchNorm1d (+ ReLU + dropout) over node rows -- SURVEY.md 8(f) rank 1; replaces the ATen BatchNorm /
