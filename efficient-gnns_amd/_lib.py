@@ -14,6 +14,17 @@ LIB_PATH = os.path.join(_HERE, "lib", "libegnn_hip.so")
 
 _p, _i64, _i32, _f32, _sz, _u64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t, C.c_uint64
 
+
+class BnAct(C.Structure):
+    """egnn_bn_act_t of include/egnn_hip.h, field for field: the operands of one fused BatchNorm (+ ReLU + dropout) call.  The entry
+    points read it only while they run (pass ``ctypes.byref``: bound as a pointer argument); pick = None / n_pick = 0 means every row."""
+    _fields_ = [("x", _p), ("ld", _i64), ("n", _i64), ("C", _i64),
+                ("mean", _p), ("var", _p), ("eps", _f32),
+                ("gamma", _p), ("beta", _p),
+                ("relu", _i32), ("p", _f32), ("seed", _u64), ("seed_dev", _p),
+                ("pick", _p), ("n_pick", _i64)]
+
+
 # name -> (restype, argtypes); must list every symbol include/egnn_hip.h declares
 SIGNATURES = {
     "egnn_abi_version": (_i32, []),
@@ -89,29 +100,15 @@ SIGNATURES = {
     "egnn_colsum_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p]),
     "egnn_bn_ws_floats": (_sz, [_i64]),
     "egnn_bn_stats_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
-    "egnn_bn_act_fwd_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _p, _i64, _p]),
-    "egnn_bn_act_bwd_f32": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _i32, _p, _p, _p, _i64,
-                                   _p, _sz, _p]),
+    "egnn_bn_act_fwd_f32": (_i32, [_p, _p, _i64, _p]),
+    "egnn_bn_act_bwd_f32": (_i32, [_p, _p, _i64, _i32, _p, _p, _p, _i64, _p, _p, _sz, _p]),
+    "egnn_bn_act_bwd_reduce_f32": (_i32, [_p, _p, _i64, _p, _p, _p, _sz, _p]),
+    "egnn_bn_act_bwd_apply_f32": (_i32, [_p, _p, _i64, _p, _p, _f32, _p, _p, _i64, _p, _p, _sz, _p]),
     "egnn_bn_merge_shards_f32": (_i32, [_p, _i32, _i64, _p, _p, _p, _p]),
-    "egnn_bn_act_bwd_colsum_f32": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _i32, _p, _p, _p, _i64,
-                                          _p, _p, _sz, _p]),
-    "egnn_bn_act_rows_fwd_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _p, _i64, _p]),
-    "egnn_bn_act_rows_bwd_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _i32, _p, _p,
-                                        _p, _i64, _p, _p, _sz, _p]),
-    "egnn_bn_act_rows_bwd_reduce_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _p, _p, _p, _sz, _p]),
-    "egnn_bn_act_rows_bwd_apply_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _p, _p, _f32, _p, _p,
-                                              _i64, _p, _p, _sz, _p]),
-    "egnn_bn_act_linear_fwd_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _p, _i64, _i32, _i64, _p, _i64, _p,
-                                          _i64, _p]),
+    "egnn_bn_act_linear_fwd_f32": (_i32, [_p, _p, _i64, _i32, _i64, _p, _i64, _p, _i64, _p]),
     "egnn_skinny_dx_bn_ws_floats": (_sz, [_i64, _i64]),
-    "egnn_skinny_dx_bn_bwd_f32": (_i32, [_p, _i64, _p, _i64, _i32, _i64, _i64, _i64, _f32, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _f32,
-                                         _p, _p, _i32, _f32, _u64, _p, _i32, _p, _p, _p, _i64, _p, _p, _sz, _p]),
-    "egnn_skinny_dx_bn_bwd_reduce_f32": (_i32, [_p, _i64, _p, _i64, _i32, _i64, _i64, _i64, _f32, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _f32,
-                                                _p, _p, _i32, _f32, _u64, _p, _p, _p, _p, _i64, _p, _sz, _p]),
-    "egnn_bn_bwd_apply_stored_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _p, _p, _f32, _p, _i64, _p, _p,
-                                            _sz, _p]),
-    "egnn_bn_act_bwd_apply_colsum_f32": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _p, _p, _f32, _p, _i64,
-                                                _p, _p, _sz, _p]),
+    "egnn_skinny_dx_bn_bwd_reduce_f32": (_i32, [_p, _i64, _p, _i64, _i32, _i64, _f32, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _sz, _p]),
+    "egnn_bn_bwd_apply_stored_f32": (_i32, [_p, _p, _p, _f32, _p, _i64, _p, _p, _sz, _p]),
     "egnn_bn_running_update_dev_f32": (_i32, [_p, _p, _i64, _p, _f32, _p, _p, _p, _p]),
     "egnn_bn_running_update_f32": (_i32, [_p, _p, _i64, _i64, _f32, _p, _p, _p, _p]),
     "egnn_split_accuracy_ws_ints": (_sz, []),
@@ -124,8 +121,6 @@ SIGNATURES = {
     "egnn_at_fwd_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _sz, _p]),
     "egnn_at_bwd_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _i64, _p, _i64, _p]),
     "egnn_probe_gather_lines_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _i32, _i32, _p, _p]),
-    "egnn_bn_act_bwd_reduce_f32": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _p, _p, _p, _sz, _p]),
-    "egnn_bn_act_bwd_apply_f32": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _f32, _p, _p, _i32, _f32, _u64, _p, _p, _p, _f32, _p, _i64, _p]),
 }
 
 _lib = None
@@ -148,7 +143,7 @@ def load() -> C.CDLL:
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype, fn.argtypes = res, args
-    if lib.egnn_abi_version() != 6:
+    if lib.egnn_abi_version() != 7:
         raise HipExtensionError("libegnn_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restri
 // MODE 0: as above.  The two halves of the backward of a BatchNorm whose OUTPUT was only formed for the rows `pick` (dy has one row
 // per picked row, every other output row has no gradient): MODE 1 walks ALL rows with d = 0 (dx = -gamma rstd (sum d + xhat sum d xhat) / n),
 // MODE 2 walks the picked rows and adds gamma rstd d to their dx rows (unique ids: no two waves touch the same row).
-// MODE 3: dy already holds d = g * gate (egnn_skinny_dx_bn_bwd_f32 wrote it, possibly into dx itself: every element is read and then
+// MODE 3: dy already holds d = g * gate (egnn_skinny_dx_bn_bwd_reduce_f32 wrote it, possibly into dx itself: every element is read and then
 // written by the same lane): no mask is recomputed.
 template <bool COLSUM, int MODE = 0>
 __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const BnParams q, const float* __restrict__ dy, int64_t ldd,
@@ -360,6 +360,19 @@ int row_blocks(int64_t n) {
   return (int)(want < 2048 ? (want < 1 ? 1 : want) : 2048);
 }
 
+// The checks every entry point makes of the descriptor, and the two parameter blocks it stands for: `all` = every row of x (the
+// statistics' rows, dx), `out` = the output rows x[pick[i]] (pick == NULL: every row again).
+int bn_unpack(const egnn_bn_act_t* b, BnParams& all, BnParams& out) {
+  EGNN_CHECK_ARG(b && b->n > 0 && b->x && b->mean && b->var && b->ld >= b->C);
+  EGNN_CHECK_ARG(!b->pick || (b->n_pick >= 0 && b->n_pick <= b->n));
+  if (!shape_ok(b->x, b->ld, b->C)) return EGNN_EALIGN;
+  all = BnParams{b->x, b->ld, b->n, b->C, b->mean, b->var, b->eps, b->gamma, b->beta, b->relu, b->p, (unsigned long long)b->seed,
+                 (const unsigned long long*)b->seed_dev, nullptr};
+  out = all;
+  if (b->pick) { out.n = b->n_pick; out.pick = b->pick; }
+  return EGNN_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -408,180 +421,96 @@ extern "C" int egnn_bn_stats_f32(const float* x, int64_t ld, int64_t n, int64_t 
   return egnn_launch_status();
 }
 
-extern "C" int egnn_bn_act_fwd_f32(const float* x, int64_t ld, int64_t n, int64_t C, const float* mean, const float* var, float eps,
-                                   const float* gamma, const float* beta, int relu, float p, uint64_t seed,
-                                   const uint64_t* seed_dev, float* y, int64_t ldy, void* stream) {
-  EGNN_CHECK_ARG(n > 0 && x && mean && var && y && ld >= C && ldy >= C && p >= 0.f && p < 1.f);
-  if (!shape_ok(x, ld, C) || !shape_ok(y, ldy, C)) return EGNN_EALIGN;
-  const BnParams q{x, ld, n, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, nullptr};
-  hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(row_blocks(n)), dim3(256), 0, (hipStream_t)stream, q, y, ldy);
+// The fused BatchNorm + activation of the descriptor `bn` (include/egnn_hip.h: egnn_bn_act_t).  With bn->pick the OUTPUT is only needed
+// on the rows pick (unique ids) -- the projection heads of the sampled criteria (gnn.py:296-306 feeding criterion.py:62-65,134-137): the
+// statistics span all n rows of x, the criterion reads max_samples of the output rows.  Forward: only those rows are formed.  Backward:
+// the reductions run over the picked rows (every other row has d = 0), dx still has all n rows (the mean / variance terms reach every row).
+extern "C" int egnn_bn_act_fwd_f32(const egnn_bn_act_t* bn, float* y, int64_t ldy, void* stream) {
+  BnParams qa, q;
+  const int rc = bn_unpack(bn, qa, q);
+  if (rc != EGNN_OK) return rc;
+  EGNN_CHECK_ARG(q.n > 0 && y && ldy >= bn->C && bn->p >= 0.f && bn->p < 1.f);
+  if (!shape_ok(y, ldy, bn->C)) return EGNN_EALIGN;
+  hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(row_blocks(q.n)), dim3(256), 0, (hipStream_t)stream, q, y, ldy);
   return egnn_launch_status();
 }
 
-extern "C" int egnn_bn_act_bwd_reduce_f32(const float* x, int64_t ld, const float* dy, int64_t ld_dy, int64_t n, int64_t C,
-                                          const float* mean, const float* var, float eps, const float* gamma, const float* beta,
-                                          int relu, float p, uint64_t seed, const uint64_t* seed_dev, float* dgamma, float* dbeta,
-                                          float* ws, size_t ws_floats, void* stream) {
-  EGNN_CHECK_ARG(n > 0 && x && dy && mean && var && dgamma && dbeta && ws && ld >= C && ld_dy >= C);
-  if (!shape_ok(x, ld, C) || !shape_ok(dy, ld_dy, C)) return EGNN_EALIGN;
+// sum d, sum d xhat over the output rows (with pick: every other output row has no gradient)
+extern "C" int egnn_bn_act_bwd_reduce_f32(const egnn_bn_act_t* bn, const float* dy, int64_t ld_dy, float* dgamma, float* dbeta, float* ws,
+                                          size_t ws_floats, void* stream) {
+  BnParams qa, q;
+  const int rc = bn_unpack(bn, qa, q);
+  if (rc != EGNN_OK) return rc;
+  const int64_t C = bn->C;
+  EGNN_CHECK_ARG(q.n > 0 && dy && dgamma && dbeta && ws && ld_dy >= C);
+  if (!shape_ok(dy, ld_dy, C)) return EGNN_EALIGN;
   if (ws_floats < egnn_bn_ws_floats(C)) return EGNN_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const BnParams q{x, ld, n, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, nullptr};
-  const int64_t want = (n + 3) / 4;
+  const int64_t want = (q.n + 3) / 4;
   const int nb = (int)(want < kStatBlocks ? want : kStatBlocks);
   hipLaunchKernelGGL(bn_act_bwd_reduce_kernel, dim3(nb), dim3(256), 0, st, q, dy, ld_dy, ws);
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((unsigned)((C + kMergeCols - 1) / kMergeCols)), dim3(256), 0, st, ws, nb, C, dbeta, dgamma);
   return egnn_launch_status();
 }
 
-extern "C" int egnn_bn_act_bwd_apply_f32(const float* x, int64_t ld, const float* dy, int64_t ld_dy, int64_t n, int64_t C,
-                                         const float* mean, const float* var, float eps, const float* gamma, const float* beta,
-                                         int relu, float p, uint64_t seed, const uint64_t* seed_dev, const float* sum_dbeta,
-                                         const float* sum_dgamma, float inv_count, float* dx, int64_t ld_dx, void* stream) {
-  EGNN_CHECK_ARG(n > 0 && x && dy && mean && var && sum_dbeta && sum_dgamma && dx && ld >= C && ld_dy >= C && ld_dx >= C);
-  if (!shape_ok(x, ld, C) || !shape_ok(dy, ld_dy, C) || !shape_ok(dx, ld_dx, C)) return EGNN_EALIGN;
-  const BnParams q{x, ld, n, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, nullptr};
-  hipLaunchKernelGGL(bn_act_bwd_apply_kernel<false>, dim3(row_blocks(n)), dim3(256), 0, (hipStream_t)stream, q, dy, ld_dy, sum_dbeta,
-                     sum_dgamma, inv_count, dx, ld_dx, nullptr);
-  return egnn_launch_status();
-}
-
-// the apply half with the column sums of dx formed on the way (the bias gradient of the layer in front), for callers that put an
-// all-rank reduction of the sums between the halves (SyncBN): ws of egnn_bn_ws_floats(C) floats
-extern "C" int egnn_bn_act_bwd_apply_colsum_f32(const float* x, int64_t ld, const float* dy, int64_t ld_dy, int64_t n, int64_t C,
-                                                const float* mean, const float* var, float eps, const float* gamma, const float* beta,
-                                                int relu, float p, uint64_t seed, const uint64_t* seed_dev, const float* sum_dbeta,
-                                                const float* sum_dgamma, float inv_count, float* dx, int64_t ld_dx, float* dx_colsum,
-                                                float* ws, size_t ws_floats, void* stream) {
-  EGNN_CHECK_ARG(n > 0 && x && dy && mean && var && sum_dbeta && sum_dgamma && dx && dx_colsum && ws && ld >= C && ld_dy >= C && ld_dx >= C);
-  if (!shape_ok(x, ld, C) || !shape_ok(dy, ld_dy, C) || !shape_ok(dx, ld_dx, C)) return EGNN_EALIGN;
-  if (ws_floats < egnn_bn_ws_floats(C)) return EGNN_EWORKSPACE;
-  const BnParams q{x, ld, n, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, nullptr};
-  int nb = row_blocks(n);
-  if (nb > 2 * kStatBlocks) nb = 2 * kStatBlocks;
-  nb = (nb + 1) & ~1;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_act_bwd_apply_kernel<true>, dim3(nb), dim3(256), 0, st, q, dy, ld_dy, sum_dbeta, sum_dgamma, inv_count, dx, ld_dx, ws);
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((unsigned)((C + kMergeCols - 1) / kMergeCols)), dim3(256), 0, st, ws, nb / 2, C, dx_colsum,
-                     (const float*)nullptr, (const float*)nullptr, 0.f, (const float*)nullptr);
-  return egnn_launch_status();
-}
-
-extern "C" int egnn_bn_act_bwd_colsum_f32(const float* x, int64_t ld, const float* dy, int64_t ld_dy, int64_t n, int64_t C,
-                                          const float* mean, const float* var, float eps, const float* gamma, const float* beta, int relu,
-                                          float p, uint64_t seed, const uint64_t* seed_dev, int batch_stats, float* dgamma, float* dbeta,
-                                          float* dx, int64_t ld_dx, float* dx_colsum, float* ws, size_t ws_floats, void* stream) {
-  EGNN_CHECK_ARG(dx && ld_dx >= C);
-  const int rc = egnn_bn_act_bwd_reduce_f32(x, ld, dy, ld_dy, n, C, mean, var, eps, gamma, beta, relu, p, seed, seed_dev, dgamma, dbeta,
-                                            ws, ws_floats, stream);
-  if (rc != EGNN_OK) return rc;
-  const float inv_count = batch_stats ? 1.f / (float)n : 0.f;
-  if (!dx_colsum)
-    return egnn_bn_act_bwd_apply_f32(x, ld, dy, ld_dy, n, C, mean, var, eps, gamma, beta, relu, p, seed, seed_dev, dbeta, dgamma, inv_count, dx,
-                                     ld_dx, stream);
-  EGNN_CHECK_ARG(n > 0 && x && dy && mean && var && ld >= C && ld_dy >= C);
-  if (!shape_ok(dx, ld_dx, C)) return EGNN_EALIGN;
-  const BnParams q{x, ld, n, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, nullptr};
-  int nb = row_blocks(n);
-  if (nb > 2 * kStatBlocks) nb = 2 * kStatBlocks;   // the workspace holds 2 kStatBlocks partial rows (the reduce half is done with it: same stream)
-  nb = (nb + 1) & ~1;                               // whole pairs; a block past the rows writes zeros
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_act_bwd_apply_kernel<true>, dim3(nb), dim3(256), 0, st, q, dy, ld_dy, dbeta, dgamma, inv_count, dx, ld_dx, ws);
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((unsigned)((C + kMergeCols - 1) / kMergeCols)), dim3(256), 0, st, ws, nb / 2, C, dx_colsum,
-                     (const float*)nullptr, (const float*)nullptr, 0.f, (const float*)nullptr);
-  return egnn_launch_status();
-}
-
-// ---- the same fused BatchNorm + activation whose OUTPUT is only needed on the rows `pick` (unique ids) ---------------------------
-// The projection heads of the sampled criteria (gnn.py:296-306 feeding criterion.py:62-65,134-137): the statistics span all n rows of
-// x, the criterion reads max_samples of the output rows.  Forward: only those rows are formed.  Backward: the reductions run over
-// the picked rows (every other row has d = 0), dx still has all n rows (the mean / variance terms reach every row).
-extern "C" int egnn_bn_act_rows_fwd_f32(const float* x, int64_t ld, int64_t n, int64_t C, const int64_t* pick, int64_t n_pick,
-                                        const float* mean, const float* var, float eps, const float* gamma, const float* beta, int relu,
-                                        float p, uint64_t seed, const uint64_t* seed_dev, float* y, int64_t ldy, void* stream) {
-  EGNN_CHECK_ARG(n > 0 && n_pick > 0 && n_pick <= n && pick && x && mean && var && y && ld >= C && ldy >= C && p >= 0.f && p < 1.f);
-  if (!shape_ok(x, ld, C) || !shape_ok(y, ldy, C)) return EGNN_EALIGN;
-  const BnParams q{x, ld, n_pick, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, pick};
-  hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(row_blocks(n_pick)), dim3(256), 0, (hipStream_t)stream, q, y, ldy);
-  return egnn_launch_status();
-}
-
-// The backward of the picked-rows form in its two halves (a node-range shard all-reduces [sum d | sum d xhat] between them: SyncBN).
-extern "C" int egnn_bn_act_rows_bwd_reduce_f32(const float* x, int64_t ld, int64_t n, int64_t C, const int64_t* pick, int64_t n_pick,
-                                               const float* dy, int64_t ld_dy, const float* mean, const float* var, float eps,
-                                               const float* gamma, const float* beta, int relu, float p, uint64_t seed,
-                                               const uint64_t* seed_dev, float* dgamma, float* dbeta, float* ws, size_t ws_floats, void* stream) {
-  EGNN_CHECK_ARG(n > 0 && n_pick > 0 && n_pick <= n && pick && x && dy && mean && var && dgamma && dbeta && ws && ld >= C && ld_dy >= C);
-  if (!shape_ok(x, ld, C) || !shape_ok(dy, ld_dy, C)) return EGNN_EALIGN;
-  if (ws_floats < egnn_bn_ws_floats(C)) return EGNN_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const BnParams qp{x, ld, n_pick, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, pick};
-  // sum d, sum d xhat over the picked rows (every other output row has no gradient)
-  const int64_t want = (n_pick + 3) / 4;
-  const int nbr = (int)(want < kStatBlocks ? want : kStatBlocks);
-  hipLaunchKernelGGL(bn_act_bwd_reduce_kernel, dim3(nbr), dim3(256), 0, st, qp, dy, ld_dy, ws);
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((unsigned)((C + kMergeCols - 1) / kMergeCols)), dim3(256), 0, st, ws, nbr, C, dbeta, dgamma);
-  return egnn_launch_status();
-}
-
 // sum_dbeta / sum_dgamma: the sums the mean / variance terms use (this tensor's own, or the all-rank ones), inv_count = 1 / rows they span
-// (0: running statistics, no such terms).  local_dbeta (needed with dx_colsum): sum d over THIS tensor's picked rows -- the picked rows'
-// own term gamma rstd d sums to gamma rstd local_dbeta per column.  n_pick == 0 (a shard without sampled rows): every row still
-// receives the mean / variance terms.
-extern "C" int egnn_bn_act_rows_bwd_apply_f32(const float* x, int64_t ld, int64_t n, int64_t C, const int64_t* pick, int64_t n_pick,
-                                              const float* dy, int64_t ld_dy, const float* mean, const float* var, float eps,
-                                              const float* gamma, const float* beta, int relu, float p, uint64_t seed,
-                                              const uint64_t* seed_dev, const float* sum_dbeta, const float* sum_dgamma, float inv_count,
-                                              const float* local_dbeta, float* dx, int64_t ld_dx, float* dx_colsum, float* ws,
-                                              size_t ws_floats, void* stream) {
-  EGNN_CHECK_ARG(n > 0 && n_pick >= 0 && n_pick <= n && x && mean && var && sum_dbeta && sum_dgamma && dx && ld >= C && ld_dx >= C);
-  EGNN_CHECK_ARG(n_pick == 0 || (pick && dy && ld_dy >= C));
-  EGNN_CHECK_ARG(dx_colsum == nullptr || n_pick == 0 || local_dbeta);
-  if (!shape_ok(x, ld, C) || !shape_ok(dx, ld_dx, C) || (n_pick > 0 && !shape_ok(dy, ld_dy, C))) return EGNN_EALIGN;
+// (0: running statistics, no such terms).  dx_colsum (nullable): the column sums of dx, formed in the same pass (ws of egnn_bn_ws_floats(C)
+// floats).  With pick, local_dbeta (needed with dx_colsum) is sum d over THIS tensor's picked rows -- the picked rows' own term
+// gamma rstd d sums to gamma rstd local_dbeta per column; n_pick == 0 (a shard without sampled rows): every row still receives the
+// mean / variance terms.
+extern "C" int egnn_bn_act_bwd_apply_f32(const egnn_bn_act_t* bn, const float* dy, int64_t ld_dy, const float* sum_dbeta,
+                                         const float* sum_dgamma, float inv_count, const float* local_dbeta, float* dx, int64_t ld_dx,
+                                         float* dx_colsum, float* ws, size_t ws_floats, void* stream) {
+  BnParams qa, qp;
+  const int rc = bn_unpack(bn, qa, qp);
+  if (rc != EGNN_OK) return rc;
+  const int64_t C = bn->C;
+  const bool rows = bn->pick != nullptr;
+  EGNN_CHECK_ARG(sum_dbeta && sum_dgamma && dx && ld_dx >= C);
+  EGNN_CHECK_ARG(qp.n == 0 || (dy && ld_dy >= C));
+  EGNN_CHECK_ARG(!dx_colsum || !rows || qp.n == 0 || local_dbeta);
+  if (!shape_ok(dx, ld_dx, C) || (qp.n > 0 && !shape_ok(dy, ld_dy, C))) return EGNN_EALIGN;
   if (dx_colsum && (ws == nullptr || ws_floats < egnn_bn_ws_floats(C))) return EGNN_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const BnParams qp{x, ld, n_pick, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, pick};
-  const BnParams qa{x, ld, n, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, nullptr};
-  // every row: the mean / variance terms;  then the picked rows: + gamma rstd d
-  int nb = row_blocks(n);
+  int nb = row_blocks(bn->n);
   if (dx_colsum) {
-    if (nb > 2 * kStatBlocks) nb = 2 * kStatBlocks;
-    nb = (nb + 1) & ~1;
-    hipLaunchKernelGGL((bn_act_bwd_apply_kernel<true, 1>), dim3(nb), dim3(256), 0, st, qa, (const float*)nullptr, (int64_t)0, sum_dbeta, sum_dgamma,
-                       inv_count, dx, ld_dx, ws);
-  } else {
-    hipLaunchKernelGGL((bn_act_bwd_apply_kernel<false, 1>), dim3(nb), dim3(256), 0, st, qa, (const float*)nullptr, (int64_t)0, sum_dbeta, sum_dgamma,
-                       inv_count, dx, ld_dx, (float*)nullptr);
+    if (nb > 2 * kStatBlocks) nb = 2 * kStatBlocks;   // the workspace holds 2 kStatBlocks partial rows
+    nb = (nb + 1) & ~1;                               // whole pairs; a block past the rows writes zeros
   }
-  if (n_pick > 0)
-    hipLaunchKernelGGL((bn_act_bwd_apply_kernel<false, 2>), dim3(row_blocks(n_pick)), dim3(256), 0, st, qp, dy, ld_dy, sum_dbeta, sum_dgamma, inv_count,
-                       dx, ld_dx, (float*)nullptr);
+  if (!rows) {
+    if (dx_colsum)
+      hipLaunchKernelGGL(bn_act_bwd_apply_kernel<true>, dim3(nb), dim3(256), 0, st, qa, dy, ld_dy, sum_dbeta, sum_dgamma, inv_count, dx, ld_dx, ws);
+    else
+      hipLaunchKernelGGL(bn_act_bwd_apply_kernel<false>, dim3(nb), dim3(256), 0, st, qa, dy, ld_dy, sum_dbeta, sum_dgamma, inv_count, dx, ld_dx,
+                         (float*)nullptr);
+  } else {
+    // every row: the mean / variance terms;  then the picked rows: + gamma rstd d
+    if (dx_colsum)
+      hipLaunchKernelGGL((bn_act_bwd_apply_kernel<true, 1>), dim3(nb), dim3(256), 0, st, qa, (const float*)nullptr, (int64_t)0, sum_dbeta, sum_dgamma,
+                         inv_count, dx, ld_dx, ws);
+    else
+      hipLaunchKernelGGL((bn_act_bwd_apply_kernel<false, 1>), dim3(nb), dim3(256), 0, st, qa, (const float*)nullptr, (int64_t)0, sum_dbeta, sum_dgamma,
+                         inv_count, dx, ld_dx, (float*)nullptr);
+    if (qp.n > 0)
+      hipLaunchKernelGGL((bn_act_bwd_apply_kernel<false, 2>), dim3(row_blocks(qp.n)), dim3(256), 0, st, qp, dy, ld_dy, sum_dbeta, sum_dgamma, inv_count,
+                         dx, ld_dx, (float*)nullptr);
+  }
   if (dx_colsum)
-    hipLaunchKernelGGL(colsum_final_kernel, dim3((unsigned)((C + kMergeCols - 1) / kMergeCols)), dim3(256), 0, st, ws, nb / 2, C, dx_colsum, gamma,
-                       var, eps, n_pick > 0 ? local_dbeta : (const float*)nullptr);
+    hipLaunchKernelGGL(colsum_final_kernel, dim3((unsigned)((C + kMergeCols - 1) / kMergeCols)), dim3(256), 0, st, ws, nb / 2, C, dx_colsum,
+                       rows ? bn->gamma : (const float*)nullptr, rows ? bn->var : (const float*)nullptr, rows ? bn->eps : 0.f,
+                       rows && qp.n > 0 ? local_dbeta : (const float*)nullptr);
   return egnn_launch_status();
 }
 
-extern "C" int egnn_bn_act_rows_bwd_f32(const float* x, int64_t ld, int64_t n, int64_t C, const int64_t* pick, int64_t n_pick,
-                                        const float* dy, int64_t ld_dy, const float* mean, const float* var, float eps, const float* gamma,
-                                        const float* beta, int relu, float p, uint64_t seed, const uint64_t* seed_dev, int batch_stats,
-                                        float* dgamma, float* dbeta, float* dx, int64_t ld_dx, float* dx_colsum, float* ws, size_t ws_floats,
-                                        void* stream) {
-  EGNN_CHECK_ARG(n > 0 && n_pick > 0 && dx && ld_dx >= C);
-  if (!shape_ok(dx, ld_dx, C)) return EGNN_EALIGN;
-  const int rc = egnn_bn_act_rows_bwd_reduce_f32(x, ld, n, C, pick, n_pick, dy, ld_dy, mean, var, eps, gamma, beta, relu, p, seed, seed_dev, dgamma,
-                                                 dbeta, ws, ws_floats, stream);
+// reduce + apply with this tensor's own sums (local_dbeta = dbeta) and inv_count = 1 / n (batch_stats) or 0 (running statistics)
+extern "C" int egnn_bn_act_bwd_f32(const egnn_bn_act_t* bn, const float* dy, int64_t ld_dy, int batch_stats, float* dgamma, float* dbeta,
+                                   float* dx, int64_t ld_dx, float* dx_colsum, float* ws, size_t ws_floats, void* stream) {
+  EGNN_CHECK_ARG(bn && dx && ld_dx >= bn->C);
+  if (!shape_ok(dx, ld_dx, bn->C)) return EGNN_EALIGN;
+  const int rc = egnn_bn_act_bwd_reduce_f32(bn, dy, ld_dy, dgamma, dbeta, ws, ws_floats, stream);
   if (rc != EGNN_OK) return rc;
-  return egnn_bn_act_rows_bwd_apply_f32(x, ld, n, C, pick, n_pick, dy, ld_dy, mean, var, eps, gamma, beta, relu, p, seed, seed_dev, dbeta, dgamma,
-                                        batch_stats ? 1.f / (float)n : 0.f, dbeta, dx, ld_dx, dx_colsum, ws, ws_floats, stream);
-}
-
-extern "C" int egnn_bn_act_bwd_f32(const float* x, int64_t ld, const float* dy, int64_t ld_dy, int64_t n, int64_t C,
-                                   const float* mean, const float* var, float eps, const float* gamma, const float* beta, int relu,
-                                   float p, uint64_t seed, const uint64_t* seed_dev, int batch_stats, float* dgamma, float* dbeta,
-                                   float* dx, int64_t ld_dx, float* ws, size_t ws_floats, void* stream) {
-  return egnn_bn_act_bwd_colsum_f32(x, ld, dy, ld_dy, n, C, mean, var, eps, gamma, beta, relu, p, seed, seed_dev, batch_stats, dgamma, dbeta, dx,
-                                    ld_dx, nullptr, ws, ws_floats, stream);
+  return egnn_bn_act_bwd_apply_f32(bn, dy, ld_dy, dbeta, dgamma, batch_stats ? 1.f / (float)bn->n : 0.f, dbeta, dx, ld_dx, dx_colsum, ws,
+                                   ws_floats, stream);
 }
 
 extern "C" int egnn_bn_running_update_f32(const float* mean, const float* var, int64_t C, int64_t n, float momentum, float* running_mean,
@@ -1007,13 +936,14 @@ int egnn_skinny_fwd_tile(const float* X, int64_t ldx, const float* W, int64_t ld
   return egnn_launch_status();
 }
 
-extern "C" int egnn_bn_act_linear_fwd_f32(const float* x, int64_t ld, int64_t n, int64_t C, const float* mean, const float* var, float eps,
-                                          const float* gamma, const float* beta, int relu, float p, uint64_t seed, const uint64_t* seed_dev,
-                                          const float* W, int64_t ldw, int w_kmajor, int64_t Ks, float* h, int64_t ldh, float* xw,
-                                          int64_t ld_xw, void* stream) {
-  EGNN_CHECK_ARG(n > 0 && x && mean && var && W && h && xw && ld >= C && ldh >= C && ld_xw >= Ks && p >= 0.f && p < 1.f);
-  if (!shape_ok(x, ld, C) || !shape_ok(h, ldh, C)) return EGNN_EALIGN;
-  const BnParams q{x, ld, n, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, nullptr};
+extern "C" int egnn_bn_act_linear_fwd_f32(const egnn_bn_act_t* bn, const float* W, int64_t ldw, int w_kmajor, int64_t Ks, float* h,
+                                          int64_t ldh, float* xw, int64_t ld_xw, void* stream) {
+  BnParams q, qo;
+  const int rc = bn_unpack(bn, q, qo);
+  if (rc != EGNN_OK) return rc;
+  const int64_t n = bn->n, C = bn->C, ld = bn->ld;
+  EGNN_CHECK_ARG(!bn->pick && W && h && xw && ldh >= C && ld_xw >= Ks && bn->p >= 0.f && bn->p < 1.f);
+  if (!shape_ok(h, ldh, C)) return EGNN_EALIGN;
   if (C != 256 || Ks < 1 || Ks > 64 || n * ld >= (1LL << 31) - 64 || n * ldh >= (1LL << 31) - 64) return EGNN_EALIGN;
   const int nt = (int)((Ks + 15) / 16);
   const int64_t nblk = (n + 15) / 16;
@@ -1037,17 +967,19 @@ extern "C" size_t egnn_skinny_dx_bn_ws_floats(int64_t M, int64_t C) {
 
 // The tail backward in its two halves, so that a node-range shard can put the all-rank sum of (sum d, sum d xhat) between them
 // (SyncBN, dist.py): `reduce` leaves d = dh * gate in dx and this shard's column sums in dbeta / dgamma; `apply` turns the stored d
-// into dx with whatever sums / 1/count it is handed.  egnn_skinny_dx_bn_bwd_f32 = reduce + apply with the local sums and 1/M.
-extern "C" int egnn_skinny_dx_bn_bwd_reduce_f32(const float* G, int64_t ldg, const float* W, int64_t ldw, int w_kmajor, int64_t M, int64_t C,
-                                                int64_t Ks, float alpha, const float* addend, int64_t ld_addend, const float* add_rows,
-                                                int64_t ld_add_rows, const int32_t* add_inv, const float* x, int64_t ldx, const float* mean,
-                                                const float* var, float eps, const float* gamma, const float* beta, int relu, float p,
-                                                uint64_t seed, const uint64_t* seed_dev, float* dgamma, float* dbeta, float* dx,
-                                                int64_t ld_dx, float* ws, size_t ws_floats, void* stream) {
-  EGNN_CHECK_ARG(M > 0 && G && W && x && mean && var && dgamma && dbeta && dx && ws && ldg >= Ks && ldx >= C && ld_dx >= C);
+// into dx with whatever sums / 1/count it is handed (on one GPU: the local sums and 1/M).
+extern "C" int egnn_skinny_dx_bn_bwd_reduce_f32(const float* G, int64_t ldg, const float* W, int64_t ldw, int w_kmajor, int64_t Ks,
+                                                float alpha, const float* addend, int64_t ld_addend, const float* add_rows,
+                                                int64_t ld_add_rows, const int32_t* add_inv, const egnn_bn_act_t* bn, float* dgamma,
+                                                float* dbeta, float* dx, int64_t ld_dx, float* ws, size_t ws_floats, void* stream) {
+  BnParams q, qo;
+  const int rc = bn_unpack(bn, q, qo);
+  if (rc != EGNN_OK) return rc;
+  const int64_t M = bn->n, C = bn->C, ldx = bn->ld;
+  EGNN_CHECK_ARG(!bn->pick && G && W && dgamma && dbeta && dx && ws && ldg >= Ks && ld_dx >= C);
   EGNN_CHECK_ARG((add_inv == nullptr) == (add_rows == nullptr));
   if (Ks > 64 || Ks < 1 || C % 64 != 0 || C < 64 || C > 1024) return EGNN_EALIGN;
-  if (!shape_ok(x, ldx, C) || !shape_ok(dx, ld_dx, C)) return EGNN_EALIGN;
+  if (!shape_ok(dx, ld_dx, C)) return EGNN_EALIGN;
   if (addend && !shape_ok(addend, ld_addend, C)) return EGNN_EALIGN;
   if (add_rows && !shape_ok(add_rows, ld_add_rows, C)) return EGNN_EALIGN;
   if (w_kmajor && (ldw % 4 != 0 || !egnn_aligned16(W))) return EGNN_EALIGN;
@@ -1056,7 +988,6 @@ extern "C" int egnn_skinny_dx_bn_bwd_reduce_f32(const float* G, int64_t ldg, con
   const int64_t lim = (1LL << 31) - 64;   // the kernel addresses with 32-bit element offsets
   if (M * ldx >= lim || M * ld_dx >= lim || (addend && M * ld_addend >= lim) || (add_rows && M * ld_add_rows >= lim)) return EGNN_EALIGN;
   hipStream_t st = (hipStream_t)stream;
-  const BnParams q{x, ldx, M, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, nullptr};
   int64_t sbs = (M + kDxBnRows - 1) / kDxBnRows;
   const int ksteps = (int)((Ks + 3) / 4);
   if (tail_tile_form(C, ksteps)) {
@@ -1086,15 +1017,16 @@ extern "C" int egnn_skinny_dx_bn_bwd_reduce_f32(const float* G, int64_t ldg, con
 }
 
 // dx <- gamma rstd (d - (sum_dbeta + xhat sum_dgamma) * inv_count), in place over the d that the reduce half left in dx
-extern "C" int egnn_bn_bwd_apply_stored_f32(const float* x, int64_t ldx, int64_t M, int64_t C, const float* mean, const float* var, float eps,
-                                            const float* gamma, const float* beta, int relu, float p, uint64_t seed, const uint64_t* seed_dev,
-                                            const float* sum_dbeta, const float* sum_dgamma, float inv_count, float* dx, int64_t ld_dx,
-                                            float* dx_colsum, float* ws, size_t ws_floats, void* stream) {
-  EGNN_CHECK_ARG(M > 0 && x && mean && var && sum_dbeta && sum_dgamma && dx && ldx >= C && ld_dx >= C);
-  if (!shape_ok(x, ldx, C) || !shape_ok(dx, ld_dx, C)) return EGNN_EALIGN;
+extern "C" int egnn_bn_bwd_apply_stored_f32(const egnn_bn_act_t* bn, const float* sum_dbeta, const float* sum_dgamma, float inv_count,
+                                            float* dx, int64_t ld_dx, float* dx_colsum, float* ws, size_t ws_floats, void* stream) {
+  BnParams q, qo;
+  const int rc = bn_unpack(bn, q, qo);
+  if (rc != EGNN_OK) return rc;
+  const int64_t M = bn->n, C = bn->C;
+  EGNN_CHECK_ARG(!bn->pick && sum_dbeta && sum_dgamma && dx && ld_dx >= C);
+  if (!shape_ok(dx, ld_dx, C)) return EGNN_EALIGN;
   if (dx_colsum && (!ws || ws_floats < egnn_bn_ws_floats(C))) return EGNN_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const BnParams q{x, ldx, M, C, mean, var, eps, gamma, beta, relu, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, nullptr};
   int nb = row_blocks(M);
   if (dx_colsum) {
     if (nb > 2 * kStatBlocks) nb = 2 * kStatBlocks;
@@ -1108,20 +1040,6 @@ extern "C" int egnn_bn_bwd_apply_stored_f32(const float* x, int64_t ldx, int64_t
                        dx, ld_dx, (float*)nullptr);
   }
   return egnn_launch_status();
-}
-
-extern "C" int egnn_skinny_dx_bn_bwd_f32(const float* G, int64_t ldg, const float* W, int64_t ldw, int w_kmajor, int64_t M, int64_t C,
-                                         int64_t Ks, float alpha, const float* addend, int64_t ld_addend, const float* add_rows,
-                                         int64_t ld_add_rows, const int32_t* add_inv, const float* x, int64_t ldx, const float* mean,
-                                         const float* var, float eps, const float* gamma, const float* beta, int relu, float p,
-                                         uint64_t seed, const uint64_t* seed_dev, int batch_stats, float* dgamma, float* dbeta, float* dx,
-                                         int64_t ld_dx, float* dx_colsum, float* ws, size_t ws_floats, void* stream) {
-  const int rc = egnn_skinny_dx_bn_bwd_reduce_f32(G, ldg, W, ldw, w_kmajor, M, C, Ks, alpha, addend, ld_addend, add_rows, ld_add_rows, add_inv, x,
-                                                  ldx, mean, var, eps, gamma, beta, relu, p, seed, seed_dev, dgamma, dbeta, dx, ld_dx, ws,
-                                                  ws_floats, stream);
-  if (rc != EGNN_OK) return rc;
-  return egnn_bn_bwd_apply_stored_f32(x, ldx, M, C, mean, var, eps, gamma, beta, relu, p, seed, seed_dev, dbeta, dgamma,
-                                      batch_stats ? 1.f / (float)M : 0.f, dx, ld_dx, dx_colsum, ws, ws_floats, stream);
 }
 
 namespace {

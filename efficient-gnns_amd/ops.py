@@ -1,6 +1,7 @@
 """autograd.Function wrappers around the C ABI (include/egnn_hip.h).  GPU only; no CPU fallback."""
 from __future__ import annotations
 
+import ctypes
 import os
 
 import torch
@@ -253,7 +254,7 @@ def _fresh(g, tap_box):
 
 def colsum(g: Tensor) -> Tensor:
     """Column sums of a [n, C] gradient (bias gradients).  A gradient that comes straight out of the fused BatchNorm
-    backward carries them already (formed while dx was written: egnn_bn_act_bwd_colsum_f32), tagged with the tensor
+    backward carries them already (formed while dx was written: egnn_bn_act_bwd_f32), tagged with the tensor
     version they belong to -- any in-place change of the gradient since then (autograd accumulation) voids the tag."""
     tag = getattr(g, "_egnn_colsum", None)
     if tag is not None and tag[1] == g._version and tag[0].shape[0] == g.shape[1]:
@@ -1040,29 +1041,45 @@ def _bn_shape_ok(x: Tensor) -> bool:
     return x.is_cuda and C % 4 == 0 and C <= 1024 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
 
 
+# an empty ``pick`` (a shard without sampled rows) may have no storage; the C side still needs a non-NULL pick to take the picked-rows
+# form and reads no entry of it (n_pick = 0)
+_NO_PICKED_ROW = ctypes.c_int64(-1)
+
+
+def _bn_desc(x, gamma, beta, mean, var, eps, relu, p, seed, seed_dev, pick=None) -> ctypes.Structure:
+    """The egnn_bn_act_t descriptor (include/egnn_hip.h) of one fused BatchNorm call over the rows of ``x``: every row, or the output
+    rows ``pick``.  Built per call from the tensors at hand; the entry points read it only while they run."""
+    n, C = x.shape
+    pick_ptr = None if pick is None else (pick.data_ptr() or ctypes.addressof(_NO_PICKED_ROW))
+    return _lib.BnAct(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), float(eps), _lib.ptr(gamma), _lib.ptr(beta),
+                      int(relu), float(p), int(seed), _lib.ptr(seed_dev), pick_ptr, 0 if pick is None else pick.numel())
+
+
+def _sync_sums(sums: Tensor, sync) -> Tensor:
+    """[sum d | sum d*xhat] of ALL ranks divided by their row total: ONE all-reduce, scaled on the device (no host read of the count)."""
+    import torch.distributed as dist
+    total, group = sync
+    if dist.get_world_size(group) > 1:
+        sums = sums.clone()
+        dist.all_reduce(sums, group=group)
+    return sums / total
+
+
 def _bn_act_fwd(x, gamma, beta, mean, var, eps, relu, p, seed, seed_dev, pick=None) -> Tensor:
-    """y = drop(relu(bn(x))) with the given statistics: every row, or only the rows ``pick`` (egnn_bn_act_rows_fwd_f32).  An empty
-    result (a shard without rows, an empty ``pick``) launches nothing."""
+    """y = drop(relu(bn(x))) with the given statistics: every row, or only the rows ``pick``.  An empty result (a shard without rows,
+    an empty ``pick``) launches nothing."""
     n, C = x.shape
     y = torch.empty(n if pick is None else pick.numel(), C, dtype=torch.float32, device=x.device)
     if y.shape[0] == 0:
         return y
-    if pick is None:
-        rc = _lib.load().egnn_bn_act_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), float(eps), _lib.ptr(gamma),
-                                             _lib.ptr(beta), int(relu), float(p), int(seed), _lib.ptr(seed_dev), _lib.ptr(y), y.stride(0),
-                                             _lib.stream())
-        _lib.check(rc, "egnn_bn_act_fwd_f32")
-    else:
-        rc = _lib.load().egnn_bn_act_rows_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), pick.numel(), _lib.ptr(mean), _lib.ptr(var),
-                                                  float(eps), _lib.ptr(gamma), _lib.ptr(beta), int(relu), float(p), int(seed),
-                                                  _lib.ptr(seed_dev), _lib.ptr(y), y.stride(0), _lib.stream())
-        _lib.check(rc, "egnn_bn_act_rows_fwd_f32")
+    bn = _bn_desc(x, gamma, beta, mean, var, eps, relu, p, seed, seed_dev, pick)
+    _lib.check(_lib.load().egnn_bn_act_fwd_f32(ctypes.byref(bn), _lib.ptr(y), y.stride(0), _lib.stream()), "egnn_bn_act_fwd_f32")
     return y
 
 
 class _BnAct(torch.autograd.Function):
     """y = drop(relu(bn(x))) with the statistics (mean, var) taken by the caller.  ``pick`` (int64 [S], unique row ids) = form only the
-    output rows ``pick``: y[i] = act(bn(x[pick[i]])) -- the statistics still span all rows of x, and so does dx (egnn_bn_act_rows_*_f32).
+    output rows ``pick``: y[i] = act(bn(x[pick[i]])) -- the statistics still span all rows of x, and so does dx.
     ``sync`` = None: statistics of this tensor alone.  ``sync`` = (total rows [1] on the device, group): statistics of the rows of ALL
     ranks (``_sync_stats``; node-range shards, where ``pick`` may hold no row of this shard) -- the backward all-reduces
     [sum d, sum d*xhat] between its reduce half and its apply half; the parameter gradients stay this shard's local sums."""
@@ -1092,73 +1109,34 @@ class _BnAct(torch.autograd.Function):
         gy = _rowmajor(gy)
         n, C = x.shape
         lib, dev = _lib.load(), x.device
-        if ctx.sync is None:
-            # statistics of this tensor alone: one backward launch, no collective between its halves
-            dx = torch.empty_like(x)
-            dgamma = torch.empty(C, dtype=torch.float32, device=dev)
-            dbeta = torch.empty(C, dtype=torch.float32, device=dev)
-            nws = lib.egnn_bn_ws_floats(C)
-            ws = torch.empty(nws, dtype=torch.float32, device=dev)
-            # the producer of x usually added a bias (GCNConv / nn.Linear in front of the BatchNorm): its gradient is the column
-            # sum of dx, formed in the same pass (ops.colsum picks the tag up)
-            cs = torch.empty(C, dtype=torch.float32, device=dev) if batch_stats else None
-            if pick is None:
-                rc = lib.egnn_bn_act_bwd_colsum_f32(_lib.ptr(x), x.stride(0), _lib.ptr(gy), gy.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), eps,
-                                                    _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev), batch_stats,
-                                                    _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dx), dx.stride(0), _lib.ptr(cs), _lib.ptr(ws), nws,
-                                                    _lib.stream())
-                _lib.check(rc, "egnn_bn_act_bwd_colsum_f32")
-            else:
-                rc = lib.egnn_bn_act_rows_bwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), pick.numel(), _lib.ptr(gy), gy.stride(0),
-                                                  _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed,
-                                                  _lib.ptr(ctx.seed_dev), batch_stats, _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dx), dx.stride(0),
-                                                  _lib.ptr(cs), _lib.ptr(ws), nws, _lib.stream())
-                _lib.check(rc, "egnn_bn_act_rows_bwd_f32")
-            if cs is not None:
-                dx._egnn_colsum = (cs, dx._version)
-            return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None
-        # all ranks: reduce half, ONE all-reduce of [sum d | sum d*xhat], apply half
-        import torch.distributed as dist
-        total, group = ctx.sync
-        n_red = n if pick is None else pick.numel()                  # rows that carry a gradient
-        sums = torch.empty(2 * C, dtype=torch.float32, device=dev)   # [dbeta | dgamma] of this shard
+        bn = ctypes.byref(_bn_desc(x, gamma, beta, mean, var, eps, relu, p, seed, ctx.seed_dev, pick))
+        sums = torch.empty(2 * C, dtype=torch.float32, device=dev)   # [dbeta | dgamma] of this tensor
+        dx = torch.empty_like(x)
         nws = lib.egnn_bn_ws_floats(C)
         ws = torch.empty(nws, dtype=torch.float32, device=dev) if n > 0 else None
-        if n_red > 0 and pick is None:
-            rc = lib.egnn_bn_act_bwd_reduce_f32(_lib.ptr(x), x.stride(0), _lib.ptr(gy), gy.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var),
-                                                eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev), _lib.ptr(sums[C:]),
-                                                _lib.ptr(sums), _lib.ptr(ws), nws, _lib.stream())
-            _lib.check(rc, "egnn_bn_act_bwd_reduce_f32")
-        elif n_red > 0:
-            rc = lib.egnn_bn_act_rows_bwd_reduce_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), n_red, _lib.ptr(gy), gy.stride(0),
-                                                     _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed,
-                                                     _lib.ptr(ctx.seed_dev), _lib.ptr(sums[C:]), _lib.ptr(sums), _lib.ptr(ws), nws, _lib.stream())
-            _lib.check(rc, "egnn_bn_act_rows_bwd_reduce_f32")
+        # the producer of x usually added a bias (GCNConv / nn.Linear in front of the BatchNorm): its gradient is the column sum of dx,
+        # formed in the same pass (ops.colsum picks the tag up)
+        cs = torch.empty(C, dtype=torch.float32, device=dev) if (batch_stats and n > 0) else None
+        if ctx.sync is None:
+            # statistics of this tensor alone: one call, no collective between its halves
+            _lib.check(lib.egnn_bn_act_bwd_f32(bn, _lib.ptr(gy), gy.stride(0), batch_stats, _lib.ptr(sums[C:]), _lib.ptr(sums), _lib.ptr(dx),
+                                               dx.stride(0), _lib.ptr(cs), _lib.ptr(ws), nws, _lib.stream()), "egnn_bn_act_bwd_f32")
         else:
-            sums.zero_()
-        local = sums                                                 # parameter grads stay local (the flat all-reduce sums them)
-        if dist.get_world_size(group) > 1:
-            sums = sums.clone()
-            dist.all_reduce(sums, group=group)
-        scaled = sums / total                                        # scaled on the device (no host read of the row count)
-        dx = torch.empty_like(x)
-        if n > 0:
-            # the column sums of dx (bias gradient of the conv / Linear in front) come out of the same pass (ops.colsum picks the tag up)
-            cs = torch.empty(C, dtype=torch.float32, device=dev)
-            if pick is None:
-                rc = lib.egnn_bn_act_bwd_apply_colsum_f32(_lib.ptr(x), x.stride(0), _lib.ptr(gy), gy.stride(0), n, C, _lib.ptr(mean),
-                                                          _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev),
-                                                          _lib.ptr(scaled), _lib.ptr(scaled[C:]), 1.0, _lib.ptr(dx), dx.stride(0), _lib.ptr(cs),
-                                                          _lib.ptr(ws), nws, _lib.stream())
-                _lib.check(rc, "egnn_bn_act_bwd_apply_colsum_f32")
+            # all ranks: reduce half, ONE all-reduce of [sum d | sum d*xhat], apply half; the parameter grads stay local (the flat
+            # all-reduce sums them)
+            if (n if pick is None else pick.numel()) > 0:          # rows that carry a gradient
+                _lib.check(lib.egnn_bn_act_bwd_reduce_f32(bn, _lib.ptr(gy), gy.stride(0), _lib.ptr(sums[C:]), _lib.ptr(sums), _lib.ptr(ws),
+                                                          nws, _lib.stream()), "egnn_bn_act_bwd_reduce_f32")
             else:
-                rc = lib.egnn_bn_act_rows_bwd_apply_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(pick), n_red, _lib.ptr(gy), gy.stride(0),
-                                                        _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed,
-                                                        _lib.ptr(ctx.seed_dev), _lib.ptr(scaled), _lib.ptr(scaled[C:]), 1.0, _lib.ptr(local),
-                                                        _lib.ptr(dx), dx.stride(0), _lib.ptr(cs), _lib.ptr(ws), nws, _lib.stream())
-                _lib.check(rc, "egnn_bn_act_rows_bwd_apply_f32")
+                sums.zero_()
+            scaled = _sync_sums(sums, ctx.sync)
+            if n > 0:
+                _lib.check(lib.egnn_bn_act_bwd_apply_f32(bn, _lib.ptr(gy), gy.stride(0), _lib.ptr(scaled), _lib.ptr(scaled[C:]), 1.0,
+                                                         _lib.ptr(sums), _lib.ptr(dx), dx.stride(0), _lib.ptr(cs), _lib.ptr(ws), nws,
+                                                         _lib.stream()), "egnn_bn_act_bwd_apply_f32")
+        if cs is not None:
             dx._egnn_colsum = (cs, dx._version)
-        return dx, local[C:], local[:C], None, None, None, None, None, None, None, None, None
+        return dx, sums[C:], sums[:C], None, None, None, None, None, None, None, None, None
 
 
 def _bn_prepare(x: Tensor, bn, p: float, training: bool):
@@ -1237,9 +1215,9 @@ def _bn_act_linear_fwd(x, w, gamma, beta, mean, var, eps, relu, p, seed, seed_de
     if n > 0 and w.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0:
         h = torch.empty(n, C, dtype=torch.float32, device=x.device)
         xw = torch.empty(n, w.shape[1], dtype=torch.float32, device=x.device)
-        rc = _lib.load().egnn_bn_act_linear_fwd_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), float(eps), _lib.ptr(gamma),
-                                                    _lib.ptr(beta), int(relu), float(p), int(seed), _lib.ptr(seed_dev), _lib.ptr(w), w.stride(0), 0,
-                                                    w.shape[1], _lib.ptr(h), h.stride(0), _lib.ptr(xw), xw.stride(0), _lib.stream())
+        bn = _bn_desc(x, gamma, beta, mean, var, eps, relu, p, seed, seed_dev)
+        rc = _lib.load().egnn_bn_act_linear_fwd_f32(ctypes.byref(bn), _lib.ptr(w), w.stride(0), 0, w.shape[1], _lib.ptr(h), h.stride(0),
+                                                    _lib.ptr(xw), xw.stride(0), _lib.stream())
         if rc != _lib.EGNN_EALIGN:
             _lib.check(rc, "egnn_bn_act_linear_fwd_f32")
             return h, xw
@@ -1251,7 +1229,7 @@ class _BnActLinear(torch.autograd.Function):
     """(h, h @ w) with h = drop(relu(bn(x))) and a NARROW w [C, Ks] (the class count): the student's last hidden layer feeding its
     output conv (gnn.py:47-52).  h also carries the gradient tap of ``grad_tap`` (the projection head's row-compact input gradient).
     Backward: dh = G w^T + tap rows (+ any dense gradient of h) is formed in MFMA tiles and goes through the BatchNorm backward
-    without being stored (egnn_skinny_dx_bn_bwd_f32): one pass over [n, C] instead of four.  ``sync``: as in ``_BnAct`` (all-rank
+    without being stored (egnn_skinny_dx_bn_bwd_reduce_f32): one pass over [n, C] instead of four.  ``sync``: as in ``_BnAct`` (all-rank
     statistics; the backward's reduce and apply halves around ONE all-reduce, see ``_tail_backward``)."""
 
     @staticmethod
@@ -1311,38 +1289,32 @@ def _tail_backward(ctx, g_h, g_xw, x, gamma, beta, mean, var, h, w, eps, relu, p
         if fused:
             inv = _inverse_rows(idx, n)
 
+    bn = ctypes.byref(_bn_desc(x, gamma, beta, mean, var, eps, relu, p, seed, ctx.seed_dev))
+
     def apply_sums():
         """(sum_dbeta, sum_dgamma, inv_count) the apply half uses; the all-rank sum on shards."""
         if sync is None:
             return dbeta, dgamma, (1.0 / n if batch_stats else 0.0)
-        import torch.distributed as dist
-        total, group = sync
-        red = sums
-        if dist.get_world_size(group) > 1:
-            red = sums.clone()
-            dist.all_reduce(red, group=group)
-        red = red / total                                          # scaled on the device (no host read of the row count)
+        red = _sync_sums(sums, sync)
         return red[:C], red[C:], 1.0
 
     done = False
     if fused:
         nws = lib.egnn_skinny_dx_bn_ws_floats(n, C)
         ws = torch.empty(nws, dtype=torch.float32, device=dev)
-        rc = lib.egnn_skinny_dx_bn_bwd_reduce_f32(_lib.ptr(g_xw), g_xw.stride(0), _lib.ptr(w), w.stride(0), 0, n, C, Ks, 1.0,
-                                                  _lib.ptr(g_h), 0 if g_h is None else g_h.stride(0), _lib.ptr(rows),
-                                                  0 if rows is None else rows.stride(0), _lib.ptr(inv), _lib.ptr(x), x.stride(0), _lib.ptr(mean),
-                                                  _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev),
-                                                  _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dx), dx.stride(0), _lib.ptr(ws), nws, _lib.stream())
+        rc = lib.egnn_skinny_dx_bn_bwd_reduce_f32(_lib.ptr(g_xw), g_xw.stride(0), _lib.ptr(w), w.stride(0), 0, Ks, 1.0, _lib.ptr(g_h),
+                                                  0 if g_h is None else g_h.stride(0), _lib.ptr(rows), 0 if rows is None else rows.stride(0),
+                                                  _lib.ptr(inv), bn, _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dx), dx.stride(0), _lib.ptr(ws),
+                                                  nws, _lib.stream())
         if rc != _lib.EGNN_EALIGN:     # EGNN_EALIGN: beyond the kernel's 32-bit element offsets (n * ld >= 2^31) -> the separate passes below
             _lib.check(rc, "egnn_skinny_dx_bn_bwd_reduce_f32")
             sb, sg, inv_count = apply_sums()
-            _lib.check(lib.egnn_bn_bwd_apply_stored_f32(_lib.ptr(x), x.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma),
-                                                        _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev), _lib.ptr(sb), _lib.ptr(sg),
-                                                        inv_count, _lib.ptr(dx), dx.stride(0), _lib.ptr(cs), _lib.ptr(ws), nws, _lib.stream()),
-                       "egnn_bn_bwd_apply_stored_f32")
+            _lib.check(lib.egnn_bn_bwd_apply_stored_f32(bn, _lib.ptr(sb), _lib.ptr(sg), inv_count, _lib.ptr(dx), dx.stride(0), _lib.ptr(cs),
+                                                        _lib.ptr(ws), nws, _lib.stream()), "egnn_bn_bwd_apply_stored_f32")
             done = True
     if not done:
-        # the separate passes: dense dh, the tap rows added into it, the BatchNorm backward (reduce, [all-reduce,] apply)
+        # the separate passes: dense dh, the tap rows added into it, the BatchNorm backward (reduce, [all-reduce,] apply; the column
+        # sums of dx -- the bias gradient of the conv in front -- in the apply pass, as on the fused route)
         dh = None
         if n > 0:
             dh = gemm_raw(g_xw, w, False, True) if g_xw is not None else None
@@ -1356,21 +1328,12 @@ def _tail_backward(ctx, g_h, g_xw, x, gamma, beta, mean, var, h, w, eps, relu, p
                                                  rows.shape[1], _lib.stream()), "egnn_rows_add_f32")
             nws = lib.egnn_bn_ws_floats(C)
             ws = torch.empty(nws, dtype=torch.float32, device=dev)
-            _lib.check(lib.egnn_bn_act_bwd_reduce_f32(_lib.ptr(x), x.stride(0), _lib.ptr(dh), dh.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var),
-                                                      eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev), _lib.ptr(dgamma),
-                                                      _lib.ptr(dbeta), _lib.ptr(ws), nws, _lib.stream()), "egnn_bn_act_bwd_reduce_f32")
+            _lib.check(lib.egnn_bn_act_bwd_reduce_f32(bn, _lib.ptr(dh), dh.stride(0), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws), nws,
+                                                      _lib.stream()), "egnn_bn_act_bwd_reduce_f32")
         sb, sg, inv_count = apply_sums()
-        if n > 0 and cs is not None:
-            # apply half + the column sums of dx (the bias gradient of the conv in front) in the same pass, as on the fused route
-            _lib.check(lib.egnn_bn_act_bwd_apply_colsum_f32(_lib.ptr(x), x.stride(0), _lib.ptr(dh), dh.stride(0), n, C, _lib.ptr(mean),
-                                                            _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed,
-                                                            _lib.ptr(ctx.seed_dev), _lib.ptr(sb), _lib.ptr(sg), inv_count, _lib.ptr(dx),
-                                                            dx.stride(0), _lib.ptr(cs), _lib.ptr(ws), nws, _lib.stream()),
-                       "egnn_bn_act_bwd_apply_colsum_f32")
-        elif n > 0:
-            _lib.check(lib.egnn_bn_act_bwd_apply_f32(_lib.ptr(x), x.stride(0), _lib.ptr(dh), dh.stride(0), n, C, _lib.ptr(mean), _lib.ptr(var),
-                                                     eps, _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, _lib.ptr(ctx.seed_dev), _lib.ptr(sb),
-                                                     _lib.ptr(sg), inv_count, _lib.ptr(dx), dx.stride(0), _lib.stream()), "egnn_bn_act_bwd_apply_f32")
+        if n > 0:
+            _lib.check(lib.egnn_bn_act_bwd_apply_f32(bn, _lib.ptr(dh), dh.stride(0), _lib.ptr(sb), _lib.ptr(sg), inv_count, None, _lib.ptr(dx),
+                                                     dx.stride(0), _lib.ptr(cs), _lib.ptr(ws), nws, _lib.stream()), "egnn_bn_act_bwd_apply_f32")
     if cs is not None:
         dx._egnn_colsum = (cs, dx._version)
     return dx, dgamma, dbeta, gw

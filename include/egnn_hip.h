@@ -39,7 +39,7 @@ extern "C" {
 #define EGNN_EWORKSPACE (-3) /* caller-provided workspace too small */
 #define EGNN_EALIGN (-4)   /* pointer / leading dimension not aligned as the entry point requires */
 
-#define EGNN_ABI_VERSION 6
+#define EGNN_ABI_VERSION 7
 int egnn_abi_version(void);
 const char* egnn_error_string(int code);
 /* Number of distinct kernels-families compiled in; used by the loader's self check. */
@@ -459,122 +459,80 @@ int egnn_gat_aggregate_bwd_f32(const int64_t* colptr, const int64_t* t_col, cons
  * Shapes: x [n,C] fp32, C % 4 == 0, C <= 1024, ld % 4 == 0, 16-byte aligned (else EGNN_EALIGN: the host uses
  * the torch operators for such shapes).
  *   egnn_bn_stats_f32     mean[c], biased var[c] over the n rows (training statistics)
- *   egnn_bn_act_fwd_f32   y = drop_p(relu?(gamma * (x - mean) * rsqrt(var + eps) + beta)); the dropout mask is a
- *                         counter-based hash of (seed + *seed_dev, row*C + c): keep if u >= p, kept values scaled 1/(1-p);
- *                         seed_dev: nullable device scalar added to `seed` -- a per-step value that lives on the device,
- *                         so that a captured hipGraph of the step draws a fresh mask on every replay
- *   egnn_bn_act_bwd_f32   recomputes xhat / ReLU sign / mask from x and seed; dgamma, dbeta [C]; dx [n,C];
- *                         batch_stats != 0: mean/var are this batch's statistics (training backward, the
- *                         -(sum d + xhat sum d xhat)/n terms apply); 0: running statistics (eval-mode graph)
- *   egnn_bn_act_bwd_reduce_f32 / _apply_f32   the two halves of the backward, for batch statistics that span several
- *                         GPUs (node-range shards): reduce writes this shard's dbeta = sum d and
- *                         dgamma = sum d*xhat; the caller all-reduces them over RCCL and passes the totals plus
- *                         inv_count = 1 / (rows of ALL shards) to apply (inv_count = 0: running statistics)
- * ws: egnn_bn_ws_floats(C) floats. */
+ *
+ * Every other entry point of this family takes its BatchNorm operands as one descriptor, egnn_bn_act_t.  The call reads
+ * it only while it runs and never keeps the pointer (kernel arguments are copied at launch: the descriptor may live on the
+ * caller's stack, also while a hipGraph is captured).  bn == NULL is EGNN_EINVAL.
+ *   y = drop_p(relu?(gamma * (x - mean) * rsqrt(var + eps) + beta)); gamma / beta nullable (1 / 0); the dropout mask is a
+ *   counter-based hash of (seed + *seed_dev, row*C + c): keep if u >= p, kept values scaled 1/(1-p); seed_dev: nullable
+ *   device scalar added to `seed` -- a per-step value that lives on the device, so that a captured hipGraph of the step
+ *   draws a fresh mask on every replay.
+ *   pick == NULL: every row of x is an output row.  pick != NULL: only the OUTPUT ROWS pick (n_pick unique ids into the n rows
+ *   of x) are formed / carry a gradient -- the projection heads feeding the sampled criteria (/root/reference/arxiv_pyg/
+ *   gnn.py:296-306 -> criterion.py:62-65,134-137: the statistics span all train rows, the criterion keeps max_samples of the
+ *   output rows).  y / dy then have n_pick rows, y[i] = act(bn(x[pick[i]])); dx always has all n rows (the mean / variance
+ *   terms reach every row).  The apply half takes n_pick == 0 (a shard without picked rows; pick still non-NULL, not read);
+ *   the other calls need n_pick > 0. */
+typedef struct egnn_bn_act {
+  const float* x; int64_t ld; int64_t n; int64_t C;   /* x [n, C]: the rows the statistics span */
+  const float* mean; const float* var; float eps;
+  const float* gamma; const float* beta;
+  int relu; float p; uint64_t seed; const uint64_t* seed_dev;
+  const int64_t* pick; int64_t n_pick;                 /* NULL / 0: every row; else the unique output rows */
+} egnn_bn_act_t;
+
+/*   egnn_bn_act_fwd_f32         y [out rows, C]
+ *   egnn_bn_act_bwd_f32         recomputes xhat / ReLU sign / mask from x and seed; dgamma = sum d*xhat, dbeta = sum d [C] over the
+ *                               output rows; dx [n,C]; batch_stats != 0: mean/var are this batch's statistics (training backward,
+ *                               the -(sum d + xhat sum d xhat)/n terms apply); 0: running statistics (eval-mode graph).
+ *                               dx_colsum [C] nullable: the column sums of dx -- the gradient of a bias added in front of the
+ *                               BatchNorm (GCNConv / nn.Linear bias, gnn.py:47-48,296-306), formed while dx is written instead of by
+ *                               a second pass over it (ATen: gy.sum(0))
+ *   egnn_bn_act_bwd_reduce_f32 / _apply_f32   the two halves of egnn_bn_act_bwd_f32, for batch statistics that span several
+ *                               GPUs (node-range shards, SURVEY.md 8e: SyncBN semantics): reduce writes this shard's dbeta = sum d and
+ *                               dgamma = sum d*xhat; the caller all-reduces them over RCCL and passes the totals plus inv_count =
+ *                               1 / (rows of ALL shards) to apply (inv_count = 0: running statistics; the all-rank sums already
+ *                               divided by the row total go with inv_count = 1).  With pick and dx_colsum, apply needs local_dbeta
+ *                               (this tensor's own sum d: the picked rows' own term is local); otherwise local_dbeta is not read.
+ * ws: egnn_bn_ws_floats(C) floats (apply: only with dx_colsum). */
 size_t egnn_bn_ws_floats(int64_t C);
 int egnn_bn_stats_f32(const float* x, int64_t ld, int64_t n, int64_t C, float* mean, float* var, float* ws, size_t ws_floats,
                       void* stream);
-int egnn_bn_act_fwd_f32(const float* x, int64_t ld, int64_t n, int64_t C, const float* mean, const float* var, float eps,
-                        const float* gamma, const float* beta, int relu, float p, uint64_t seed, const uint64_t* seed_dev,
-                        float* y, int64_t ldy, void* stream);
-int egnn_bn_act_bwd_f32(const float* x, int64_t ld, const float* dy, int64_t ld_dy, int64_t n, int64_t C, const float* mean,
-                        const float* var, float eps, const float* gamma, const float* beta, int relu, float p, uint64_t seed,
-                        const uint64_t* seed_dev, int batch_stats, float* dgamma, float* dbeta, float* dx, int64_t ld_dx, float* ws,
-                        size_t ws_floats, void* stream);
+int egnn_bn_act_fwd_f32(const egnn_bn_act_t* bn, float* y, int64_t ldy, void* stream);
+int egnn_bn_act_bwd_f32(const egnn_bn_act_t* bn, const float* dy, int64_t ld_dy, int batch_stats, float* dgamma, float* dbeta,
+                        float* dx, int64_t ld_dx, float* dx_colsum, float* ws, size_t ws_floats, void* stream);
+int egnn_bn_act_bwd_reduce_f32(const egnn_bn_act_t* bn, const float* dy, int64_t ld_dy, float* dgamma, float* dbeta, float* ws,
+                               size_t ws_floats, void* stream);
+int egnn_bn_act_bwd_apply_f32(const egnn_bn_act_t* bn, const float* dy, int64_t ld_dy, const float* sum_dbeta, const float* sum_dgamma,
+                              float inv_count, const float* local_dbeta, float* dx, int64_t ld_dx, float* dx_colsum, float* ws,
+                              size_t ws_floats, void* stream);
 
 /* Merge the per-shard statistics of a sharded batch: stats [world, 2C+1] = (mean[C] | biased var[C] | rows) per shard
  * (all-gathered over RCCL), combined in shard order with the pairwise update of Chan et al. (identical on every rank);
  * shards with 0 rows are skipped.  Outputs mean [C], biased var [C], total [1] (rows of all shards). */
 int egnn_bn_merge_shards_f32(const float* stats, int world, int64_t C, float* mean, float* var, float* total, void* stream);
-int egnn_bn_act_bwd_reduce_f32(const float* x, int64_t ld, const float* dy, int64_t ld_dy, int64_t n, int64_t C,
-                               const float* mean, const float* var, float eps, const float* gamma, const float* beta, int relu,
-                               float p, uint64_t seed, const uint64_t* seed_dev, float* dgamma, float* dbeta, float* ws,
-                               size_t ws_floats, void* stream);
-int egnn_bn_act_bwd_apply_f32(const float* x, int64_t ld, const float* dy, int64_t ld_dy, int64_t n, int64_t C,
-                              const float* mean, const float* var, float eps, const float* gamma, const float* beta, int relu,
-                              float p, uint64_t seed, const uint64_t* seed_dev, const float* sum_dbeta, const float* sum_dgamma,
-                              float inv_count, float* dx, int64_t ld_dx, void* stream);
-/* The apply half that also returns the column sums of dx (dx_colsum [C]: the bias gradient of the layer in front of the BatchNorm);
- * ws: egnn_bn_ws_floats(C) floats. */
-int egnn_bn_act_bwd_apply_colsum_f32(const float* x, int64_t ld, const float* dy, int64_t ld_dy, int64_t n, int64_t C,
-                                     const float* mean, const float* var, float eps, const float* gamma, const float* beta, int relu,
-                                     float p, uint64_t seed, const uint64_t* seed_dev, const float* sum_dbeta, const float* sum_dgamma,
-                                     float inv_count, float* dx, int64_t ld_dx, float* dx_colsum, float* ws, size_t ws_floats, void* stream);
 
-/* egnn_bn_act_bwd_f32 that also leaves dx_colsum[c] = sum over rows of dx[:,c] (nullable): the gradient of a bias added in
- * front of the BatchNorm (GCNConv / nn.Linear bias, /root/reference/arxiv_pyg/gnn.py:47-48,296-306), formed while dx is
- * written instead of by a second pass over it (ATen: gy.sum(0)).  Same workspace. */
-int egnn_bn_act_bwd_colsum_f32(const float* x, int64_t ld, const float* dy, int64_t ld_dy, int64_t n, int64_t C, const float* mean,
-                               const float* var, float eps, const float* gamma, const float* beta, int relu, float p, uint64_t seed,
-                               const uint64_t* seed_dev, int batch_stats, float* dgamma, float* dbeta, float* dx, int64_t ld_dx,
-                               float* dx_colsum, float* ws, size_t ws_floats, void* stream);
-
-/* The fused BatchNorm + activation when only the OUTPUT ROWS `pick` (n_pick unique ids into the n rows of x) are read afterwards: the
- * projection heads feeding the sampled criteria (/root/reference/arxiv_pyg/gnn.py:296-306 -> criterion.py:62-65,134-137: the
- * statistics span all train rows, the criterion keeps max_samples of the output rows).
- *   fwd: y [n_pick, C], y[i] = act(bn(x[pick[i]]))  (mean / var: the statistics of ALL n rows, egnn_bn_stats_f32)
- *   bwd: dy [n_pick, C] -> dgamma, dbeta (sums over the picked rows: every other output row has no gradient), dx [n, C] (all rows:
- *        the mean / variance terms reach every row), dx_colsum nullable as in egnn_bn_act_bwd_colsum_f32.  Same arithmetic as
- *        scattering dy into a zero [n, C] gradient and calling egnn_bn_act_bwd_colsum_f32, without the zero rows. */
-int egnn_bn_act_rows_fwd_f32(const float* x, int64_t ld, int64_t n, int64_t C, const int64_t* pick, int64_t n_pick, const float* mean,
-                             const float* var, float eps, const float* gamma, const float* beta, int relu, float p, uint64_t seed,
-                             const uint64_t* seed_dev, float* y, int64_t ldy, void* stream);
-int egnn_bn_act_rows_bwd_f32(const float* x, int64_t ld, int64_t n, int64_t C, const int64_t* pick, int64_t n_pick, const float* dy,
-                             int64_t ld_dy, const float* mean, const float* var, float eps, const float* gamma, const float* beta,
-                             int relu, float p, uint64_t seed, const uint64_t* seed_dev, int batch_stats, float* dgamma, float* dbeta,
-                             float* dx, int64_t ld_dx, float* dx_colsum, float* ws, size_t ws_floats, void* stream);
-
-/* The two halves of egnn_bn_act_rows_bwd_f32 (which is their composition): on node-range shards the projection heads' BatchNorm has
- * all-rank statistics (/root/reference/arxiv_pyg/gnn.py:296-306 on shards: dist.SyncBatchNorm1d), so [sum d | sum d xhat] is all-reduced
- * between them.
- *   reduce: dgamma = sum d xhat, dbeta = sum d over the picked rows of THIS tensor (same workspace as egnn_bn_ws_floats).
- *   apply:  dx [n, C] from the sums the mean / variance terms use (sum_dbeta / sum_dgamma with inv_count = 1 / rows they span; the
- *           all-rank sums already divided by the row total go with inv_count = 1), n_pick >= 0; dx_colsum nullable -- it needs
- *           local_dbeta, this tensor's own sum d, because the picked rows' own term is local. */
-int egnn_bn_act_rows_bwd_reduce_f32(const float* x, int64_t ld, int64_t n, int64_t C, const int64_t* pick, int64_t n_pick, const float* dy,
-                                    int64_t ld_dy, const float* mean, const float* var, float eps, const float* gamma, const float* beta,
-                                    int relu, float p, uint64_t seed, const uint64_t* seed_dev, float* dgamma, float* dbeta, float* ws,
-                                    size_t ws_floats, void* stream);
-int egnn_bn_act_rows_bwd_apply_f32(const float* x, int64_t ld, int64_t n, int64_t C, const int64_t* pick, int64_t n_pick, const float* dy,
-                                   int64_t ld_dy, const float* mean, const float* var, float eps, const float* gamma, const float* beta,
-                                   int relu, float p, uint64_t seed, const uint64_t* seed_dev, const float* sum_dbeta,
-                                   const float* sum_dgamma, float inv_count, const float* local_dbeta, float* dx, int64_t ld_dx,
-                                   float* dx_colsum, float* ws, size_t ws_floats, void* stream);
-
-/* Backward of  h = act(bn(x)) [M, C]  followed by the narrow Linear  h W  (W [C, Ks] for w_kmajor = 0, [Ks, C] rows for 1 -- the same
- * flag as egnn_bn_act_linear_fwd_f32; Ks <= 64, C % 64 == 0)
- * in one pass over the [M, C] tensors -- the last hidden layer of the students (/root/reference/arxiv_pyg/gnn.py:47-52 under loss.backward()):
- *   dh = alpha G W^T (+ addend, nullable dense [M, C]) (+ add_rows[add_inv[row]] where add_inv[row] >= 0: the row-compact input gradient of
- *   the projection head, gnn.py:150; add_inv int32 [M], -1 = no row), d = dh * gate(x) never stored as dh; dgamma / dbeta / dx / dx_colsum as
- *   egnn_bn_act_bwd_colsum_f32 would return them for dy = dh.  ws: egnn_skinny_dx_bn_ws_floats(M, C) floats. */
-/* Forward of the same pair in one pass over x: h = act(bn(x)) [n, C] is stored AND multiplied by the narrow W ([C, Ks] for w_kmajor = 0 /
- * [Ks, C] rows for 1) while its 16-byte pieces are in registers: xw = h W [n, Ks].  h is bit-identical to egnn_bn_act_fwd_f32.
- * EGNN_EALIGN when the shape is not taken (Ks > 64, C % 16 != 0, C > 1024): the caller then makes the two calls. */
-int egnn_bn_act_linear_fwd_f32(const float* x, int64_t ld, int64_t n, int64_t C, const float* mean, const float* var, float eps,
-                               const float* gamma, const float* beta, int relu, float p, uint64_t seed, const uint64_t* seed_dev,
-                               const float* W, int64_t ldw, int w_kmajor, int64_t Ks, float* h, int64_t ldh, float* xw, int64_t ld_xw,
-                               void* stream);
+/* h = act(bn(x)) [M, C] followed by the narrow Linear  h W  (W [C, Ks] for w_kmajor = 0, [Ks, C] rows for 1; Ks <= 64): the last
+ * hidden layer of the students (/root/reference/arxiv_pyg/gnn.py:47-52).  bn->pick must be NULL; M = bn->n, C = bn->C.
+ * Forward in one pass over x: h is stored AND multiplied by W while its 16-byte pieces are in registers: xw = h W [M, Ks].  h is
+ * bit-identical to egnn_bn_act_fwd_f32.  EGNN_EALIGN when the shape is not taken (C != 256, M * ld >= 2^31): the caller then makes
+ * the two calls. */
+int egnn_bn_act_linear_fwd_f32(const egnn_bn_act_t* bn, const float* W, int64_t ldw, int w_kmajor, int64_t Ks, float* h, int64_t ldh,
+                               float* xw, int64_t ld_xw, void* stream);
+/* Backward in one pass over the [M, C] tensors (loss.backward()), in two halves so that node-range shards can all-reduce the column
+ * sums between them (SyncBN semantics); C % 64 == 0:
+ *   reduce: dh = alpha G W^T (+ addend, nullable dense [M, C]) (+ add_rows[add_inv[row]] where add_inv[row] >= 0: the row-compact input
+ *           gradient of the projection head, gnn.py:150; add_inv int32 [M], -1 = no row); d = dh * gate(x) is left in dx (dh is never
+ *           stored) and THIS shard's (sum d, sum d xhat) in dbeta / dgamma.  ws: egnn_skinny_dx_bn_ws_floats(M, C) floats.
+ *   apply:  turns the stored d into dx = gamma rstd (d - (sum_dbeta + xhat sum_dgamma) inv_count) in place (dx_colsum nullable:
+ *           column sums of dx, ws of egnn_bn_ws_floats(C) floats then).  On one GPU: the local sums and inv_count = 1 / M. */
 size_t egnn_skinny_dx_bn_ws_floats(int64_t M, int64_t C);
-int egnn_skinny_dx_bn_bwd_f32(const float* G, int64_t ldg, const float* W, int64_t ldw, int w_kmajor, int64_t M, int64_t C, int64_t Ks,
-                              float alpha, const float* addend, int64_t ld_addend, const float* add_rows, int64_t ld_add_rows,
-                              const int32_t* add_inv, const float* x, int64_t ldx, const float* mean, const float* var, float eps,
-                              const float* gamma, const float* beta, int relu, float p, uint64_t seed, const uint64_t* seed_dev,
-                              int batch_stats, float* dgamma, float* dbeta, float* dx, int64_t ld_dx, float* dx_colsum, float* ws,
-                              size_t ws_floats, void* stream);
-/* The same backward in its two halves, for BatchNorm statistics that span several node-range shards (SyncBN semantics):
- * `reduce` leaves d = dh * gate in dx and THIS shard's (sum d, sum d xhat) in dbeta / dgamma; the caller all-reduces them; `apply` then
- * turns the stored d into dx = gamma rstd (d - (sum_dbeta + xhat sum_dgamma) inv_count) in place (dx_colsum nullable: column sums of dx,
- * ws of egnn_bn_ws_floats(C) floats then).  egnn_skinny_dx_bn_bwd_f32 = reduce + apply with the local sums and inv_count = 1 / M. */
-int egnn_skinny_dx_bn_bwd_reduce_f32(const float* G, int64_t ldg, const float* W, int64_t ldw, int w_kmajor, int64_t M, int64_t C,
-                                     int64_t Ks, float alpha, const float* addend, int64_t ld_addend, const float* add_rows,
-                                     int64_t ld_add_rows, const int32_t* add_inv, const float* x, int64_t ldx, const float* mean,
-                                     const float* var, float eps, const float* gamma, const float* beta, int relu, float p, uint64_t seed,
-                                     const uint64_t* seed_dev, float* dgamma, float* dbeta, float* dx, int64_t ld_dx, float* ws,
-                                     size_t ws_floats, void* stream);
-int egnn_bn_bwd_apply_stored_f32(const float* x, int64_t ldx, int64_t M, int64_t C, const float* mean, const float* var, float eps,
-                                 const float* gamma, const float* beta, int relu, float p, uint64_t seed, const uint64_t* seed_dev,
-                                 const float* sum_dbeta, const float* sum_dgamma, float inv_count, float* dx, int64_t ld_dx,
-                                 float* dx_colsum, float* ws, size_t ws_floats, void* stream);
+int egnn_skinny_dx_bn_bwd_reduce_f32(const float* G, int64_t ldg, const float* W, int64_t ldw, int w_kmajor, int64_t Ks, float alpha,
+                                     const float* addend, int64_t ld_addend, const float* add_rows, int64_t ld_add_rows,
+                                     const int32_t* add_inv, const egnn_bn_act_t* bn, float* dgamma, float* dbeta, float* dx,
+                                     int64_t ld_dx, float* ws, size_t ws_floats, void* stream);
+int egnn_bn_bwd_apply_stored_f32(const egnn_bn_act_t* bn, const float* sum_dbeta, const float* sum_dgamma, float inv_count, float* dx,
+                                 int64_t ld_dx, float* dx_colsum, float* ws, size_t ws_floats, void* stream);
 
 /* nn.BatchNorm1d's training-step state update in one launch (torch/nn/modules/batchnorm.py: num_batches_tracked += 1,
  * running = (1 - m) running + m stat with the unbiased variance n/(n-1) var):  mean / var [C] = this batch's statistics,

@@ -23,14 +23,14 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(egnn_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_of_abi_7():
     syms = declared_symbols()
     assert len(syms) >= 30
     lib = ctypes.CDLL(E._lib.LIB_PATH)
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/egnn_hip.h but not exported"
     assert set(syms) == set(E._lib.SIGNATURES), "ctypes table and header disagree"
-    assert E._lib.load().egnn_abi_version() == 6
+    assert E._lib.load().egnn_abi_version() == 7
     assert "gfx950" in E._lib.build_info()
     assert E._lib.load().egnn_error_string(-3) == b"workspace too small"
 
@@ -148,7 +148,7 @@ def test_conv_parameter_layouts_match_pyg_1_7():
     assert sorted(PM.make_projection(256, 128).state_dict())[:2] == ["0.bias", "0.weight"]
 
 
-def test_c_abi_argument_errors_are_reported_before_any_launch():
+def test_c_abi_and_bn_descriptor_argument_errors_are_reported_before_any_launch():
     """Every entry point validates its arguments on the host and returns a negative EGNN_E* code without enqueueing
     anything (include/egnn_hip.h conventions) -- callable without a GPU."""
     lib = _lib.load()
@@ -174,9 +174,18 @@ def test_c_abi_argument_errors_are_reported_before_any_launch():
     assert lib.egnn_nce_bwd_f32(p, p, 4, 4, 4, 0.1, 1, p, p, None, p, p, p, 1, None) < 0
     assert lib.egnn_nce_bwd_ws_floats(0, 4, 4) == 0 and lib.egnn_nce_bwd_ws_floats(128, 128, 16) >= 128 * 16
     assert lib.egnn_nce_saves_exp(0.075, 1) == 1 and lib.egnn_nce_saves_exp(0.075, 0) == 0 and lib.egnn_nce_saves_exp(0.01, 1) == 0
-    # BatchNorm halves: null pointers
-    assert lib.egnn_bn_act_bwd_reduce_f32(None, 4, p, 4, 4, 4, p, p, 1e-5, p, p, 1, 0.0, 0, None, p, p, p, 1 << 20, None) < 0
-    assert lib.egnn_bn_act_bwd_apply_f32(p, 4, p, 4, 4, 4, p, p, 1e-5, p, p, 1, 0.0, 0, None, None, p, 1.0, p, 4, None) < 0
+    # BatchNorm halves: null pointers (x in the descriptor, sum_dbeta), and no descriptor at all
+    bn = _lib.BnAct(p, 4, 4, 4, p, p, 1e-5, p, p, 1, 0.0, 0, None, None, 0)
+    no_x = _lib.BnAct(None, 4, 4, 4, p, p, 1e-5, p, p, 1, 0.0, 0, None, None, 0)
+    assert lib.egnn_bn_act_bwd_reduce_f32(ctypes.byref(no_x), p, 4, p, p, p, 1 << 20, None) < 0
+    assert lib.egnn_bn_act_bwd_apply_f32(ctypes.byref(bn), p, 4, None, p, 1.0, None, p, 4, None, None, 0, None) < 0
+    assert lib.egnn_bn_act_bwd_reduce_f32(None, p, 4, p, p, p, 1 << 20, None) == EINVAL
+    assert lib.egnn_bn_act_bwd_apply_f32(None, p, 4, p, p, 1.0, None, p, 4, None, None, 0, None) == EINVAL
+    assert lib.egnn_bn_act_fwd_f32(None, p, 4, None) == EINVAL
+    assert lib.egnn_bn_act_bwd_f32(None, p, 4, 1, p, p, p, 4, None, p, 1 << 20, None) == EINVAL
+    assert lib.egnn_bn_act_linear_fwd_f32(None, p, 4, 0, 4, p, 4, p, 4, None) == EINVAL
+    assert lib.egnn_skinny_dx_bn_bwd_reduce_f32(p, 4, p, 4, 0, 4, 1.0, None, 0, None, 0, None, None, p, p, p, 4, p, 1 << 20, None) == EINVAL
+    assert lib.egnn_bn_bwd_apply_stored_f32(None, p, p, 1.0, p, 4, None, None, 0, None) == EINVAL
 
 
 def test_segment_plan_covers_every_entry_exactly_once():
@@ -482,6 +491,32 @@ def test_ctypes_table_matches_the_header_argument_by_argument():
         else:
             assert restype is C.c_char_p
     assert seen == set(_lib.SIGNATURES)
+
+
+def test_ctypes_bn_descriptor_matches_the_header_field_by_field():
+    """egnn_bn_act_t of include/egnn_hip.h parsed and compared with efficient-gnns_amd/_lib.py::BnAct: same fields in the same order and
+    of the same kind (pointer / int64 / int / float / uint64) -- a layout mismatch would not fail at load time either, the kernels would
+    read shifted operands."""
+    import ctypes as C
+    from efficient_gnns_amd import _lib
+    src = open(os.path.join(ROOT, "include", "egnn_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    body = re.search(r"typedef\s+struct\s+egnn_bn_act\s*\{([^}]*)\}\s*egnn_bn_act_t\s*;", src).group(1)
+
+    def kind(t):
+        t = t.replace("const", "").strip()
+        return "p" if t.endswith("*") else {"int64_t": "i64", "int": "i32", "float": "f32", "uint64_t": "u64"}[t]
+    want = [(m.group(2), kind(m.group(1))) for m in (re.match(r"(.*?)(\w+)$", d.strip(), flags=re.S) for d in body.split(";") if d.strip())]
+    assert len(want) == 15
+    kinds = {C.c_void_p: "p", C.c_int64: "i64", C.c_int: "i32", C.c_float: "f32", C.c_uint64: "u64"}
+    got = [(name, kinds[t]) for name, t in _lib.BnAct._fields_]
+    assert got == want, f"egnn_bn_act_t: ctypes {got} vs header {want}"
+    # every entry point that takes the descriptor binds it as a pointer argument
+    for ret, name, args in re.findall(r"\b(int64_t|size_t|int)\s+(egnn_\w+)\s*\(([^;{]*)\)\s*;", src):
+        for i, a in enumerate(args.split(",")):
+            if "egnn_bn_act_t" in a:
+                assert re.fullmatch(r"\s*const\s+egnn_bn_act_t\s*\*\s*\w+\s*", a), f"{name}: {a}"
+                assert _lib.SIGNATURES[name][1][i] is C.c_void_p, name
 
 
 def test_student_layer_form_table():

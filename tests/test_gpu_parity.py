@@ -4,6 +4,7 @@ product package, against the CPU oracle and the golden vectors.
 Bars: integer / index results bit-exact; fp32 layer outputs rtol 1e-5 with
 atol = 1e-5 * max|ref|; scalar losses rtol 1e-5 (NCE 2e-5); gradients rtol 1e-4.
 """
+import ctypes
 import os
 
 import numpy as np
@@ -1792,11 +1793,11 @@ def test_plain_c_host_program_drives_the_c_abi(tmp_path):
 
 
 @pytest.mark.gpu
-def test_sharded_batchnorm_pieces_on_simulated_shards():
+def test_sharded_batchnorm_descriptor_pieces_on_simulated_shards():
     """The N > 1 BatchNorm math without N GPUs: rows split into 3 uneven shards (one of them empty), per-shard
     egnn_bn_stats_f32 -> egnn_bn_merge_shards_f32 must equal the full-batch statistics, and per-shard
     egnn_bn_act_bwd_reduce_f32 summed over shards (what the all-reduce does) -> egnn_bn_act_bwd_apply_f32 with 1/N_total
-    must equal the single-GPU backward on the whole batch."""
+    must equal the single-GPU backward (egnn_bn_act_bwd_f32) on the whole batch."""
     lib = _lib.load()
     g = torch.Generator().manual_seed(3)
     n, C = 5000, 64
@@ -1823,18 +1824,20 @@ def test_sharded_batchnorm_pieces_on_simulated_shards():
     close(var, x.double().var(0, unbiased=False), rtol=1e-5, atol_scale=1e-6)
     # backward: reference = the single-GPU entry point on the whole batch with the same statistics
     eps, relu, p, seed = 1e-5, 1, 0.0, 0
+
+    def desc(rows):   # egnn_bn_act_t over the rows `rows` of x, every row an output row
+        return ctypes.byref(_lib.BnAct(_lib.ptr(rows), C, rows.shape[0], C, _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta),
+                                       relu, p, seed, None, None, 0))
     dg_ref, db_ref, dx_ref = torch.empty(C, device=DEV), torch.empty(C, device=DEV), torch.empty_like(x)
-    _lib.check(lib.egnn_bn_act_bwd_f32(_lib.ptr(x), C, _lib.ptr(dy), C, n, C, _lib.ptr(mean), _lib.ptr(var), eps, _lib.ptr(gamma), _lib.ptr(beta),
-                                       relu, p, seed, None, 1, _lib.ptr(dg_ref), _lib.ptr(db_ref), _lib.ptr(dx_ref), C, _lib.ptr(ws), nws,
+    _lib.check(lib.egnn_bn_act_bwd_f32(desc(x), _lib.ptr(dy), C, 1, _lib.ptr(dg_ref), _lib.ptr(db_ref), _lib.ptr(dx_ref), C, None, _lib.ptr(ws), nws,
                                        _lib.stream()), "bwd")
     total = torch.zeros(2 * C, device=DEV)                           # [dbeta | dgamma] summed over the shards
     for w in range(world):
         xs, ds = x[cuts[w]:cuts[w + 1]], dy[cuts[w]:cuts[w + 1]]
         if xs.shape[0]:
             part = torch.empty(2 * C, device=DEV)
-            _lib.check(lib.egnn_bn_act_bwd_reduce_f32(_lib.ptr(xs), C, _lib.ptr(ds), C, xs.shape[0], C, _lib.ptr(mean), _lib.ptr(var), eps,
-                                                      _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, None, _lib.ptr(part[C:]), _lib.ptr(part),
-                                                      _lib.ptr(ws), nws, _lib.stream()), "reduce")
+            _lib.check(lib.egnn_bn_act_bwd_reduce_f32(desc(xs), _lib.ptr(ds), C, _lib.ptr(part[C:]), _lib.ptr(part), _lib.ptr(ws), nws,
+                                                      _lib.stream()), "reduce")
             total += part
     close(total[:C], db_ref, rtol=1e-4, atol_scale=1e-5)
     close(total[C:], dg_ref, rtol=1e-4, atol_scale=1e-5)
@@ -1842,9 +1845,8 @@ def test_sharded_batchnorm_pieces_on_simulated_shards():
     for w in range(world):
         xs, ds = x[cuts[w]:cuts[w + 1]], dy[cuts[w]:cuts[w + 1]]
         if xs.shape[0]:
-            _lib.check(lib.egnn_bn_act_bwd_apply_f32(_lib.ptr(xs), C, _lib.ptr(ds), C, xs.shape[0], C, _lib.ptr(mean), _lib.ptr(var), eps,
-                                                     _lib.ptr(gamma), _lib.ptr(beta), relu, p, seed, None, _lib.ptr(total), _lib.ptr(total[C:]),
-                                                     1.0 / n, _lib.ptr(dx[cuts[w]:cuts[w + 1]]), C, _lib.stream()), "apply")
+            _lib.check(lib.egnn_bn_act_bwd_apply_f32(desc(xs), _lib.ptr(ds), C, _lib.ptr(total), _lib.ptr(total[C:]), 1.0 / n, None,
+                                                     _lib.ptr(dx[cuts[w]:cuts[w + 1]]), C, None, None, 0, _lib.stream()), "apply")
     close(dx, dx_ref, rtol=1e-4, atol_scale=1e-5)
 
 

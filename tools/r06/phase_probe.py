@@ -31,10 +31,9 @@ print("tensor bytes", nbytes, "span", span, "base mod 2MiB", base % (2 << 20))
 for d in (0, 256, 1024, 4096, 16384, 65536, 262144, 1 << 20, nbytes - span + 0, nbytes - span + 4096):
     x = view(0); y = view(span + d); dy = view(2 * span + 2 * d); dx = view(3 * span + 3 * d)
     x.normal_(); dy.normal_()
-    fwd = t(lambda: _lib.check(lib.egnn_bn_act_fwd_f32(_lib.ptr(x), Cc, n, Cc, _lib.ptr(mean), _lib.ptr(var), 1e-5, _lib.ptr(g), _lib.ptr(b), 1, 0.5, 123, None,
-                                                        _lib.ptr(y), Cc, _lib.stream()), "fwd"))
-    bwd = t(lambda: _lib.check(lib.egnn_bn_act_bwd_colsum_f32(_lib.ptr(x), Cc, _lib.ptr(dy), Cc, n, Cc, _lib.ptr(mean), _lib.ptr(var), 1e-5, _lib.ptr(g), _lib.ptr(b),
-                                                               1, 0.5, 123, None, 1, _lib.ptr(dg), _lib.ptr(db), _lib.ptr(dx), Cc, _lib.ptr(cs), _lib.ptr(ws), nws,
-                                                               _lib.stream()), "bwd"))
+    bn = C.byref(_lib.BnAct(_lib.ptr(x), Cc, n, Cc, _lib.ptr(mean), _lib.ptr(var), 1e-5, _lib.ptr(g), _lib.ptr(b), 1, 0.5, 123, None, None, 0))
+    fwd = t(lambda: _lib.check(lib.egnn_bn_act_fwd_f32(bn, _lib.ptr(y), Cc, _lib.stream()), "fwd"))
+    bwd = t(lambda: _lib.check(lib.egnn_bn_act_bwd_f32(bn, _lib.ptr(dy), Cc, 1, _lib.ptr(dg), _lib.ptr(db), _lib.ptr(dx), Cc, _lib.ptr(cs), _lib.ptr(ws),
+                                                       nws, _lib.stream()), "bwd"))
     cp = t(lambda: y.copy_(x))
     print(f"distance between tensors = span + {d:8d} B : bn_act_fwd {fwd:7.1f} us   bwd(reduce+apply) {bwd:7.1f} us   copy {cp:7.1f} us", flush=True)
