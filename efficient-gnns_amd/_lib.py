@@ -25,6 +25,18 @@ class BnAct(C.Structure):
                 ("pick", _p), ("n_pick", _i64)]
 
 
+class GatLayer(C.Structure):
+    """egnn_gat_layer_t of include/egnn_hip.h, field for field: the operands of one DGL-style GAT layer (forward and backward)."""
+    _fields_ = [("rowptr", _p), ("col", _p),
+                ("colptr", _p), ("t_col", _p), ("perm", _p),
+                ("n", _i64), ("nnz", _i64), ("H", _i32), ("C", _i32),
+                ("xl", _p), ("ld_xl", _i64),
+                ("el", _p), ("er", _p),
+                ("attn_l", _p), ("attn_r", _p),
+                ("keep", _p), ("mult", _p), ("src_scale", _p), ("dst_scale", _p),
+                ("negative_slope", _f32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/egnn_hip.h declares
 SIGNATURES = {
     "egnn_abi_version": (_i32, []),
@@ -90,6 +102,9 @@ SIGNATURES = {
     "egnn_gat_aggregate_bwd_ws_floats": (_sz, [_i64, _i32, _i32]),
     "egnn_gat_aggregate_bwd_f32": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _p, _i64, _p, _p, _p, _i64, _i64, _i32, _i32, _p, _i64,
                                           _p, _p, _sz, _p]),
+    "egnn_gat_layer_fwd_f32": (_i32, [_p, _p, _p, _i64, _p]),
+    "egnn_gat_layer_bwd_ws_floats": (_sz, [_i64, _i32, _i32]),
+    "egnn_gat_layer_bwd_f32": (_i32, [_p, _p, _p, _i64, _p, _p, _p, _i64, _p, _p, _sz, _p]),
     "egnn_segment_softmax_fwd_f32": (_i32, [_p, _p, _i64, _p, _p]),
     "egnn_segment_softmax_bwd_f32": (_i32, [_p, _p, _p, _i64, _p, _p]),
     "egnn_segment_sum_f32": (_i32, [_p, _p, _i64, _p, _p]),

@@ -10,6 +10,15 @@
 // Three launches for all heads: the target-side kernel (one wavefront per target row), the source-side kernel over the transposed
 // structure (one wavefront per source row, no H permuted value copies, per-block partials of d_att_l / d_att_r in LDS) and a
 // fixed-order finalize.  No atomics: every sum has a fixed order, so two backward passes are bit-equal.
+//
+// The arxiv GAT teacher's layer (/root/reference/arxiv_dgl/models.py:95-236, trained by arxiv_dgl/gat.py:116-148) adds an edge subset
+// `keep` (edge_drop: the softmax runs over the kept entries, att = 0 elsewhere), a source scale r (out-degree^-1/2) and a target
+// scale q (in-degree^1/2), and has no a_dst term without attn_r:
+//   out[i,h,:] = q_i sum_e att[h,e] m[h,e] r_{col e} xl[col e,h,:]
+// gat_layer_fwd_kernel forms att and out for all heads in one launch (one wavefront per target row, xl read in place with row stride
+// H*C -- float2 loads for C = 250 --, r folded into the coefficient).  The two backward kernels take r and q as nullable arguments:
+// with go' = q_i go_i,  g_e = m_e r_{col e} <go'_i, xl[col e]>,  dxl[j] = r_j (sum att m go' + d_a_src[j] att_l) + d_a_dst[j] att_r,
+// d_att_l = sum_j r_j xl_j d_a_src[j]  (a_src comes from the scaled source features, a_dst from the unscaled ones).
 #include "common.h"
 
 namespace {
@@ -39,12 +48,14 @@ __global__ __launch_bounds__(256) void gat_attention_bwd_kernel(const int64_t* _
                                                                 const float* __restrict__ att, const float* __restrict__ mult,
                                                                 const float* __restrict__ xl, int64_t ld_xl, const float* __restrict__ go,
                                                                 int64_t ld_go, int64_t go_hs, float go_scale, int64_t n_rows, int64_t nnz,
-                                                                int H, int C, float slope, float* __restrict__ d_raw,
+                                                                int H, int C, float slope, const float* __restrict__ r,
+                                                                const float* __restrict__ q, float* __restrict__ d_raw,
                                                                 float* __restrict__ d_adst) {
   const int lane = egnn_lane();
   const int64_t row = (int64_t)blockIdx.x * 4 + egnn_wave_id();
   if (row >= n_rows) return;
   const int64_t start = rowptr[row], end = rowptr[row + 1];
+  const float qi = q != nullptr ? q[row] : 1.f;
   for (int h = 0; h < H; ++h) {
     const float* gor = go + row * ld_go + h * go_hs;
     const float* a_h = att + (int64_t)h * nnz;
@@ -62,14 +73,16 @@ __global__ __launch_bounds__(256) void gat_attention_bwd_kernel(const int64_t* _
       if (lane < cnt) {
         const int64_t e = base + lane;
         float g = mine * go_scale;
+        if (q != nullptr) g *= qi;
         if (mult != nullptr) g *= mult[(int64_t)h * nnz + e];
+        if (r != nullptr) g *= r[col[e]];
         acc = fmaf(a_h[e], g, acc);
         dr_h[e] = g;
       }
     }
     const float tot = egnn_wave_sum(acc);
     // pass 2: softmax and LeakyReLU backward (s recomputed exactly as the forward formed it), row sum -> d_a_dst
-    const float ad = adst[row * H + h];
+    const float ad = adst != nullptr ? adst[row * H + h] : 0.f;
     float dsum = 0.f;
     for (int64_t e = start + lane; e < end; e += 64) {
       const float ds = a_h[e] * (dr_h[e] - tot);
@@ -78,6 +91,7 @@ __global__ __launch_bounds__(256) void gat_attention_bwd_kernel(const int64_t* _
       dr_h[e] = d;
       dsum += d;
     }
+    if (d_adst == nullptr) continue;
     dsum = egnn_wave_sum(dsum);
     if (lane == 0) d_adst[row * H + h] = dsum;
   }
@@ -92,8 +106,9 @@ __global__ __launch_bounds__(256) void gat_aggregate_bwd_kernel(const int64_t* _
                                                                 const float* __restrict__ go, int64_t ld_go, int64_t go_hs, float go_scale,
                                                                 const float* __restrict__ xl, int64_t ld_xl, const float* __restrict__ att_l,
                                                                 const float* __restrict__ att_r, const float* __restrict__ d_adst,
-                                                                int64_t n_src, int64_t nnz, int H, int C, float* __restrict__ dxl,
-                                                                int64_t ld_dxl, float* __restrict__ partials) {
+                                                                int64_t n_src, int64_t nnz, int H, int C, const float* __restrict__ r_src,
+                                                                const float* __restrict__ q_dst, float* __restrict__ dxl, int64_t ld_dxl,
+                                                                float* __restrict__ partials) {
   extern __shared__ float s_acc[];   // [4 waves][2 H C] when partials != nullptr
   const int lane = egnn_lane();
   const int wave = egnn_wave_id();
@@ -104,6 +119,7 @@ __global__ __launch_bounds__(256) void gat_aggregate_bwd_kernel(const int64_t* _
   __syncthreads();
   for (int64_t j = (int64_t)blockIdx.x * 4 + wave; j < n_src; j += (int64_t)gridDim.x * 4) {
     const int64_t b = colptr[j], e_end = colptr[j + 1];
+    const float rj = r_src != nullptr ? r_src[j] : 1.f;
     for (int h = 0; h < H; ++h) {
       const int64_t hoff = (int64_t)h * nnz;
       float das = 0.f;
@@ -120,6 +136,7 @@ __global__ __launch_bounds__(256) void gat_aggregate_bwd_kernel(const int64_t* _
             t = t_col[base + lane];
             coef = att[hoff + p];
             if (mult != nullptr) coef *= mult[hoff + p];
+            if (q_dst != nullptr) coef *= q_dst[t];
             if (c0 == 0) das_part += d_raw[hoff + p];
           }
           for (int k = 0; k < cnt; ++k) {
@@ -147,11 +164,12 @@ __global__ __launch_bounds__(256) void gat_aggregate_bwd_kernel(const int64_t* _
           if (c >= C) continue;
           const int64_t hc = (int64_t)h * C + c;
           float v = fmaf(das, att_l[hc], acc[r] * go_scale);
+          if (r_src != nullptr) v *= rj;
           if (att_r != nullptr) v = fmaf(dad, att_r[hc], v);
           dxl[j * ld_dxl + hc] = v;
           if (partials != nullptr) {
             const float x = xl[j * ld_xl + hc];
-            my[hc] = fmaf(x, das, my[hc]);
+            my[hc] = fmaf(x, r_src != nullptr ? das * rj : das, my[hc]);
             my[HC + hc] = fmaf(x, dad, my[HC + hc]);
           }
         }
@@ -181,6 +199,162 @@ inline int gat_bwd_blocks(int64_t n_src) {
   return (int)(want < 1 ? 1 : (want < kGatBwdBlocks ? want : kGatBwdBlocks));
 }
 
+// VEC floats of one load / store: float4 (16-byte aligned head blocks), float2 (8-byte: C = 250) or float
+template <int VEC> struct GatVec;
+template <> struct GatVec<4> { using T = float4; };
+template <> struct GatVec<2> { using T = float2; };
+template <> struct GatVec<1> { using T = float; };
+
+template <int VEC>
+__device__ __forceinline__ void gat_vec_fma(float ck, const typename GatVec<VEC>::T& v, float* acc) {
+  if constexpr (VEC == 4) {
+    acc[0] = fmaf(ck, v.x, acc[0]); acc[1] = fmaf(ck, v.y, acc[1]); acc[2] = fmaf(ck, v.z, acc[2]); acc[3] = fmaf(ck, v.w, acc[3]);
+  } else if constexpr (VEC == 2) {
+    acc[0] = fmaf(ck, v.x, acc[0]); acc[1] = fmaf(ck, v.y, acc[1]);
+  } else {
+    acc[0] = fmaf(ck, v, acc[0]);
+  }
+}
+
+// The whole forward of one DGL-style GAT layer, one wavefront per target row, all heads in one launch: scores + LeakyReLU + softmax
+// over the KEPT entries of the row (att [H, nnz], exactly 0 at dropped entries; a row without a kept entry: zeros), then
+//   out[i,h,:] = q_i sum_e (att[h,e] mult[h,e] r_{col e}) xl[col e,h,:]
+// with xl gathered in place (row stride ld_xl, head block h*C: no padded or scaled copy).  Columns of a head in tiles of 256: a lane
+// owns R = 4 / VEC vectors of VEC floats.  Entries go 64 at a time (lane k forms the coefficient of entry base + k), the gathers of
+// four entries are issued together; an entry whose coefficient is 0 (dropped edge, dropped attention) is not gathered.
+template <int VEC>
+__global__ __launch_bounds__(256) void gat_layer_fwd_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
+                                                            const float* __restrict__ el, const float* __restrict__ er,
+                                                            const uint8_t* __restrict__ keep, const float* __restrict__ mult,
+                                                            const float* __restrict__ r_src, const float* __restrict__ q_dst,
+                                                            const float* __restrict__ xl, int64_t ld_xl, int64_t n_rows, int64_t nnz, int H,
+                                                            int C, float slope, float* __restrict__ att, float* __restrict__ out,
+                                                            int64_t ld_out) {
+  using V = typename GatVec<VEC>::T;
+  constexpr int R = 4 / VEC;
+  const int lane = egnn_lane();
+  const int64_t row = (int64_t)blockIdx.x * 4 + egnn_wave_id();
+  if (row >= n_rows) return;
+  const int64_t start = rowptr[row], end = rowptr[row + 1];
+  const float qi = q_dst != nullptr ? q_dst[row] : 1.f;
+  for (int h = 0; h < H; ++h) {
+    const float ad = er != nullptr ? er[row * H + h] : 0.f;
+    const int64_t hoff = (int64_t)h * nnz;
+    float m = -INFINITY;
+    for (int64_t e = start + lane; e < end; e += 64) {
+      if (keep != nullptr && keep[e] == 0) continue;
+      float s = el[col[e] * H + h] + ad;
+      s = s > 0.f ? s : s * slope;
+      m = fmaxf(m, s);
+    }
+    m = egnn_wave_max(m);
+    float z = 0.f;
+    for (int64_t e = start + lane; e < end; e += 64) {
+      if (keep != nullptr && keep[e] == 0) continue;
+      float s = el[col[e] * H + h] + ad;
+      s = s > 0.f ? s : s * slope;
+      z += expf(s - m);
+    }
+    z = egnn_wave_sum(z);   // >= 1 when the row has a kept entry (the maximum contributes exp(0)), 0 otherwise
+    for (int c0 = 0; c0 < C; c0 += 256) {
+      float acc[R][VEC];
+#pragma unroll
+      for (int t = 0; t < R; ++t)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[t][v] = 0.f;
+      for (int64_t base = start; base < end; base += 64) {
+        const int cnt = (int)(end - base < 64 ? end - base : 64);
+        int64_t cj = 0;
+        float coef = 0.f;
+        if (lane < cnt) {
+          const int64_t e = base + lane;
+          cj = col[e];
+          float a = 0.f;
+          if (keep == nullptr || keep[e] != 0) {
+            float s = el[cj * H + h] + ad;
+            s = s > 0.f ? s : s * slope;
+            a = expf(s - m) / z;
+          }
+          if (c0 == 0) att[hoff + e] = a;
+          coef = a;
+          if (mult != nullptr) coef *= mult[hoff + e];
+          if (r_src != nullptr) coef *= r_src[cj];
+        }
+        for (int k = 0; k < cnt; k += 4) {   // cnt <= 64: lanes k .. k + 3 exist; those at or past cnt hold coef = 0
+          float ck[4];
+          const float* xr[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            ck[u] = __shfl(coef, k + u);
+            xr[u] = xl + __shfl(cj, k + u) * ld_xl + (int64_t)h * C + c0;
+          }
+          V v[4][R];
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int t = 0; t < R; ++t) {
+              const int c = (lane + 64 * t) * VEC;
+              v[u][t] = V{};
+              if (ck[u] != 0.f && c0 + c < C) v[u][t] = *reinterpret_cast<const V*>(xr[u] + c);
+            }
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int t = 0; t < R; ++t) gat_vec_fma<VEC>(ck[u], v[u][t], acc[t]);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < R; ++t) {
+        const int c = c0 + (lane + 64 * t) * VEC;
+        if (c >= C) continue;
+        float* o = out + row * ld_out + (int64_t)h * C + c;
+        if constexpr (VEC == 4) *reinterpret_cast<float4*>(o) = make_float4(qi * acc[t][0], qi * acc[t][1], qi * acc[t][2], qi * acc[t][3]);
+        else if constexpr (VEC == 2) *reinterpret_cast<float2*>(o) = make_float2(qi * acc[t][0], qi * acc[t][1]);
+        else *o = qi * acc[t][0];
+      }
+    }
+  }
+}
+
+inline bool gat_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
+int gat_launch_attention_bwd(const int64_t* rowptr, const int64_t* col, const float* alpha_src, const float* alpha_dst, const float* att,
+                             const float* mult, const float* xl, int64_t ld_xl, const float* go, int64_t ld_go, int64_t go_head_stride,
+                             float go_scale, int64_t n_rows, int64_t nnz, int H, int C, float negative_slope, const float* r, const float* q,
+                             float* d_raw, float* d_alpha_dst, hipStream_t st) {
+  const int64_t blocks = (n_rows + 3) / 4;
+  if (blocks > 0x7fffffffLL) return EGNN_EINVAL;
+  const bool vec4 = C % 4 == 0 && ld_xl % 4 == 0 && ld_go % 4 == 0 && go_head_stride % 4 == 0 && egnn_aligned16(xl) && egnn_aligned16(go);
+  if (vec4)
+    hipLaunchKernelGGL(gat_attention_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, rowptr, col, alpha_src, alpha_dst, att,
+                       mult, xl, ld_xl, go, ld_go, go_head_stride, go_scale, n_rows, nnz, H, C, negative_slope, r, q, d_raw, d_alpha_dst);
+  else
+    hipLaunchKernelGGL(gat_attention_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, rowptr, col, alpha_src, alpha_dst, att,
+                       mult, xl, ld_xl, go, ld_go, go_head_stride, go_scale, n_rows, nnz, H, C, negative_slope, r, q, d_raw, d_alpha_dst);
+  return egnn_launch_status();
+}
+
+int gat_launch_aggregate_bwd(const int64_t* colptr, const int64_t* t_col, const int64_t* perm, const float* att, const float* mult,
+                             const float* d_raw, const float* go, int64_t ld_go, int64_t go_head_stride, float go_scale, const float* xl,
+                             int64_t ld_xl, const float* att_l, const float* att_r, const float* d_alpha_dst, int64_t n_src, int64_t nnz,
+                             int H, int C, const float* r, const float* q, float* dxl, int64_t ld_dxl, float* d_att, float* ws,
+                             hipStream_t st) {
+  const int64_t HC = (int64_t)H * C;
+  const int nb = gat_bwd_blocks(n_src);
+  const bool vec4 = C % 4 == 0 && ld_go % 4 == 0 && go_head_stride % 4 == 0 && egnn_aligned16(go);
+  const size_t lds = d_att != nullptr ? (size_t)4 * 2 * HC * sizeof(float) : 0;
+  float* partials = d_att != nullptr ? ws : nullptr;
+  if (vec4)
+    hipLaunchKernelGGL(gat_aggregate_bwd_kernel<true>, dim3(nb), dim3(256), lds, st, colptr, t_col, perm, att, mult, d_raw, go, ld_go,
+                       go_head_stride, go_scale, xl, ld_xl, att_l, att_r, d_alpha_dst, n_src, nnz, H, C, r, q, dxl, ld_dxl, partials);
+  else
+    hipLaunchKernelGGL(gat_aggregate_bwd_kernel<false>, dim3(nb), dim3(256), lds, st, colptr, t_col, perm, att, mult, d_raw, go, ld_go,
+                       go_head_stride, go_scale, xl, ld_xl, att_l, att_r, d_alpha_dst, n_src, nnz, H, C, r, q, dxl, ld_dxl, partials);
+  if (d_att != nullptr)
+    hipLaunchKernelGGL(gat_partials_final_kernel, dim3((unsigned)((2 * HC + 3) / 4)), dim3(256), 0, st, ws, nb, 2 * HC, d_att);
+  return egnn_launch_status();
+}
+
 }  // namespace
 
 extern "C" int egnn_gat_attention_bwd_f32(const int64_t* rowptr, const int64_t* col, const float* alpha_src, const float* alpha_dst,
@@ -192,17 +366,8 @@ extern "C" int egnn_gat_attention_bwd_f32(const int64_t* rowptr, const int64_t* 
   if (n_rows == 0) return EGNN_OK;
   EGNN_CHECK_ARG(rowptr && d_alpha_dst);
   EGNN_CHECK_ARG(nnz == 0 || (col && alpha_src && alpha_dst && att && xl && go && d_raw));
-  const int64_t blocks = (n_rows + 3) / 4;
-  if (blocks > 0x7fffffffLL) return EGNN_EINVAL;
-  const bool vec4 = C % 4 == 0 && ld_xl % 4 == 0 && ld_go % 4 == 0 && go_head_stride % 4 == 0 && egnn_aligned16(xl) && egnn_aligned16(go);
-  hipStream_t st = (hipStream_t)stream;
-  if (vec4)
-    hipLaunchKernelGGL(gat_attention_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, rowptr, col, alpha_src, alpha_dst, att,
-                       mult, xl, ld_xl, go, ld_go, go_head_stride, go_scale, n_rows, nnz, H, C, negative_slope, d_raw, d_alpha_dst);
-  else
-    hipLaunchKernelGGL(gat_attention_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, rowptr, col, alpha_src, alpha_dst, att,
-                       mult, xl, ld_xl, go, ld_go, go_head_stride, go_scale, n_rows, nnz, H, C, negative_slope, d_raw, d_alpha_dst);
-  return egnn_launch_status();
+  return gat_launch_attention_bwd(rowptr, col, alpha_src, alpha_dst, att, mult, xl, ld_xl, go, ld_go, go_head_stride, go_scale, n_rows, nnz,
+                                  H, C, negative_slope, nullptr, nullptr, d_raw, d_alpha_dst, (hipStream_t)stream);
 }
 
 extern "C" size_t egnn_gat_aggregate_bwd_ws_floats(int64_t n_src, int H, int C) {
@@ -223,18 +388,60 @@ extern "C" int egnn_gat_aggregate_bwd_f32(const int64_t* colptr, const int64_t* 
   if (n_src == 0) return EGNN_OK;
   EGNN_CHECK_ARG(colptr && att_l && dxl);
   EGNN_CHECK_ARG(nnz == 0 || (t_col && perm && att && d_raw && go));
-  const int nb = gat_bwd_blocks(n_src);
-  const bool vec4 = C % 4 == 0 && ld_go % 4 == 0 && go_head_stride % 4 == 0 && egnn_aligned16(go);
-  const size_t lds = d_att != nullptr ? (size_t)4 * 2 * HC * sizeof(float) : 0;
-  float* partials = d_att != nullptr ? ws : nullptr;
+  return gat_launch_aggregate_bwd(colptr, t_col, perm, att, mult, d_raw, go, ld_go, go_head_stride, go_scale, xl, ld_xl, att_l, att_r,
+                                  d_alpha_dst, n_src, nnz, H, C, nullptr, nullptr, dxl, ld_dxl, d_att, ws, (hipStream_t)stream);
+}
+
+// ---- one DGL-style GAT layer as a descriptor (include/egnn_hip.h: egnn_gat_layer_t) ----
+static int gat_layer_check(const egnn_gat_layer_t* L) {
+  EGNN_CHECK_ARG(L != nullptr);
+  EGNN_CHECK_ARG(L->n >= 0 && L->nnz >= 0 && L->H > 0 && L->H <= 64 && L->C > 0 && L->ld_xl >= (int64_t)L->H * L->C);
+  if (L->n == 0) return EGNN_OK;
+  EGNN_CHECK_ARG(L->rowptr && L->xl && L->el);
+  EGNN_CHECK_ARG(L->nnz == 0 || L->col);
+  return EGNN_OK;
+}
+
+extern "C" int egnn_gat_layer_fwd_f32(const egnn_gat_layer_t* L, float* att, float* out, int64_t ld_out, void* stream) {
+  const int rc = gat_layer_check(L);
+  if (rc != EGNN_OK) return rc;
+  EGNN_CHECK_ARG(ld_out >= (int64_t)L->H * L->C);
+  if (L->n == 0) return EGNN_OK;
+  EGNN_CHECK_ARG(out && (L->nnz == 0 || att));
+  const int64_t blocks = (L->n + 3) / 4;
+  if (blocks > 0x7fffffffLL) return EGNN_EINVAL;
+  const int C = L->C;
+  const auto fits = [&](int v) {
+    return C % v == 0 && L->ld_xl % v == 0 && ld_out % v == 0 && gat_aligned(L->xl, 4u * v) && gat_aligned(out, 4u * v);
+  };
   hipStream_t st = (hipStream_t)stream;
-  if (vec4)
-    hipLaunchKernelGGL(gat_aggregate_bwd_kernel<true>, dim3(nb), dim3(256), lds, st, colptr, t_col, perm, att, mult, d_raw, go, ld_go,
-                       go_head_stride, go_scale, xl, ld_xl, att_l, att_r, d_alpha_dst, n_src, nnz, H, C, dxl, ld_dxl, partials);
-  else
-    hipLaunchKernelGGL(gat_aggregate_bwd_kernel<false>, dim3(nb), dim3(256), lds, st, colptr, t_col, perm, att, mult, d_raw, go, ld_go,
-                       go_head_stride, go_scale, xl, ld_xl, att_l, att_r, d_alpha_dst, n_src, nnz, H, C, dxl, ld_dxl, partials);
-  if (d_att != nullptr)
-    hipLaunchKernelGGL(gat_partials_final_kernel, dim3((unsigned)((2 * HC + 3) / 4)), dim3(256), 0, st, ws, nb, 2 * HC, d_att);
+#define EGNN_GAT_LAYER_FWD(V)                                                                                                        \
+  hipLaunchKernelGGL(gat_layer_fwd_kernel<V>, dim3((unsigned)blocks), dim3(256), 0, st, L->rowptr, L->col, L->el, L->er, L->keep,    \
+                     L->mult, L->src_scale, L->dst_scale, L->xl, L->ld_xl, L->n, L->nnz, L->H, L->C, L->negative_slope, att, out, ld_out)
+  if (fits(4)) EGNN_GAT_LAYER_FWD(4);
+  else if (fits(2)) EGNN_GAT_LAYER_FWD(2);
+  else EGNN_GAT_LAYER_FWD(1);
+#undef EGNN_GAT_LAYER_FWD
   return egnn_launch_status();
+}
+
+extern "C" size_t egnn_gat_layer_bwd_ws_floats(int64_t n, int H, int C) { return egnn_gat_aggregate_bwd_ws_floats(n, H, C); }
+
+extern "C" int egnn_gat_layer_bwd_f32(const egnn_gat_layer_t* L, const float* att, const float* go, int64_t ld_go, float* d_raw, float* d_er,
+                                      float* dxl, int64_t ld_dxl, float* d_attn, float* ws, size_t ws_floats, void* stream) {
+  const int rc = gat_layer_check(L);
+  if (rc != EGNN_OK) return rc;
+  const int64_t HC = (int64_t)L->H * L->C;
+  EGNN_CHECK_ARG(ld_go >= HC && ld_dxl >= HC);
+  EGNN_CHECK_ARG((L->attn_r == nullptr) == (L->er == nullptr) && (L->er == nullptr) == (d_er == nullptr));
+  if (d_attn != nullptr) EGNN_CHECK_ARG(HC <= kGatMaxHC && ws && ws_floats >= egnn_gat_layer_bwd_ws_floats(L->n, L->H, L->C));
+  if (L->n == 0) return EGNN_OK;
+  EGNN_CHECK_ARG(L->colptr && L->attn_l && dxl);
+  EGNN_CHECK_ARG(L->nnz == 0 || (L->t_col && L->perm && att && go && d_raw));
+  hipStream_t st = (hipStream_t)stream;
+  const int rc2 = gat_launch_attention_bwd(L->rowptr, L->col, L->el, L->er, att, L->mult, L->xl, L->ld_xl, go, ld_go, L->C, 1.f, L->n, L->nnz,
+                                           L->H, L->C, L->negative_slope, L->src_scale, L->dst_scale, d_raw, d_er, st);
+  if (rc2 != EGNN_OK) return rc2;
+  return gat_launch_aggregate_bwd(L->colptr, L->t_col, L->perm, att, L->mult, d_raw, go, ld_go, L->C, 1.f, L->xl, L->ld_xl, L->attn_l,
+                                  L->attn_r, d_er, L->n, L->nnz, L->H, L->C, L->src_scale, L->dst_scale, dxl, ld_dxl, d_attn, ws, st);
 }

@@ -8,6 +8,7 @@ signatures, ``convs`` / ``bns`` state_dict keys, ``.out_feat`` side channel); ``
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 
 import torch
@@ -570,7 +571,7 @@ class ElementWiseLinear(nn.Module):
 
 class ArxivGAT(nn.Module):
     """The arxiv GAT teacher (/root/reference/arxiv_dgl/models.py:239-313; ``gat.py`` builds it 3 layers x 250 x 3 heads,
-    expt ``gat-3L250x3h``) for inference on the kernels -- same attribute names (``convs``, ``norms``, ``bias_last``), so the
+    expt ``gat-3L250x3h``) on the kernels, for inference and (training mode, autograd on) for training -- same attribute names (``convs``, ``norms``, ``bias_last``), so the
     reference's ``checkpoints/<expt>/<seed>.pt['model_state_dict']`` loads.  ``self.feat`` = the last hidden features: the
     [N, 750] tensor the student reads as ``teacher_out_feat`` (arxiv_pyg/gnn.py:278)."""
 
@@ -598,8 +599,11 @@ class ArxivGAT(nn.Module):
             if i < self.n_layers - 1:
                 h = h.flatten(1)
                 bn = self.norms[i]
-                if h.is_cuda and not self.training and ops.bn_shape_ok(h) and getattr(self.activation, "__name__", "") == "relu":
+                fusable = h.is_cuda and ops.bn_shape_ok(h) and getattr(self.activation, "__name__", "") == "relu"
+                if fusable and not self.training:
                     h = ops.bn_act(h, bn, relu=True, p=0.0, training=False)      # BatchNorm (running statistics) + ReLU fused
+                elif fusable and torch.is_grad_enabled():
+                    h = ops.bn_act(h, bn, relu=True, p=self.dropout.p, training=True)   # batch statistics + ReLU + dropout fused
                 else:
                     h = self.dropout(self.activation(bn(h)))
                 self.feat = h
@@ -611,6 +615,57 @@ def add_labels(feat, labels, idx, n_classes):
     onehot = torch.zeros([feat.shape[0], n_classes], dtype=feat.dtype, device=feat.device)
     onehot[idx, labels[idx, 0]] = 1
     return torch.cat([feat, onehot], dim=-1)
+
+
+ARXIV_GAT_EPSILON = 1 - math.log(2)
+
+
+def arxiv_gat_loss(x, labels):
+    """gat.py:98-101: mean of log(epsilon + CE) - log(epsilon) with epsilon = 1 - log 2 (``labels`` [n, 1])."""
+    y = F.cross_entropy(x, labels[:, 0], reduction="none")
+    return torch.mean(torch.log(ARXIV_GAT_EPSILON + y) - math.log(ARXIV_GAT_EPSILON))
+
+
+def arxiv_gat_label_split(train_idx, mask_rate, mask=None):
+    """gat.py:121-125: (train_labels_idx, train_pred_idx) -- the train nodes whose labels become input features (``rand < mask_rate``)
+    and the rest, whose predictions carry the loss.  ``mask``: a recorded draw (bool, one per train node) instead of a fresh one."""
+    if mask is None:
+        mask = torch.rand(train_idx.shape) < mask_rate
+    mask = mask.to(train_idx.device)
+    return train_idx[mask], train_idx[~mask]
+
+
+def arxiv_gat_adjust_learning_rate(optimizer, lr, epoch):
+    """gat.py:110-113: linear warm-up over the first 50 epochs (epochs count from 1)."""
+    if epoch <= 50:
+        for group in optimizer.param_groups:
+            group["lr"] = lr * epoch / 50
+
+
+def arxiv_gat_train_step(model, graph, feat, labels, train_idx, val_idx, test_idx, optimizer, n_classes, use_labels=True,
+                         n_label_iters=0, mask_rate=0.5, mask=None):
+    """One teacher training step, gat.py:116-148: label masking by ``mask_rate``, the masked-in labels appended as input features
+    (``add_labels``), ``n_label_iters`` label-reuse rounds (detached soft predictions written back for the unlabelled nodes, then
+    another forward), the loss of gat.py:98-101 on the prediction rows, backward, optimizer step.  Returns (train accuracy, loss)."""
+    model.train()
+    if use_labels:
+        train_labels_idx, train_pred_idx = arxiv_gat_label_split(train_idx, mask_rate, mask)
+        feat = add_labels(feat, labels, train_labels_idx, n_classes)
+    else:
+        train_pred_idx = arxiv_gat_label_split(train_idx, mask_rate, mask)[0]
+    optimizer.zero_grad()
+    pred = model(graph, feat)
+    if n_label_iters > 0:
+        unlabel_idx = torch.cat([train_pred_idx, val_idx, test_idx])
+        for _ in range(n_label_iters):
+            pred = pred.detach()
+            feat[unlabel_idx, -n_classes:] = F.softmax(pred[unlabel_idx], dim=-1)
+            pred = model(graph, feat)
+    loss = arxiv_gat_loss(pred[train_pred_idx], labels[train_pred_idx])
+    loss.backward()
+    optimizer.step()
+    acc = (pred[train_idx].argmax(dim=-1, keepdim=True) == labels[train_idx]).float().mean()
+    return float(acc), float(loss)
 
 
 @torch.no_grad()

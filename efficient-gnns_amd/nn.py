@@ -314,8 +314,9 @@ class DGLGATConv(nn.Module):
     gat.py:56-71 ``preprocess``: ``utils.dgl_bidirected_with_self_loops``).  x W on the fp32 MFMA, ``el`` / ``er`` as one more
     small GEMM, ``u_add_v`` + LeakyReLU + ``edge_softmax`` fused in ``egnn_gat_attention_fwd_f32``, ``u_mul_e`` + ``sum`` as
     one valued SpMM per head; symmetric normalisation (out-degree^-1/2 on the sources, in-degree^1/2 on the result) and the
-    residual projection as in the reference.  Returns [N, H, F].  Training the teacher is out of scope: training-mode drops
-    (``edge_drop`` / ``attn_drop`` / ``feat_drop``) raise."""
+    residual projection as in the reference.  Returns [N, H, F].  In training mode with autograd on the layer is differentiable
+    (``_forward_train``: one fused launch for all heads forward, three backward; ``edge_drop`` / ``attn_drop`` / ``feat_drop`` act
+    there).  In eval mode a call that would need gradients raises: the eval forward is the frozen teacher's."""
 
     def __init__(self, in_feats, out_feats, num_heads=1, feat_drop=0.0, attn_drop=0.0, edge_drop=0.0, negative_slope=0.2,
                  use_attn_dst=True, residual=False, activation=None, allow_zero_in_degree=False, use_symmetric_norm=False):
@@ -361,9 +362,13 @@ class DGLGATConv(nn.Module):
     def forward(self, adj: SparseTensor, feat: Tensor) -> Tensor:
         feat = _lib.real(feat)
         if torch.is_grad_enabled() and (feat.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("DGLGATConv runs the teacher's inference forward (torch.no_grad()); teacher training is out of scope")
+            if not self.training:
+                raise NotImplementedError("DGLGATConv in eval mode runs the frozen teacher (torch.no_grad() / requires_grad_(False)); "
+                                          "train it in training mode (.train())")
+            return self._forward_train(adj, feat)
         if self.training and (self.edge_drop > 0 or self.attn_drop_p > 0 or self.feat_drop_p > 0):
-            raise NotImplementedError("training-mode edge / attention / feature drop: teacher training is out of scope (use .eval())")
+            raise NotImplementedError("training-mode edge / attention / feature drop act in the differentiable forward only "
+                                      "(autograd on); use .eval() for inference")
         _lib.require_gpu(feat)
         n, H, F_ = feat.shape[0], self._num_heads, self._out_feats
         in_sqrt, out_rsqrt, has_isolated = self._degrees(adj)
@@ -400,6 +405,41 @@ class DGLGATConv(nn.Module):
             rst = rst * in_sqrt.view(n, 1, 1)
         if self.res_fc is not None:
             rst = rst + ops.linear(feat, self.res_fc.weight).view(n, -1, F_)
+        if self._activation is not None:
+            rst = self._activation(rst)
+        return rst
+
+    def _draw_edge_keep(self, nnz: int, device) -> Tensor:
+        """The entries edge_drop keeps in this call, as a bool [nnz] mask over the CSR entries: ``nnz - int(nnz * edge_drop)`` of
+        them chosen uniformly (models.py:207-212: ``randperm(E)[int(E * edge_drop):]``).  Overridable: a test injects a recorded set."""
+        keep = torch.zeros(nnz, dtype=torch.bool, device=device)
+        keep[torch.randperm(nnz, device=device)[int(nnz * self.edge_drop):]] = True
+        return keep
+
+    def _forward_train(self, adj: SparseTensor, feat: Tensor) -> Tensor:
+        """The differentiable forward (training mode, autograd on; models.py:154-236): ``feat_drop`` through ``F.dropout``, ``fc`` /
+        ``res_fc`` through ``ops.linear``, scores + edge softmax over the kept edges + aggregation + both symmetric-norm scales as one
+        autograd node (``ops_edge.dgl_gat_attention``: one HIP launch forward, three backward, csrc/gat.hip).  ``attn_drop`` draws one
+        [heads, nnz] multiplier per call (kept where >= p, scaled by 1 / (1 - p)), ``edge_drop`` one kept-entry set (``_draw_edge_keep``)."""
+        from .ops_edge import dgl_gat_attention
+        _lib.require_gpu(feat)
+        n, H, F_ = feat.shape[0], self._num_heads, self._out_feats
+        in_sqrt, out_rsqrt, has_isolated = self._degrees(adj)
+        if has_isolated and not self._allow_zero_in_degree:
+            raise AssertionError("zero in-degree node (arxiv_dgl/models.py:167-169)")
+        h = torch.nn.functional.dropout(feat, self.feat_drop_p, True) if self.feat_drop_p > 0 else feat
+        feat_src = ops.linear(h, self.fc.weight)                                  # [n, H*F], unscaled
+        nnz = adj.nnz()
+        keep = self._draw_edge_keep(nnz, feat.device) if self.edge_drop > 0 else None
+        mult = None
+        if self.attn_drop_p > 0:
+            kept = torch.rand(H, nnz, dtype=torch.float32, device=feat.device) >= self.attn_drop_p
+            mult = kept.to(torch.float32).mul_(1.0 / (1.0 - self.attn_drop_p) if self.attn_drop_p < 1 else 0.0)
+        r, q = (out_rsqrt, in_sqrt) if self._use_symmetric_norm else (None, None)
+        rst = dgl_gat_attention(feat_src, self.attn_l, self.attn_r, adj, H, self.negative_slope, keep=keep, mult=mult,
+                                src_scale=r, dst_scale=q)                         # [n, H, F]
+        if self.res_fc is not None:
+            rst = rst + ops.linear(h, self.res_fc.weight).view(n, -1, F_)
         if self._activation is not None:
             rst = self._activation(rst)
         return rst

@@ -285,3 +285,122 @@ def gat_attention(xl: Tensor, att_l: Tensor, att_r: Tensor, adj: SparseTensor, h
     if mult is not None:
         mult = mult.contiguous()
     return _GATAttention.apply(xl, att_l.contiguous(), att_r.contiguous(), adj, H, C, concat, negative_slope, mult)
+
+
+# ------------------------------------------------------------------------------------------------
+# one layer of the arxiv GAT teacher (DGL-style GATConv): fused all-heads forward + three-launch backward (csrc/gat.hip)
+# ------------------------------------------------------------------------------------------------
+def _block_diag_logits(xl: Tensor, attn_l: Tensor, attn_r: Tensor | None, H: int, C: int) -> Tensor:
+    """[n, 2H]: <xl[i,h,:], attn_l[h,:]> | <xl[i,h,:], attn_r[h,:]> (zeros without ``attn_r``) as ONE GEMM with a block-diagonal
+    [H*C, 2H] matrix."""
+    blk = torch.zeros(H * C, 2 * H, dtype=torch.float32, device=xl.device)
+    rows = torch.arange(H * C, device=xl.device)
+    blk[rows, rows // C] = attn_l.reshape(-1)
+    if attn_r is not None:
+        blk[rows, H + rows // C] = attn_r.reshape(-1)
+    return ops.matmul(xl, blk)
+
+
+def _gat_layer_desc(adj: SparseTensor, with_transpose: bool, n, nnz, H, C, xl, el, er, attn_l, attn_r, keep, mult, r, q, slope):
+    """The egnn_gat_layer_t descriptor (include/egnn_hip.h) of one layer call; the caller keeps the tensors alive for the call."""
+    rowptr, col, _ = adj.csr()
+    colptr = perm = t_col = None
+    if with_transpose:
+        colptr, perm = adj._transpose_meta()
+        t_col = adj.t()._col
+    return _lib.GatLayer(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(colptr), _lib.ptr(t_col), _lib.ptr(perm), n, nnz, H, C,
+                         _lib.ptr(xl), xl.stride(0), _lib.ptr(el), _lib.ptr(er), _lib.ptr(attn_l), _lib.ptr(attn_r),
+                         _lib.ptr(keep), _lib.ptr(mult), _lib.ptr(r), _lib.ptr(q), float(slope))
+
+
+def dgl_gat_layer_forward(xl, attn_l, attn_r, adj, H, C, slope, keep=None, mult=None, r=None, q=None):
+    """(out [n, H*C], att [H, nnz], el, er) of one layer without autograd: the logits GEMM and egnn_gat_layer_fwd_f32.  ``xl``
+    contiguous [n, H*C]; ``keep`` uint8 [nnz], ``mult`` float32 [H, nnz], ``r`` / ``q`` float32 [n], each or None."""
+    import ctypes
+    n, nnz = xl.shape[0], adj.nnz()
+    alpha = _block_diag_logits(xl, attn_l, attn_r, H, C)
+    el = alpha[:, :H]
+    el = (el * r.view(n, 1) if r is not None else el).contiguous()      # from the scaled source features
+    er = alpha[:, H:].contiguous() if attn_r is not None else None      # from the unscaled ones
+    att = torch.empty(H, nnz, dtype=torch.float32, device=xl.device)
+    out = torch.empty(n, H * C, dtype=torch.float32, device=xl.device)
+    desc = _gat_layer_desc(adj, False, n, nnz, H, C, xl, el, er, attn_l, attn_r, keep, mult, r, q, slope)
+    _lib.check(_lib.load().egnn_gat_layer_fwd_f32(ctypes.byref(desc), _lib.ptr(att), _lib.ptr(out), H * C, _lib.stream()),
+               "egnn_gat_layer_fwd_f32")
+    return out, att, el, er
+
+
+class _DGLGATAttention(torch.autograd.Function):
+    """out[i,h,:] = q_i sum_e att[h,e] mult[h,e] r_{col e} xl[col e,h,:], att = the per-target softmax over the kept entries of
+    leaky_relu(<r_j xl[j,h], attn_l[h]> + <xl[i,h], attn_r[h]>) (arxiv_dgl/models.py:179-225).  Forward: the small logits GEMM and ONE
+    launch for all heads (egnn_gat_layer_fwd_f32); backward: three launches (egnn_gat_layer_bwd_f32).  The transposed structure is
+    formed in the forward, so nothing in the backward waits for the host."""
+
+    @staticmethod
+    def forward(ctx, xl, attn_l, attn_r, adj, H, C, slope, keep, mult, r, q):
+        xl = xl.contiguous()
+        out, att, el, er = dgl_gat_layer_forward(xl, attn_l, attn_r, adj, H, C, slope, keep, mult, r, q)
+        adj._transpose_meta()
+        adj.t()
+        ctx.adj, ctx.H, ctx.C, ctx.slope = adj, H, C, float(slope)
+        ctx.has_r = attn_r is not None
+        ctx.save_for_backward(xl, el, er, att, keep, mult, r, q, attn_l, attn_r)
+        return out.view(xl.shape[0], H, C)
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes
+        xl, el, er, att, keep, mult, r, q, attn_l, attn_r = ctx.saved_tensors
+        adj, H, C = ctx.adj, ctx.H, ctx.C
+        n, nnz, HC = xl.shape[0], adj.nnz(), H * C
+        g = g.contiguous().view(n, HC)
+        lib, dev = _lib.load(), xl.device
+        d_raw = torch.empty(H, nnz, dtype=torch.float32, device=dev)
+        d_er = torch.empty(n, H, dtype=torch.float32, device=dev) if er is not None else None
+        dxl = torch.empty(n, HC, dtype=torch.float32, device=dev)
+        d_attn = torch.empty(2, HC, dtype=torch.float32, device=dev)
+        nws = lib.egnn_gat_layer_bwd_ws_floats(n, H, C)
+        ws = torch.empty(nws, dtype=torch.float32, device=dev)
+        desc = _gat_layer_desc(adj, True, n, nnz, H, C, xl, el, er, attn_l, attn_r, keep, mult, r, q, ctx.slope)
+        _lib.check(lib.egnn_gat_layer_bwd_f32(ctypes.byref(desc), _lib.ptr(att), _lib.ptr(g), HC, _lib.ptr(d_raw), _lib.ptr(d_er),
+                                              _lib.ptr(dxl), HC, _lib.ptr(d_attn), _lib.ptr(ws), nws, _lib.stream()),
+                   "egnn_gat_layer_bwd_f32")
+        d_r = d_attn[1].view(1, H, C) if ctx.has_r else None
+        return dxl, d_attn[0].view(1, H, C), d_r, None, None, None, None, None, None, None, None
+
+
+def dgl_gat_attention(xl: Tensor, attn_l: Tensor, attn_r: Tensor | None, adj: SparseTensor, heads: int, negative_slope: float,
+                      keep: Tensor | None = None, mult: Tensor | None = None, src_scale: Tensor | None = None,
+                      dst_scale: Tensor | None = None) -> Tensor:
+    """Differentiable attention + aggregation of one ``DGLGATConv`` (``xl`` = fc(h) [n, heads*C], unscaled) -> [n, heads, C].
+    ``adj``: square, CSR by target.  ``keep`` [nnz] bool / uint8: the entries edge_drop keeps (softmax over those; None = all);
+    ``mult`` [heads, nnz]: the attention-dropout multiplier; ``src_scale`` / ``dst_scale`` [n]: out-degree^-1/2 on the sources (folded
+    into the coefficient and into ``el``) and in-degree^1/2 on the result.  Gradients for ``xl``, ``attn_l`` and ``attn_r``."""
+    _lib.require_gpu(xl)
+    H = heads
+    n, C = xl.shape[0], xl.shape[1] // H
+    if xl.dim() != 2 or xl.shape[1] != H * C or attn_l.numel() != H * C or (attn_r is not None and attn_r.numel() != H * C):
+        raise ValueError("dgl_gat_attention: xl [n, heads*C], attn_l / attn_r [1, heads, C]")
+    if adj.sparse_size(0) != n or adj.sparse_size(1) != n:
+        raise ValueError("dgl_gat_attention: the message graph must be square over the rows of xl")
+    if H * C > 2048:
+        raise ValueError("dgl_gat_attention: heads * out_feats > 2048 is not supported by the backward (egnn_gat_layer_bwd_f32)")
+    nnz = adj.nnz()
+    if keep is not None:
+        if keep.numel() != nnz:
+            raise ValueError("dgl_gat_attention: keep has one entry per edge")
+        keep = keep.to(torch.uint8).contiguous()
+    if mult is not None:
+        if tuple(mult.shape) != (H, nnz):
+            raise ValueError("dgl_gat_attention: mult is [heads, nnz]")
+        mult = mult.to(torch.float32).contiguous()
+    scales = []
+    for s in (src_scale, dst_scale):
+        if s is not None:
+            if s.numel() != n:
+                raise ValueError("dgl_gat_attention: src_scale / dst_scale have one entry per node")
+            s = s.reshape(n).to(torch.float32).contiguous()
+        scales.append(s)
+    plain = adj.set_value(None) if adj.has_value() else adj
+    return _DGLGATAttention.apply(xl, attn_l.contiguous(), None if attn_r is None else attn_r.contiguous(), plain, H, C,
+                                  negative_slope, keep, mult, scales[0], scales[1])

@@ -453,6 +453,42 @@ int egnn_gat_aggregate_bwd_f32(const int64_t* colptr, const int64_t* t_col, cons
                                const float* d_alpha_dst, int64_t n_src, int64_t nnz, int H, int C, float* dxl, int64_t ld_dxl,
                                float* d_att, float* ws, size_t ws_floats, void* stream);
 
+/* One layer of the arxiv GAT teacher in training and inference (the reference's own GATConv over DGL message passing,
+ * /root/reference/arxiv_dgl/models.py:95-236; trained by arxiv_dgl/gat.py:116-148 with --use-norm --no-attn-dst --edge-drop=0.3,
+ * arxiv_dgl/scripts/gat-teachers.sh).  The layer's operands travel as ONE descriptor, egnn_gat_layer_t, read only while the
+ * call runs (it may live on the caller's stack).  Square message graph of n nodes, CSR by target (rowptr / col) and, for the
+ * backward, its transposed structure (colptr / t_col / perm as in egnn_gat_aggregate_bwd_f32; not read by the forward).
+ *   xl [n, ld_xl >= H*C]  the projected features fc(h), UNSCALED, read in place (any C: 16-, 8- or 4-byte aligned head blocks)
+ *   el [n,H]              <r_j xl[j,h,:], attn_l[h,:]> (from the scaled source features, models.py:179-196)
+ *   er [n,H] nullable     <xl[i,h,:], attn_r[h,:]> (from the unscaled ones, :199-200); NULL together with attn_r (--no-attn-dst)
+ *   keep [nnz] bytes, nullable      the entries edge_drop keeps (models.py:207-212); the softmax runs over the kept entries
+ *   mult [H,nnz] nullable           the attention-dropout multiplier (mask / (1 - p))
+ *   src_scale r [n], dst_scale q [n], nullable   out-degree^-1/2 and in-degree^1/2 of use_symmetric_norm (:179-184,220-225)
+ * Forward, one launch for all heads (csrc/gat.hip):
+ *   s_e = leaky_relu(el[col e,h] + er[i,h]);  att[h,e] = softmax of s over the kept entries of row i, exactly 0 at dropped
+ *   entries (a row without a kept entry: all zeros);  out[i,h,:] = q_i sum_e att[h,e] mult[h,e] r_{col e} xl[col e,h,:]
+ *   att [H,nnz] head-major; out [n, ld_out >= H*C].
+ * Backward, three launches for all heads, fixed summation order, no atomics.  go [n, ld_go >= H*C] = d out; with go' = q_i go_i:
+ *   g_e = mult_e r_{col e} <go'_i, xl[col e]>;  d_raw[h,e] = att_e (g_e - sum_row att g) * (s_e > 0 ? 1 : negative_slope)
+ *   d_er[i,h] = sum_row d_raw (NULL with er);  d_el[j,h] = sum_{col e = j} d_raw
+ *   dxl[j,h,:] = r_j (sum_{col e = j} att_e mult_e go'_{row e} + d_el[j,h] attn_l[h,:]) + d_er[j,h] attn_r[h,:]
+ *   d_attn [2,H*C] nullable: d_attn[0] = sum_j r_j xl_j d_el[j] (= d attn_l), d_attn[1] = sum_j xl_j d_er[j] (= d attn_r);
+ *   needs H*C <= 2048 and ws of egnn_gat_layer_bwd_ws_floats(n, H, C) floats.  d_raw [H,nnz]: scratch of the call. */
+typedef struct egnn_gat_layer {
+  const int64_t* rowptr; const int64_t* col;
+  const int64_t* colptr; const int64_t* t_col; const int64_t* perm;
+  int64_t n; int64_t nnz; int H; int C;
+  const float* xl; int64_t ld_xl;
+  const float* el; const float* er;
+  const float* attn_l; const float* attn_r;
+  const uint8_t* keep; const float* mult; const float* src_scale; const float* dst_scale;
+  float negative_slope;
+} egnn_gat_layer_t;
+int egnn_gat_layer_fwd_f32(const egnn_gat_layer_t* layer, float* att, float* out, int64_t ld_out, void* stream);
+size_t egnn_gat_layer_bwd_ws_floats(int64_t n, int H, int C);
+int egnn_gat_layer_bwd_f32(const egnn_gat_layer_t* layer, const float* att, const float* go, int64_t ld_go, float* d_raw, float* d_er,
+                           float* dxl, int64_t ld_dxl, float* d_attn, float* ws, size_t ws_floats, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused BatchNorm1d (+ ReLU + dropout) over node rows -- SURVEY.md 8(f) rank 1; replaces the ATen BatchNorm /
  * threshold / fused_dropout chain at /root/reference/arxiv_pyg/gnn.py:48-50,80-82,296-306.
