@@ -135,7 +135,14 @@ SIGNATURES = {
     "egnn_fitnet_bwd_f32": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _i64, _p, _i64, _p]),
     "egnn_at_fwd_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _sz, _p]),
     "egnn_at_bwd_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _i64, _p, _i64, _p]),
-    "egnn_probe_gather_lines_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _i32, _i32, _p, _p]),
+    "egnn_saint_induced_geometry": (_i64, [_i32]),
+    "egnn_saint_random_walk_i64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _u64, _p, _p, _p, _p]),
+    "egnn_saint_scan_ws_bytes": (_sz, [_i64]),
+    "egnn_saint_select_i64": (_i32, [_p, _i64, _p, _p, _i64, _p, _sz, _p]),
+    "egnn_saint_induced_count_i64": (_i32, [_p, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _p, _sz, _p]),
+    "egnn_saint_induced_fill_i64": (_i32, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _p, _p, _p]),
+    "egnn_saint_gather_i64": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p]),
+    "egnn_probe_gather_lines_f32":(_i32, [_p, _i64, _i64, _i64, _p, _i64, _i32, _i32, _p, _p]),
 }
 
 _lib = None

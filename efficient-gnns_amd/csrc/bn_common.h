@@ -26,10 +26,12 @@ __device__ __forceinline__ unsigned mix32(unsigned x) {
   x ^= x >> 16;
   return x;
 }
-__device__ __forceinline__ float uniform01(unsigned long long seed, unsigned long long idx) {
+__device__ __forceinline__ unsigned hash32(unsigned long long seed, unsigned long long idx) {
   unsigned h = mix32((unsigned)idx ^ (unsigned)seed);
-  h = mix32(h + (unsigned)(seed >> 32) + (unsigned)(idx >> 32) * 0x9E3779B9U);
-  return (float)(h >> 8) * (1.0f / 16777216.0f);
+  return mix32(h + (unsigned)(seed >> 32) + (unsigned)(idx >> 32) * 0x9E3779B9U);
+}
+__device__ __forceinline__ float uniform01(unsigned long long seed, unsigned long long idx) {
+  return (float)(hash32(seed, idx) >> 8) * (1.0f / 16777216.0f);
 }
 
 // per-element forward pieces shared by forward and backward

@@ -7,6 +7,7 @@ network).  Integer / host-side generation only -- tensors are move
                     (/root/reference/arxiv_pyg/gnn.py:236-279)
   * ``ppi_like``    PPI: 20+2+2 graphs, x [n,50], 121 labels (/root/reference/ppi_pyg/gnn.py:301-310)
   * ``mag_like``    ogbn-mag grouped homogeneous graph (/root/reference/mag_pyg/gnn.py:322-346)
+  * ``mag_hetero_like``  ogbn-mag as the heterogeneous dataset the script loads (/root/reference/mag_pyg/gnn.py:308-320)
 """
 from __future__ import annotations
 
@@ -204,6 +205,81 @@ def mag_like(scale: float = 1.0, seed: int = 0, feats: int = 128):
     d.num_nodes, d.num_features, d.num_classes = n, feats, 349
     d.x = torch.randn(n, feats, generator=g)
     d.adj_t = to_sparse_tensor(ei, n).to_symmetric()
+    return d
+
+
+MAG = dict(num_nodes=dict(author=1_134_649, field_of_study=59_965, institution=8_740, paper=736_389),
+           num_edges={("author", "affiliated_with", "institution"): 1_043_998, ("author", "writes", "paper"): 7_145_660,
+                      ("paper", "cites", "paper"): 5_416_271, ("paper", "has_topic", "field_of_study"): 7_505_078},
+           num_features=128, num_classes=349, split=(629_571, 64_879, 41_939))
+
+
+def powerlaw_bipartite_edges(n_src: int, n_dst: int, e: int, gamma: float = 2.2, max_degree: int | None = None, seed: int = 0) -> np.ndarray:
+    """``powerlaw_edges`` between two node sets: [2, e] (source in [0, n_src), target in [0, n_dst)), power-law in-degree of the
+    targets (same Chung-Lu weights and hub bisection), near-uniform out-degree, no duplicate edges, target ids randomly permuted."""
+    rng = np.random.default_rng(seed)
+    alpha = 1.0 / (gamma - 1.0)
+    ranks = np.arange(n_dst, dtype=np.float64)
+
+    def probs(i0):
+        w = (ranks + i0) ** (-alpha)
+        return w / w.sum()
+
+    i0 = 1.0
+    if max_degree is not None:
+        lo, hi = 1e-3, 1e7
+        for _ in range(60):
+            mid = (lo * hi) ** 0.5
+            if probs(mid)[0] * e > max_degree:
+                lo = mid
+            else:
+                hi = mid
+        i0 = hi
+    p = probs(i0)
+    perm = rng.permutation(n_dst)
+    keys = np.empty(0, dtype=np.int64)
+    need = e
+    while need > 0:
+        m = int(need * 1.1) + 16
+        dst = perm[rng.choice(n_dst, size=m, p=p)]
+        src = rng.integers(0, n_src, size=m)
+        keys = np.unique(np.concatenate([keys, src.astype(np.int64) * n_dst + dst]))
+        need = e - keys.size
+    if keys.size > e:
+        keys = np.sort(rng.choice(keys, size=e, replace=False))
+    return np.stack([keys // n_dst, keys % n_dst])
+
+
+def mag_hetero_like(scale: float = 1.0, seed: int = 0, feats: int = 128):
+    """Synthetic ogbn-mag-shaped heterogeneous dataset (CPU tensors) with the fields /root/reference/mag_pyg/gnn.py:308-357 reads:
+    ``x_dict`` (paper features only), ``edge_index_dict`` (the four directed relations; the script adds the reverses and symmetrises
+    ``cites`` itself), ``num_nodes_dict``, ``y_dict`` (paper labels [n, 1]) and ``split_idx`` ({'train' | 'valid' | 'test': {'paper':
+    ids}}).  ``scale`` = 1: 736 389 papers, 1 134 649 authors, 8 740 institutions, 59 965 fields of study; 1 043 998 / 7 145 660 /
+    5 416 271 / 7 505 078 edges; 349 classes; power-law in-degrees as in ``powerlaw_edges``.  ``scale`` < 1 shrinks every count."""
+    nodes = {k: max(4, int(round(v * scale))) for k, v in MAG["num_nodes"].items()}
+    hub = max(8, int(30_000 * min(1.0, scale * 4)))
+    d = types.SimpleNamespace()
+    d.num_nodes_dict = dict(nodes)
+    d.edge_index_dict = {}
+    for i, (key, e_full) in enumerate(MAG["num_edges"].items()):
+        n_src, n_dst = nodes[key[0]], nodes[key[-1]]
+        e = min(max(8, int(round(e_full * scale))), n_src * (n_dst - (key[0] == key[-1])) // 2)
+        md = max(2, min(hub, n_src // 2))
+        if key[0] == key[-1]:
+            ei = powerlaw_edges(n_src, e, gamma=2.3, max_degree=md, seed=seed * 16 + i)
+        else:
+            ei = powerlaw_bipartite_edges(n_src, n_dst, e, gamma=2.3, max_degree=md, seed=seed * 16 + i)
+        d.edge_index_dict[key] = torch.from_numpy(ei)
+    g = torch.Generator().manual_seed(seed)
+    n_paper = nodes["paper"]
+    d.num_features, d.num_classes = feats, MAG["num_classes"]
+    d.x_dict = {"paper": torch.randn(n_paper, feats, generator=g)}
+    d.y_dict = {"paper": torch.randint(0, d.num_classes, (n_paper, 1), generator=g)}
+    tr, va, te = MAG["split"]
+    n_tr, n_va = int(round(n_paper * tr / (tr + va + te))), int(round(n_paper * va / (tr + va + te)))
+    perm = torch.randperm(n_paper, generator=g)
+    d.split_idx = {"train": {"paper": perm[:n_tr].clone()}, "valid": {"paper": perm[n_tr:n_tr + n_va].clone()},
+                   "test": {"paper": perm[n_tr + n_va:].clone()}}
     return d
 
 

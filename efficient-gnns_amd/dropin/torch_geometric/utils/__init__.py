@@ -1,4 +1,6 @@
-from efficient_gnns_amd.utils import softmax, subgraph  # noqa: F401
+from efficient_gnns_amd.utils import group_hetero_graph, softmax, subgraph, to_undirected  # noqa: F401
+
+from . import hetero  # noqa: F401
 
 
 def _not_on_hot_path(name):

@@ -748,7 +748,8 @@ class StudentNet(nn.Module):
 class RGCN(nn.Module):
     """/root/reference/mag_pyg/gnn.py:71-168 on the kernels: ``forward`` on a (sampled) grouped subgraph through
     ``nn.RGCNConv``; ``inference`` full-batch, one rectangular mean-SpMM (``adj_t.matmul(x, reduce='mean')``, :151,162) and
-    one GEMM per relation and layer.  The GraphSAINT sampler that feeds ``forward`` in the reference is out of scope."""
+    one GEMM per relation and layer.  The GraphSAINT sampler that feeds ``forward`` in the reference is ``saint.py``: its batches
+    carry the per-relation structure (``batch.relations``), which ``forward(..., relations=)`` hands to every layer."""
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, dropout, num_nodes_dict, x_types, num_edge_types):
         super().__init__()
@@ -779,10 +780,10 @@ class RGCN(nn.Module):
             h[mask] = emb[local_node_idx[mask]]
         return h
 
-    def forward(self, x_dict, edge_index, edge_type, node_type, local_node_idx):
+    def forward(self, x_dict, edge_index, edge_type, node_type, local_node_idx, relations=None):
         x = self.group_input(x_dict, node_type, local_node_idx)
         for i, conv in enumerate(self.convs):
-            x = conv(x, edge_index, edge_type, node_type)
+            x = conv(x, edge_index, edge_type, node_type, relations=relations)
             if i != self.num_layers - 1:
                 x = F.dropout(F.relu(x), p=0.5, training=self.training)
                 self.out_feat = x
@@ -876,3 +877,88 @@ def ppi_test(model, graphs):
     if tp + fp == 0:
         return 0
     return 2 * tp / (2 * tp + fp + fn)
+
+
+MAG_MODES = PPI_MODES
+
+
+def mag_batch_loss(model, batch, x_dict, mode, hp, teacher_model=None, student_proj=None, teacher_proj=None):
+    """``(loss, loss_cls, loss_aux)`` of one GraphSAINT batch: the loop body of /root/reference/mag_pyg/gnn.py:188-253.  Logits and
+    labels on the rows ``batch.train_mask``; class-index cross entropy criteria (mag_pyg/criterion.py); in every mode but
+    ``supervised`` the frozen teacher's forward runs under ``no_grad`` on the same batch, sharing ``batch.relations`` with the student.
+    ``fitnet`` / ``nce`` pass the features through ``student_proj`` / ``teacher_proj`` (``make_projection``); ``at`` / ``gpw`` / ``lpw``
+    compare ``out_feat`` directly (:226); ``lpw`` runs over the subgraph induced by the train rows (:237).  ``hp`` as in
+    ``ppi_train_epoch``."""
+    if mode not in MAG_MODES:
+        raise NotImplementedError(mode)
+    rel = getattr(batch, "relations", None)
+    args = (x_dict, batch.edge_index, batch.edge_attr, batch.node_type, batch.local_node_idx)
+    out = model(*args, relations=rel)
+    rows = batch.train_mask.nonzero().view(-1)          # the rows [train_mask] of :191-192, picked inside the CE / KD kernels
+    labels = batch.y.view(-1)
+    if mode == "supervised":
+        loss = ops.cross_entropy(out, labels, rows)
+        return loss, loss, loss * 0
+    with torch.no_grad():
+        teacher_out = teacher_model(*args, relations=rel)
+        teacher_feat = ops.take_rows(teacher_model.out_feat, rows)
+    if mode == "kd":
+        return C.rows_kd_criterion(out, labels, teacher_out, hp["alpha"], hp["kd_T"], rows=rows)
+    feat = ops.take_rows(model.out_feat, rows)
+    if mode == "fitnet":
+        return C.rows_fitnet_criterion(out, labels, student_proj(feat), teacher_proj(teacher_feat), hp["beta"], rows=rows)
+    if mode == "at":
+        return C.rows_at_criterion(out, labels, feat, teacher_feat, hp["beta"], rows=rows)
+    if mode == "gpw":
+        return C.rows_gpw_criterion(out, labels, feat, teacher_feat, hp["kernel"], hp["beta"], hp["max_samples"], rows=rows)
+    if mode == "lpw":
+        from .utils import subgraph
+        edge_index = subgraph(rows, batch.edge_index, relabel_nodes=True, num_nodes=batch.num_nodes)[0]
+        return C.rows_lpw_criterion(out, labels, feat, teacher_feat, edge_index, hp["kernel"], hp["beta"], rows=rows)
+    return C.rows_nce_criterion(out, labels, student_proj(feat), teacher_proj(teacher_feat), hp["beta"], hp["nce_T"], hp["max_samples"],
+                                rows=rows)
+
+
+def mag_train_epoch(model, loader, x_dict, optimizer, mode, hp, teacher_model=None, student_proj=None, teacher_proj=None):
+    """One MAG epoch (/root/reference/mag_pyg/gnn.py:174-268): one optimisation step per GraphSAINT batch of ``loader``
+    (``saint.GraphSAINTRandomWalkSampler`` or any iterable of batches); returns the epoch means of (loss, loss_cls, loss_aux) weighted
+    by the number of train rows of each batch, like the reference."""
+    if mode not in MAG_MODES:
+        raise NotImplementedError(mode)
+    model.train()
+    for m in (student_proj, teacher_proj):
+        if m is not None:
+            m.train()
+    if teacher_model is not None:
+        teacher_model.eval()
+    tot, examples = [0.0, 0.0, 0.0], 0
+    dev = next(model.parameters()).device
+    for batch in loader:
+        batch = batch.to(dev)
+        loss, loss_cls, loss_aux = mag_batch_loss(model, batch, x_dict, mode, hp, teacher_model, student_proj, teacher_proj)
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        vals = torch.stack([loss.detach(), loss_cls.detach(), loss_aux.detach(), batch.train_mask.sum().to(loss.dtype)]).tolist()
+        n = int(vals[3])
+        for i in range(3):
+            tot[i] += vals[i] * n
+        examples += n
+    return tuple(v / max(1, examples) for v in tot)
+
+
+@torch.no_grad()
+def mag_test(model, x_dict, edge_index_dict, key2int, y_paper, split_idx):
+    """``test()`` of /root/reference/mag_pyg/gnn.py:271-294: full-batch ``model.inference``, argmax over the paper rows, the three
+    accuracies (train, valid, test) through ``accuracy``.  ``split_idx``: {'train' | 'valid' | 'test': paper ids, or the reference's
+    nested {'paper': ids}}."""
+    model.eval()
+    out = model.inference(x_dict, edge_index_dict, key2int)[key2int["paper"]]
+    y_pred = out.argmax(dim=-1, keepdim=True)
+    y_true = y_paper.to(y_pred.device).view(-1, 1)
+    accs = []
+    for k in ("train", "valid", "test"):
+        idx = split_idx[k]
+        idx = (idx["paper"] if isinstance(idx, dict) else idx).to(y_pred.device)
+        accs.append(accuracy(y_true[idx], y_pred[idx]))
+    return tuple(accs)

@@ -485,11 +485,13 @@ class RGCNConv(nn.Module):
             return adjs, rows
         return _RGCN_REL_CACHE.get((edge_index, edge_type, node_type), (n, self.num_edge_types, self.num_node_types), build)
 
-    def forward(self, x: Tensor, edge_index: Tensor, edge_type: Tensor, node_type: Tensor) -> Tensor:
+    def forward(self, x: Tensor, edge_index: Tensor, edge_type: Tensor, node_type: Tensor, relations=None) -> Tensor:
+        """``relations``: what ``_relations`` would return for these arguments, built elsewhere (``saint.SaintBatch.relations``: the
+        sampler forms it with the batch); None = build (and memoise) it here."""
         x = _lib.real(x)
         _lib.require_gpu(x, edge_index)
         n = x.shape[0]
-        adjs, rows = self._relations(edge_index, edge_type, node_type, n)
+        adjs, rows = relations if relations is not None else self._relations(edge_index, edge_type, node_type, n)
         out = torch.zeros(n, self.out_channels, dtype=torch.float32, device=x.device)
         for i, adj in enumerate(adjs):
             if adj is not None:

@@ -621,6 +621,60 @@ int egnn_at_fwd_f32(const float* f, int64_t ldf, int64_t Df, const float* t, int
 int egnn_at_bwd_f32(const float* f, int64_t ldf, int64_t Df, const float* t, int64_t ldt, int64_t Dt, int64_t n, float eps, const float* ws,
                     const float* g, float* df, int64_t lddf, float* dt, int64_t lddt, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * GraphSAINT random-walk mini-batches formed on the device (csrc/saint.hip).
+ *
+ * Replaces torch_geometric.data.GraphSAINTRandomWalkSampler, /root/reference/mag_pyg/gnn.py:361-366, i.e.
+ * torch_sparse::random_walk + SparseTensor.saint_subgraph + the attribute gathers of its collate step (CPU C++ inside
+ * DataLoader workers there, iterated by train() at :187-190), and the per-relation structure RGCNConv needs per batch (:25-68).
+ * Integer work, no atomics, every output written with plain stores; node ids and row counts must be below 2^31.
+ *
+ * egnn_saint_random_walk_i64   B walks of L >= 1 steps over the CSR (rowptr [N+1], col [nnz]).  Step rule of
+ *     torch_sparse::random_walk: from node n with d = rowptr[n+1] - rowptr[n] entries stay at n when d == 0, else go to
+ *     col[rowptr[n] + min(int64(u * d), d - 1)], the product formed in fp32.  walks [B, L+1] (nullable) receives the nodes;
+ *     flag [N] (uint8, zeroed by the caller) gets 1 at every visited node.
+ *     Draws: INJECTED when start [B] (int64, ids outside [0, N) are clamped into it) and rand [B, L] (fp32 in [0, 1)) are given;
+ *     OWN when both are NULL (one without the other is EGNN_EINVAL): with key = seed + *seed_dev (seed_dev nullable: 0) and
+ *     h(key, c) the two-round 32-bit counter hash of the dropout kernels (csrc/bn_common.h hash32 / uniform01), walk b uses the
+ *     counters c = b * (L + 1) + j:  j = 0: start = (h * N) >> 32 (64-bit product of the 32-bit hash; no float involved);
+ *     j = 1 .. L: u of step j = (h >> 8) * 2^-24.
+ * egnn_saint_select_i64        relabel [N+1] = exclusive scan of flag (relabel[N] = number of flagged nodes = n_sub) and
+ *     node_idx[relabel[i]] = i for every flagged i: the ascending list walks.view(-1).unique().  node_idx holds node_cap >= n_sub
+ *     ids (B * (L + 1) always suffices).  ws: egnn_saint_scan_ws_bytes(N) bytes.
+ * egnn_saint_induced_count_i64 / _fill_i64   the sub-matrix of a parent CSR (rowptr, col [, val]) on flagged rows and columns.
+ *     Output row r = g * n_map + i, g < groups, i < n_map, stands for parent row g * group_stride + row_map[i]; rows with
+ *     i >= *n_map_dev (nullable: all n_map rows) are empty, so the caller may size n_map by an upper bound before n_sub is known
+ *     on the host.  groups = 1: SparseTensor.saint_subgraph(node_idx); groups = T over a parent of T * N rows sorted by
+ *     (edge type, destination, source): the per-relation CSRs of the batch.  N = number of columns = length of flag / relabel.
+ *     count: counts [groups * n_map] = flagged entries per output row, out_ptr [groups * n_map + 1] = their exclusive scan
+ *            (ws: egnn_saint_scan_ws_bytes(groups * n_map) bytes);
+ *     fill:  for the kept entries of output row r, IN THE PARENT'S ORDER, at out_ptr[r] ...: out_row (nullable) = i,
+ *            out_col = relabel[col], out_val (nullable) = val[entry] (val nullable: the entry's position in the parent).
+ *            Positions >= out_cap are not written.  flag must be the one the counts were taken with.
+ *     A wave compacts egnn_saint_induced_geometry(0) entries per pass (ballot + popcount prefix); rows with more than
+ *     egnn_saint_induced_geometry(2) entries are compacted by one workgroup, egnn_saint_induced_geometry(1) entries per pass;
+ *     both carry the row's running offset from pass to pass.
+ * egnn_saint_gather_i64        o_*[i] = *[node_idx[i]], i < n_sub, for node_type / local_idx / y (int64) and train_mask (uint8),
+ *     each nullable; o_edge_attr[e] = edge_attr[edge_idx[e]], e < e_sub (edge_attr nullable).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t egnn_saint_induced_geometry(int which);
+int egnn_saint_random_walk_i64(const int64_t* rowptr, const int64_t* col, int64_t N, int64_t nnz, int64_t B, int64_t L,
+                               const int64_t* start, const float* rand, uint64_t seed, const uint64_t* seed_dev, int64_t* walks,
+                               uint8_t* flag, void* stream);
+size_t egnn_saint_scan_ws_bytes(int64_t items);
+int egnn_saint_select_i64(const uint8_t* flag, int64_t N, int64_t* relabel, int64_t* node_idx, int64_t node_cap, void* ws,
+                          size_t ws_bytes, void* stream);
+int egnn_saint_induced_count_i64(const int64_t* rowptr, const int64_t* col, const int64_t* row_map, int64_t n_map,
+                                 const int64_t* n_map_dev, int64_t groups, int64_t group_stride, int64_t N, const uint8_t* flag,
+                                 int64_t* counts, int64_t* out_ptr, void* ws, size_t ws_bytes, void* stream);
+int egnn_saint_induced_fill_i64(const int64_t* rowptr, const int64_t* col, const int64_t* val, const int64_t* row_map, int64_t n_map,
+                                const int64_t* n_map_dev, int64_t groups, int64_t group_stride, int64_t N, const uint8_t* flag,
+                                const int64_t* relabel, const int64_t* out_ptr, int64_t out_cap, int64_t* out_row, int64_t* out_col,
+                                int64_t* out_val, void* stream);
+int egnn_saint_gather_i64(const int64_t* node_idx, int64_t n_sub, const int64_t* node_type, const int64_t* local_idx, const int64_t* y,
+                          const uint8_t* train_mask, int64_t* o_node_type, int64_t* o_local_idx, int64_t* o_y, uint8_t* o_train_mask,
+                          const int64_t* edge_idx, int64_t e_sub, const int64_t* edge_attr, int64_t* o_edge_attr, void* stream);
+
 /* DIAGNOSTIC (measurement only; bench.py's roofline.gather_ceiling_GBs): replays the gather stream of one aggregation call and
  * nothing else -- for every stored entry e, the 128-byte slice s of row col[e] of X [n_src, K] is read by an 8-lane sub-group,
  * slice s by the workgroups with blockIdx % (K / 32) == s (the aggregation kernel's slice <-> XCD binding,
