@@ -26,7 +26,7 @@ class BnAct(C.Structure):
 
 
 class GatLayer(C.Structure):
-    """egnn_gat_layer_t of include/egnn_hip.h, field for field: the operands of one DGL-style GAT layer (forward and backward)."""
+    """egnn_gat_layer_t of include/egnn_hip.h, field for field: the operands of one GAT layer (PyG GATConv or the DGL-style one)."""
     _fields_ = [("rowptr", _p), ("col", _p),
                 ("colptr", _p), ("t_col", _p), ("perm", _p),
                 ("n", _i64), ("nnz", _i64), ("H", _i32), ("C", _i32),
@@ -98,13 +98,9 @@ SIGNATURES = {
     "egnn_edge_sim_f32": (_i32, [_p, _i64, _i64, _p, _p, _i64, _i32, _p, _p, _p]),
     "egnn_edge_sim_coef_f32": (_i32, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p]),
     "egnn_gat_attention_fwd_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, _i32, _f32, _p, _p]),
-    "egnn_gat_attention_bwd_f32": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _f32, _i64, _i64, _i32, _i32, _f32, _p, _p, _p]),
-    "egnn_gat_aggregate_bwd_ws_floats": (_sz, [_i64, _i32, _i32]),
-    "egnn_gat_aggregate_bwd_f32": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _p, _i64, _p, _p, _p, _i64, _i64, _i32, _i32, _p, _i64,
-                                          _p, _p, _sz, _p]),
     "egnn_gat_layer_fwd_f32": (_i32, [_p, _p, _p, _i64, _p]),
     "egnn_gat_layer_bwd_ws_floats": (_sz, [_i64, _i32, _i32]),
-    "egnn_gat_layer_bwd_f32": (_i32, [_p, _p, _p, _i64, _p, _p, _p, _i64, _p, _p, _sz, _p]),
+    "egnn_gat_layer_bwd_f32": (_i32, [_p, _p, _p, _i64, _i32, _p, _p, _p, _i64, _p, _p, _sz, _p]),
     "egnn_segment_softmax_fwd_f32": (_i32, [_p, _p, _i64, _p, _p]),
     "egnn_segment_softmax_bwd_f32": (_i32, [_p, _p, _p, _i64, _p, _p]),
     "egnn_segment_sum_f32": (_i32, [_p, _p, _i64, _p, _p]),
@@ -165,7 +161,7 @@ def load() -> C.CDLL:
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype, fn.argtypes = res, args
-    if lib.egnn_abi_version() != 7:
+    if lib.egnn_abi_version() != 8:
         raise HipExtensionError("libegnn_hip.so ABI version mismatch")
     _lib = lib
     return lib

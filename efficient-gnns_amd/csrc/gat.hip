@@ -357,42 +357,7 @@ int gat_launch_aggregate_bwd(const int64_t* colptr, const int64_t* t_col, const 
 
 }  // namespace
 
-extern "C" int egnn_gat_attention_bwd_f32(const int64_t* rowptr, const int64_t* col, const float* alpha_src, const float* alpha_dst,
-                                          const float* att, const float* mult, const float* xl, int64_t ld_xl, const float* go,
-                                          int64_t ld_go, int64_t go_head_stride, float go_scale, int64_t n_rows, int64_t nnz, int H,
-                                          int C, float negative_slope, float* d_raw, float* d_alpha_dst, void* stream) {
-  EGNN_CHECK_ARG(n_rows >= 0 && nnz >= 0 && H > 0 && H <= 64 && C > 0);
-  EGNN_CHECK_ARG(ld_xl >= (int64_t)H * C && go_head_stride >= 0 && ld_go >= (H - 1) * go_head_stride + C);
-  if (n_rows == 0) return EGNN_OK;
-  EGNN_CHECK_ARG(rowptr && d_alpha_dst);
-  EGNN_CHECK_ARG(nnz == 0 || (col && alpha_src && alpha_dst && att && xl && go && d_raw));
-  return gat_launch_attention_bwd(rowptr, col, alpha_src, alpha_dst, att, mult, xl, ld_xl, go, ld_go, go_head_stride, go_scale, n_rows, nnz,
-                                  H, C, negative_slope, nullptr, nullptr, d_raw, d_alpha_dst, (hipStream_t)stream);
-}
-
-extern "C" size_t egnn_gat_aggregate_bwd_ws_floats(int64_t n_src, int H, int C) {
-  if (n_src < 0 || H <= 0 || C <= 0) return 0;
-  return (size_t)gat_bwd_blocks(n_src) * 2 * (size_t)H * (size_t)C;
-}
-
-extern "C" int egnn_gat_aggregate_bwd_f32(const int64_t* colptr, const int64_t* t_col, const int64_t* perm, const float* att,
-                                          const float* mult, const float* d_raw, const float* go, int64_t ld_go, int64_t go_head_stride,
-                                          float go_scale, const float* xl, int64_t ld_xl, const float* att_l, const float* att_r,
-                                          const float* d_alpha_dst, int64_t n_src, int64_t nnz, int H, int C, float* dxl, int64_t ld_dxl,
-                                          float* d_att, float* ws, size_t ws_floats, void* stream) {
-  EGNN_CHECK_ARG(n_src >= 0 && nnz >= 0 && H > 0 && H <= 64 && C > 0);
-  const int64_t HC = (int64_t)H * C;
-  EGNN_CHECK_ARG(ld_dxl >= HC && ld_xl >= HC && go_head_stride >= 0 && ld_go >= (H - 1) * go_head_stride + C);
-  EGNN_CHECK_ARG((att_r == nullptr) == (d_alpha_dst == nullptr));
-  if (d_att != nullptr) EGNN_CHECK_ARG(HC <= kGatMaxHC && ws && xl && ws_floats >= egnn_gat_aggregate_bwd_ws_floats(n_src, H, C));
-  if (n_src == 0) return EGNN_OK;
-  EGNN_CHECK_ARG(colptr && att_l && dxl);
-  EGNN_CHECK_ARG(nnz == 0 || (t_col && perm && att && d_raw && go));
-  return gat_launch_aggregate_bwd(colptr, t_col, perm, att, mult, d_raw, go, ld_go, go_head_stride, go_scale, xl, ld_xl, att_l, att_r,
-                                  d_alpha_dst, n_src, nnz, H, C, nullptr, nullptr, dxl, ld_dxl, d_att, ws, (hipStream_t)stream);
-}
-
-// ---- one DGL-style GAT layer as a descriptor (include/egnn_hip.h: egnn_gat_layer_t) ----
+// ---- one GAT layer (PyG GATConv or the DGL-style one) as a descriptor (include/egnn_hip.h: egnn_gat_layer_t) ----
 static int gat_layer_check(const egnn_gat_layer_t* L) {
   EGNN_CHECK_ARG(L != nullptr);
   EGNN_CHECK_ARG(L->n >= 0 && L->nnz >= 0 && L->H > 0 && L->H <= 64 && L->C > 0 && L->ld_xl >= (int64_t)L->H * L->C);
@@ -425,23 +390,31 @@ extern "C" int egnn_gat_layer_fwd_f32(const egnn_gat_layer_t* L, float* att, flo
   return egnn_launch_status();
 }
 
-extern "C" size_t egnn_gat_layer_bwd_ws_floats(int64_t n, int H, int C) { return egnn_gat_aggregate_bwd_ws_floats(n, H, C); }
+extern "C" size_t egnn_gat_layer_bwd_ws_floats(int64_t n, int H, int C) {
+  if (n < 0 || H <= 0 || C <= 0) return 0;
+  return (size_t)gat_bwd_blocks(n) * 2 * (size_t)H * (size_t)C;
+}
 
-extern "C" int egnn_gat_layer_bwd_f32(const egnn_gat_layer_t* L, const float* att, const float* go, int64_t ld_go, float* d_raw, float* d_er,
-                                      float* dxl, int64_t ld_dxl, float* d_attn, float* ws, size_t ws_floats, void* stream) {
+extern "C" int egnn_gat_layer_bwd_f32(const egnn_gat_layer_t* L, const float* att, const float* go, int64_t ld_go, int mean_heads,
+                                      float* d_raw, float* d_er, float* dxl, int64_t ld_dxl, float* d_attn, float* ws, size_t ws_floats,
+                                      void* stream) {
   const int rc = gat_layer_check(L);
   if (rc != EGNN_OK) return rc;
   const int64_t HC = (int64_t)L->H * L->C;
-  EGNN_CHECK_ARG(ld_go >= HC && ld_dxl >= HC);
+  EGNN_CHECK_ARG(ld_go >= (mean_heads ? (int64_t)L->C : HC) && ld_dxl >= HC);
   EGNN_CHECK_ARG((L->attn_r == nullptr) == (L->er == nullptr) && (L->er == nullptr) == (d_er == nullptr));
   if (d_attn != nullptr) EGNN_CHECK_ARG(HC <= kGatMaxHC && ws && ws_floats >= egnn_gat_layer_bwd_ws_floats(L->n, L->H, L->C));
   if (L->n == 0) return EGNN_OK;
   EGNN_CHECK_ARG(L->colptr && L->attn_l && dxl);
   EGNN_CHECK_ARG(L->nnz == 0 || (L->t_col && L->perm && att && go && d_raw));
+  // go[i,h,:] = go_scale * go[i * ld_go + h * go_hs + :]: the gradient of the head average reaches every head, scaled by 1/H
+  const int64_t go_hs = mean_heads ? 0 : L->C;
+  const float go_scale = mean_heads ? (float)(1.0 / L->H) : 1.f;
   hipStream_t st = (hipStream_t)stream;
-  const int rc2 = gat_launch_attention_bwd(L->rowptr, L->col, L->el, L->er, att, L->mult, L->xl, L->ld_xl, go, ld_go, L->C, 1.f, L->n, L->nnz,
-                                           L->H, L->C, L->negative_slope, L->src_scale, L->dst_scale, d_raw, d_er, st);
+  const int rc2 = gat_launch_attention_bwd(L->rowptr, L->col, L->el, L->er, att, L->mult, L->xl, L->ld_xl, go, ld_go, go_hs, go_scale, L->n,
+                                           L->nnz, L->H, L->C, L->negative_slope, L->src_scale, L->dst_scale, d_raw, d_er, st);
   if (rc2 != EGNN_OK) return rc2;
-  return gat_launch_aggregate_bwd(L->colptr, L->t_col, L->perm, att, L->mult, d_raw, go, ld_go, L->C, 1.f, L->xl, L->ld_xl, L->attn_l,
-                                  L->attn_r, d_er, L->n, L->nnz, L->H, L->C, L->src_scale, L->dst_scale, dxl, ld_dxl, d_attn, ws, st);
+  return gat_launch_aggregate_bwd(L->colptr, L->t_col, L->perm, att, L->mult, d_raw, go, ld_go, go_hs, go_scale, L->xl, L->ld_xl,
+                                  L->attn_l, L->attn_r, d_er, L->n, L->nnz, L->H, L->C, L->src_scale, L->dst_scale, dxl, ld_dxl, d_attn,
+                                  ws, st);
 }

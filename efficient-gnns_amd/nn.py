@@ -14,7 +14,7 @@ from torch import Tensor, nn
 from . import ops
 import os
 
-from . import _lib
+from . import _lib, ops_edge
 from .sparse import SparseTensor, _ind2ptr, csr_from_coo, gcn_norm
 
 # opt-in: the headline bench keeps the reference's per-step work (aggregate every layer every step)
@@ -205,11 +205,12 @@ class GATConv(nn.Module):
     PyG 1.6/1.7 (``lin_l.weight`` shared with ``lin_r``, ``att_l`` / ``att_r`` [1,H,C], ``bias``).
 
     Forward on the gfx950 kernels: x W on the fp32 MFMA, the 2H attention logits per node as one more small GEMM
-    (block-diagonal ``att``), scores + LeakyReLU + per-target softmax fused in ``egnn_gat_attention_fwd_f32`` (no [E,H]
-    gathers or scatter-softmax temporaries), one valued SpMM per head written straight into its column block.
-    In training mode with autograd on, the attention + aggregation is one autograd node (``ops_edge.gat_attention``) whose
-    backward runs in three HIP launches for all heads (csrc/gat.hip).  In eval mode a call that would need gradients raises:
-    the eval forward is the frozen teacher's."""
+    (``ops_edge.gat_logits``), scores + LeakyReLU + per-target softmax fused in one launch (``ops_edge.gat_coefficients``: no [E,H]
+    gathers or scatter-softmax temporaries), one valued SpMM per head written straight into its column block
+    (``ops_edge.gat_aggregate``).  In training mode with autograd on, the same three steps are one autograd node
+    (``ops_edge.gat_attention``) whose backward -- the one ``DGLGATConv`` runs too -- takes three HIP launches for all heads
+    (``egnn_gat_layer_bwd_f32``, csrc/gat.hip).  In eval mode a call that would need gradients raises: the eval forward is the
+    frozen teacher's."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True, negative_slope: float = 0.2,
                  dropout: float = 0.0, add_self_loops: bool = True, bias: bool = True, **_):
@@ -260,25 +261,13 @@ class GATConv(nn.Module):
         _lib.require_gpu(x)
         n, H, C = x.shape[0], self.heads, self.out_channels
         xl = ops.linear(x, self.lin_l.weight)                                   # [n, H*C]
-        # alpha_l[i,h] = <xl[i,h,:], att_l[h,:]> (and alpha_r) as ONE GEMM with a block-diagonal [H*C, 2H] matrix
-        blk = torch.zeros(H * C, 2 * H, dtype=torch.float32, device=x.device)
-        rows = torch.arange(H * C, device=x.device)
-        blk[rows, rows // C] = self.att_l.detach().reshape(-1)
-        blk[rows, H + rows // C] = self.att_r.detach().reshape(-1)
-        alpha = ops.matmul(xl, blk)                                             # [n, 2H]
+        alpha = ops_edge.gat_logits(xl, self.att_l.detach(), self.att_r.detach(), H, C)   # [n, 2H]
         a_src, a_dst = alpha[:, :H].contiguous(), alpha[:, H:].contiguous()
         adj = self._structure(edge_index, n)
-        rowptr, col, _ = adj.csr()
-        nnz = adj.nnz()
-        att = torch.empty(H, nnz, dtype=torch.float32, device=x.device)         # head-major: att[h] is a value array
-        _lib.check(_lib.load().egnn_gat_attention_fwd_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(a_src), _lib.ptr(a_dst), n, nnz, H,
-                                                          float(self.negative_slope), _lib.ptr(att), _lib.stream()),
-                   "egnn_gat_attention_fwd_f32")
+        att = ops_edge.gat_coefficients(adj, a_src, a_dst, self.negative_slope)
         if self.training and self.dropout > 0:
             att = torch.nn.functional.dropout(att, p=self.dropout, training=True)
-        out = torch.empty(n, H * C, dtype=torch.float32, device=x.device)
-        for h in range(H):
-            ops.spmm_raw(adj.set_value(att[h]), xl[:, h * C:(h + 1) * C], "sum", out=out[:, h * C:(h + 1) * C])
+        out = ops_edge.gat_aggregate(adj, att, xl, C)
         if not self.concat:
             out = out.view(n, H, C).mean(dim=1)
         return ops.add_bias(out, self.bias)
@@ -288,7 +277,6 @@ class GATConv(nn.Module):
         ``ops_edge.gat_attention`` (HIP backward, csrc/gat.hip), the bias through ``ops.add_bias``.  Attention dropout draws its
         mask with torch's RNG as one ``torch.rand(heads, nnz)`` per call (kept where >= p, scaled by 1 / (1 - p)), on the
         entries of the cached structure."""
-        from .ops_edge import gat_attention
         _lib.require_gpu(x)
         n = x.shape[0]
         xl = ops.linear(x, self.lin_l.weight)                                   # [n, H*C]
@@ -297,7 +285,7 @@ class GATConv(nn.Module):
         if self.dropout > 0:
             keep = torch.rand(self.heads, adj.nnz(), dtype=torch.float32, device=x.device) >= self.dropout
             mult = keep.to(torch.float32).mul_(1.0 / (1.0 - self.dropout) if self.dropout < 1 else 0.0)
-        out = gat_attention(xl, self.att_l, self.att_r, adj, self.heads, self.concat, self.negative_slope, mult)
+        out = ops_edge.gat_attention(xl, self.att_l, self.att_r, adj, self.heads, self.concat, self.negative_slope, mult)
         return ops.add_bias(out, self.bias)
 
     def __repr__(self):
@@ -311,12 +299,12 @@ class DGLGATConv(nn.Module):
     (``fc``, ``attn_l``, ``attn_r`` (absent with ``use_attn_dst=False``), ``res_fc``), so its checkpoints load.
 
     ``forward(adj, feat)``: ``adj`` = ``SparseTensor`` whose row i lists the sources of the edges j -> i (the DGL graph after
-    gat.py:56-71 ``preprocess``: ``utils.dgl_bidirected_with_self_loops``).  x W on the fp32 MFMA, ``el`` / ``er`` as one more
-    small GEMM, ``u_add_v`` + LeakyReLU + ``edge_softmax`` fused in ``egnn_gat_attention_fwd_f32``, ``u_mul_e`` + ``sum`` as
-    one valued SpMM per head; symmetric normalisation (out-degree^-1/2 on the sources, in-degree^1/2 on the result) and the
+    gat.py:56-71 ``preprocess``: ``utils.dgl_bidirected_with_self_loops``).  The steps of ``GATConv``'s forward through the same
+    helpers of ``ops_edge`` (``el`` / ``er`` = the logits GEMM, ``u_add_v`` + LeakyReLU + ``edge_softmax`` = the coefficients,
+    ``u_mul_e`` + ``sum`` = one valued SpMM per head over head blocks padded to 16 bytes); symmetric normalisation (out-degree^-1/2 on the sources, in-degree^1/2 on the result) and the
     residual projection as in the reference.  Returns [N, H, F].  In training mode with autograd on the layer is differentiable
-    (``_forward_train``: one fused launch for all heads forward, three backward; ``edge_drop`` / ``attn_drop`` / ``feat_drop`` act
-    there).  In eval mode a call that would need gradients raises: the eval forward is the frozen teacher's."""
+    (``_forward_train``: one fused launch for all heads forward, ``GATConv``'s three backward; ``edge_drop`` / ``attn_drop`` /
+    ``feat_drop`` act there).  In eval mode a call that would need gradients raises: the eval forward is the frozen teacher's."""
 
     def __init__(self, in_feats, out_feats, num_heads=1, feat_drop=0.0, attn_drop=0.0, edge_drop=0.0, negative_slope=0.2,
                  use_attn_dst=True, residual=False, activation=None, allow_zero_in_degree=False, use_symmetric_norm=False):
@@ -375,31 +363,18 @@ class DGLGATConv(nn.Module):
         if has_isolated and not self._allow_zero_in_degree:
             raise AssertionError("zero in-degree node (arxiv_dgl/models.py:167-169)")
         feat_src = ops.linear(feat, self.fc.weight)                               # [n, H*F]
-        # el[i,h] = <feat_src[i,h,:], attn_l[h,:]> (and er) as ONE GEMM with a block-diagonal [H*F, 2H] matrix
-        blk = torch.zeros(H * F_, 2 * H, dtype=torch.float32, device=feat.device)
-        rows = torch.arange(H * F_, device=feat.device)
-        blk[rows, rows // F_] = self.attn_l.detach().reshape(-1)
-        if self.attn_r is not None:
-            blk[rows, H + rows // F_] = self.attn_r.detach().reshape(-1)
-        alpha = ops.matmul(feat_src, blk)                                         # [n, 2H]; er = 0 without attn_r (copy_u)
-        el, er = alpha[:, :H].contiguous(), alpha[:, H:].contiguous()
+        alpha = ops_edge.gat_logits(feat_src, self.attn_l.detach(), None if self.attn_r is None else self.attn_r.detach(), H, F_)
+        el, er = alpha[:, :H].contiguous(), alpha[:, H:].contiguous()             # er = 0 without attn_r (copy_u)
         if self._use_symmetric_norm:
             # the reference scales the SOURCE features (and with them el) by out-degree^-1/2 but forms er from the unscaled
             # destination features (models.py:178-200: feat_dst is bound before the scaling)
             feat_src = feat_src * out_rsqrt
             el = el * out_rsqrt
-        rowptr, col, _ = adj.csr()
-        nnz = adj.nnz()
-        att = torch.empty(H, nnz, dtype=torch.float32, device=feat.device)        # head-major: att[h] is a value array
-        _lib.check(_lib.load().egnn_gat_attention_fwd_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(el), _lib.ptr(er), n, nnz, H,
-                                                          float(self.negative_slope), _lib.ptr(att), _lib.stream()),
-                   "egnn_gat_attention_fwd_f32")
+        att = ops_edge.gat_coefficients(adj, el, er, self.negative_slope)
         Fp = (F_ + 3) // 4 * 4                                                      # head blocks on 16-byte boundaries (F = 250 -> 252)
         src_heads = feat_src if Fp == F_ else torch.nn.functional.pad(feat_src.view(n, H, F_), (0, Fp - F_)).reshape(n, H * Fp)
-        out = torch.empty(n, H * Fp, dtype=torch.float32, device=feat.device)
         plain = adj.set_value(None) if adj.has_value() else adj
-        for h in range(H):
-            ops.spmm_raw(plain.set_value(att[h]), src_heads[:, h * Fp:(h + 1) * Fp], "sum", out=out[:, h * Fp:(h + 1) * Fp])
+        out = ops_edge.gat_aggregate(plain, att, src_heads, Fp)
         rst = out.view(n, H, Fp)[:, :, :F_]
         if self._use_symmetric_norm:
             rst = rst * in_sqrt.view(n, 1, 1)
@@ -421,7 +396,6 @@ class DGLGATConv(nn.Module):
         ``res_fc`` through ``ops.linear``, scores + edge softmax over the kept edges + aggregation + both symmetric-norm scales as one
         autograd node (``ops_edge.dgl_gat_attention``: one HIP launch forward, three backward, csrc/gat.hip).  ``attn_drop`` draws one
         [heads, nnz] multiplier per call (kept where >= p, scaled by 1 / (1 - p)), ``edge_drop`` one kept-entry set (``_draw_edge_keep``)."""
-        from .ops_edge import dgl_gat_attention
         _lib.require_gpu(feat)
         n, H, F_ = feat.shape[0], self._num_heads, self._out_feats
         in_sqrt, out_rsqrt, has_isolated = self._degrees(adj)
@@ -436,8 +410,8 @@ class DGLGATConv(nn.Module):
             kept = torch.rand(H, nnz, dtype=torch.float32, device=feat.device) >= self.attn_drop_p
             mult = kept.to(torch.float32).mul_(1.0 / (1.0 - self.attn_drop_p) if self.attn_drop_p < 1 else 0.0)
         r, q = (out_rsqrt, in_sqrt) if self._use_symmetric_norm else (None, None)
-        rst = dgl_gat_attention(feat_src, self.attn_l, self.attn_r, adj, H, self.negative_slope, keep=keep, mult=mult,
-                                src_scale=r, dst_scale=q)                         # [n, H, F]
+        rst = ops_edge.dgl_gat_attention(feat_src, self.attn_l, self.attn_r, adj, H, self.negative_slope, keep=keep, mult=mult,
+                                         src_scale=r, dst_scale=q)                # [n, H, F]
         if self.res_fc is not None:
             rst = rst + ops.linear(h, self.res_fc.weight).view(n, -1, F_)
         if self._activation is not None:

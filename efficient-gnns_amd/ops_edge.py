@@ -1,6 +1,7 @@
 """LSP: per-edge similarity + segment softmax loss (kernels in csrc/edge_softmax.hip, csrc/spmm.hip)."""
 from __future__ import annotations
 
+import ctypes
 import os
 
 import torch
@@ -205,100 +206,39 @@ def lsp_loss(feat: Tensor, teacher_feat: Tensor, edge_index: Tensor, kernel: str
 
 
 # ------------------------------------------------------------------------------------------------
-# GAT attention + aggregation of one GATConv with its backward (csrc/edge_softmax.hip forward, csrc/gat.hip backward)
+# GAT attention + aggregation with its backward, for nn.GATConv (PyG) and nn.DGLGATConv (the arxiv GAT teacher's layer):
+# csrc/edge_softmax.hip + csrc/spmm.hip (per-head forward), csrc/gat.hip (fused forward, the one backward)
 # ------------------------------------------------------------------------------------------------
-class _GATAttention(torch.autograd.Function):
-    """out[i,h,:] = sum_e att[h,e] mult[h,e] xl[col e,h,:] (heads concatenated, or averaged), att = the per-target softmax of
-    leaky_relu(<xl[col e,h], att_l[h]> + <xl[i,h], att_r[h]>).  Gradients for xl, att_l and att_r in three launches for all heads
-    (egnn_gat_attention_bwd_f32, egnn_gat_aggregate_bwd_f32 = source-side kernel + finalize); the averaged heads' 1/H is folded
-    into the kernels.  ``adj``: the layer's cached structure (CSR by target, value-less); the backward reads its transposed
-    structure, formed here in the forward, so nothing in the backward waits for the host."""
-
-    @staticmethod
-    def forward(ctx, xl, att_l, att_r, adj, H, C, concat, slope, mult):
-        n = xl.shape[0]
-        xl = xl.contiguous()
-        blk = torch.zeros(H * C, 2 * H, dtype=torch.float32, device=xl.device)
-        rows = torch.arange(H * C, device=xl.device)
-        blk[rows, rows // C] = att_l.reshape(-1)
-        blk[rows, H + rows // C] = att_r.reshape(-1)
-        alpha = ops.matmul(xl, blk)                                             # [n, 2H]: alpha_src | alpha_dst
-        a_src, a_dst = alpha[:, :H].contiguous(), alpha[:, H:].contiguous()
-        rowptr, col, _ = adj.csr()
-        nnz = adj.nnz()
-        lib = _lib.load()
-        att = torch.empty(H, nnz, dtype=torch.float32, device=xl.device)
-        _lib.check(lib.egnn_gat_attention_fwd_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(a_src), _lib.ptr(a_dst), n, nnz, H,
-                                                  float(slope), _lib.ptr(att), _lib.stream()), "egnn_gat_attention_fwd_f32")
-        vals = att if mult is None else att * mult
-        out = torch.empty(n, H * C, dtype=torch.float32, device=xl.device)
-        for h in range(H):
-            ops.spmm_raw(adj.set_value(vals[h]), xl[:, h * C:(h + 1) * C], "sum", out=out[:, h * C:(h + 1) * C])
-        if not concat:
-            out = out.view(n, H, C).mean(dim=1)
-        adj._transpose_meta()
-        adj.t()
-        ctx.adj, ctx.H, ctx.C, ctx.concat, ctx.slope = adj, H, C, concat, float(slope)
-        ctx.save_for_backward(xl, a_src, a_dst, att, mult, att_l, att_r)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        xl, a_src, a_dst, att, mult, att_l, att_r = ctx.saved_tensors
-        adj, H, C = ctx.adj, ctx.H, ctx.C
-        g = g.contiguous()
-        n, nnz, HC = xl.shape[0], adj.nnz(), H * C
-        ld_go, go_hs, go_scale = (HC, C, 1.0) if ctx.concat else (C, 0, 1.0 / H)
-        rowptr, col, _ = adj.csr()
-        colptr, perm = adj._transpose_meta()
-        t_col = adj.t()._col
-        lib = _lib.load()
-        d_raw = torch.empty(H, nnz, dtype=torch.float32, device=xl.device)
-        d_adst = torch.empty(n, H, dtype=torch.float32, device=xl.device)
-        _lib.check(lib.egnn_gat_attention_bwd_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(a_src), _lib.ptr(a_dst), _lib.ptr(att),
-                                                  _lib.ptr(mult), _lib.ptr(xl), HC, _lib.ptr(g), ld_go, go_hs, go_scale, n, nnz, H, C,
-                                                  ctx.slope, _lib.ptr(d_raw), _lib.ptr(d_adst), _lib.stream()),
-                   "egnn_gat_attention_bwd_f32")
-        dxl = torch.empty(n, HC, dtype=torch.float32, device=xl.device)
-        d_att = torch.empty(2, HC, dtype=torch.float32, device=xl.device)
-        nws = lib.egnn_gat_aggregate_bwd_ws_floats(n, H, C)
-        ws = torch.empty(nws, dtype=torch.float32, device=xl.device)
-        _lib.check(lib.egnn_gat_aggregate_bwd_f32(_lib.ptr(colptr), _lib.ptr(t_col), _lib.ptr(perm), _lib.ptr(att), _lib.ptr(mult),
-                                                  _lib.ptr(d_raw), _lib.ptr(g), ld_go, go_hs, go_scale, _lib.ptr(xl), HC,
-                                                  _lib.ptr(att_l), _lib.ptr(att_r), _lib.ptr(d_adst), n, nnz, H, C, _lib.ptr(dxl), HC,
-                                                  _lib.ptr(d_att), _lib.ptr(ws), nws, _lib.stream()),
-                   "egnn_gat_aggregate_bwd_f32")
-        return dxl, d_att[0].view(1, H, C), d_att[1].view(1, H, C), None, None, None, None, None, None
-
-
-def gat_attention(xl: Tensor, att_l: Tensor, att_r: Tensor, adj: SparseTensor, heads: int, concat: bool, negative_slope: float,
-                  mult: Tensor | None = None) -> Tensor:
-    """Differentiable attention + aggregation of one GATConv (``xl`` = x W^T [n, heads*C]); ``mult`` [heads, nnz]: the
-    attention-dropout multiplier (mask / (1 - p)) or None.  Returns [n, heads*C] (concat) or [n, C] (heads averaged)."""
-    _lib.require_gpu(xl)
-    H = heads
-    C = xl.shape[1] // H
-    if xl.shape[1] != H * C or att_l.numel() != H * C or att_r.numel() != H * C:
-        raise ValueError("gat_attention: xl [n, heads*C], att_l / att_r [1, heads, C]")
-    if H * C > 2048:
-        raise ValueError("gat_attention: heads * out_channels > 2048 is not supported by the backward (egnn_gat_aggregate_bwd_f32)")
-    if mult is not None:
-        mult = mult.contiguous()
-    return _GATAttention.apply(xl, att_l.contiguous(), att_r.contiguous(), adj, H, C, concat, negative_slope, mult)
-
-
-# ------------------------------------------------------------------------------------------------
-# one layer of the arxiv GAT teacher (DGL-style GATConv): fused all-heads forward + three-launch backward (csrc/gat.hip)
-# ------------------------------------------------------------------------------------------------
-def _block_diag_logits(xl: Tensor, attn_l: Tensor, attn_r: Tensor | None, H: int, C: int) -> Tensor:
-    """[n, 2H]: <xl[i,h,:], attn_l[h,:]> | <xl[i,h,:], attn_r[h,:]> (zeros without ``attn_r``) as ONE GEMM with a block-diagonal
-    [H*C, 2H] matrix."""
+def gat_logits(xl: Tensor, att_l: Tensor, att_r: Tensor | None, H: int, C: int) -> Tensor:
+    """[n, 2H]: <xl[i,h,:], att_l[h,:]> | <xl[i,h,:], att_r[h,:]> (zeros without ``att_r``) -- ``alpha_src | alpha_dst`` of GATConv,
+    ``el | er`` of DGLGATConv -- as ONE GEMM with a block-diagonal [H*C, 2H] matrix."""
     blk = torch.zeros(H * C, 2 * H, dtype=torch.float32, device=xl.device)
     rows = torch.arange(H * C, device=xl.device)
-    blk[rows, rows // C] = attn_l.reshape(-1)
-    if attn_r is not None:
-        blk[rows, H + rows // C] = attn_r.reshape(-1)
+    blk[rows, rows // C] = att_l.reshape(-1)
+    if att_r is not None:
+        blk[rows, H + rows // C] = att_r.reshape(-1)
     return ops.matmul(xl, blk)
+
+
+def gat_coefficients(adj: SparseTensor, a_src: Tensor, a_dst: Tensor, slope: float) -> Tensor:
+    """att [H, nnz] (head-major: att[h] is a value array of ``adj``): the per-target softmax of leaky_relu(a_src[col e] + a_dst[i]);
+    ``a_src`` / ``a_dst`` contiguous [n, H]."""
+    rowptr, col, _ = adj.csr()
+    n, H, nnz = a_dst.shape[0], a_dst.shape[1], adj.nnz()
+    att = torch.empty(H, nnz, dtype=torch.float32, device=a_src.device)
+    _lib.check(_lib.load().egnn_gat_attention_fwd_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(a_src), _lib.ptr(a_dst), n, nnz, H,
+                                                      float(slope), _lib.ptr(att), _lib.stream()), "egnn_gat_attention_fwd_f32")
+    return att
+
+
+def gat_aggregate(adj: SparseTensor, vals: Tensor, src: Tensor, width: int) -> Tensor:
+    """out[i, h*width:(h+1)*width] = sum_e vals[h,e] src[col e, h*width:(h+1)*width]: one valued SpMM per head, written straight into
+    its column block of the [n, H*width] result."""
+    H = vals.shape[0]
+    out = torch.empty(src.shape[0], H * width, dtype=torch.float32, device=src.device)
+    for h in range(H):
+        ops.spmm_raw(adj.set_value(vals[h]), src[:, h * width:(h + 1) * width], "sum", out=out[:, h * width:(h + 1) * width])
+    return out
 
 
 def _gat_layer_desc(adj: SparseTensor, with_transpose: bool, n, nnz, H, C, xl, el, er, attn_l, attn_r, keep, mult, r, q, slope):
@@ -316,9 +256,8 @@ def _gat_layer_desc(adj: SparseTensor, with_transpose: bool, n, nnz, H, C, xl, e
 def dgl_gat_layer_forward(xl, attn_l, attn_r, adj, H, C, slope, keep=None, mult=None, r=None, q=None):
     """(out [n, H*C], att [H, nnz], el, er) of one layer without autograd: the logits GEMM and egnn_gat_layer_fwd_f32.  ``xl``
     contiguous [n, H*C]; ``keep`` uint8 [nnz], ``mult`` float32 [H, nnz], ``r`` / ``q`` float32 [n], each or None."""
-    import ctypes
     n, nnz = xl.shape[0], adj.nnz()
-    alpha = _block_diag_logits(xl, attn_l, attn_r, H, C)
+    alpha = gat_logits(xl, attn_l, attn_r, H, C)
     el = alpha[:, :H]
     el = (el * r.view(n, 1) if r is not None else el).contiguous()      # from the scaled source features
     er = alpha[:, H:].contiguous() if attn_r is not None else None      # from the unscaled ones
@@ -330,30 +269,40 @@ def dgl_gat_layer_forward(xl, attn_l, attn_r, adj, H, C, slope, keep=None, mult=
     return out, att, el, er
 
 
-class _DGLGATAttention(torch.autograd.Function):
+class _GATAttention(torch.autograd.Function):
     """out[i,h,:] = q_i sum_e att[h,e] mult[h,e] r_{col e} xl[col e,h,:], att = the per-target softmax over the kept entries of
-    leaky_relu(<r_j xl[j,h], attn_l[h]> + <xl[i,h], attn_r[h]>) (arxiv_dgl/models.py:179-225).  Forward: the small logits GEMM and ONE
-    launch for all heads (egnn_gat_layer_fwd_f32); backward: three launches (egnn_gat_layer_bwd_f32).  The transposed structure is
-    formed in the forward, so nothing in the backward waits for the host."""
+    leaky_relu(<r_j xl[j,h], attn_l[h]> + <xl[i,h], attn_r[h]>); ``adj``: the layer's cached structure (CSR by target, value-less).
+    ``fused`` (DGLGATConv, arxiv_dgl/models.py:179-225): the logits GEMM and ONE launch for all heads (egnn_gat_layer_fwd_f32), result
+    [n, H, C].  Otherwise (GATConv: no keep / r / q): coefficients, then one valued SpMM per head; result [n, H*C], or [n, C] = the
+    head average without ``concat`` (its 1/H is folded into the backward kernels).  One backward for both, three launches for all
+    heads (egnn_gat_layer_bwd_f32); it reads the transposed structure, formed here in the forward, so nothing in it waits for the host."""
 
     @staticmethod
-    def forward(ctx, xl, attn_l, attn_r, adj, H, C, slope, keep, mult, r, q):
+    def forward(ctx, xl, attn_l, attn_r, adj, H, C, slope, mult, concat, fused, keep, r, q):
+        n = xl.shape[0]
         xl = xl.contiguous()
-        out, att, el, er = dgl_gat_layer_forward(xl, attn_l, attn_r, adj, H, C, slope, keep, mult, r, q)
+        if fused:
+            out, att, el, er = dgl_gat_layer_forward(xl, attn_l, attn_r, adj, H, C, slope, keep, mult, r, q)
+            out = out.view(n, H, C)
+        else:
+            alpha = gat_logits(xl, attn_l, attn_r, H, C)
+            el, er = alpha[:, :H].contiguous(), alpha[:, H:].contiguous()
+            att = gat_coefficients(adj, el, er, slope)
+            out = gat_aggregate(adj, att if mult is None else att * mult, xl, C)
+            if not concat:
+                out = out.view(n, H, C).mean(dim=1)
         adj._transpose_meta()
         adj.t()
-        ctx.adj, ctx.H, ctx.C, ctx.slope = adj, H, C, float(slope)
-        ctx.has_r = attn_r is not None
+        ctx.adj, ctx.H, ctx.C, ctx.slope, ctx.mean_heads = adj, H, C, float(slope), not concat
         ctx.save_for_backward(xl, el, er, att, keep, mult, r, q, attn_l, attn_r)
-        return out.view(xl.shape[0], H, C)
+        return out
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes
         xl, el, er, att, keep, mult, r, q, attn_l, attn_r = ctx.saved_tensors
         adj, H, C = ctx.adj, ctx.H, ctx.C
         n, nnz, HC = xl.shape[0], adj.nnz(), H * C
-        g = g.contiguous().view(n, HC)
+        g = g.contiguous().view(n, C if ctx.mean_heads else HC)         # averaged heads: the gradient of the head average
         lib, dev = _lib.load(), xl.device
         d_raw = torch.empty(H, nnz, dtype=torch.float32, device=dev)
         d_er = torch.empty(n, H, dtype=torch.float32, device=dev) if er is not None else None
@@ -362,11 +311,28 @@ class _DGLGATAttention(torch.autograd.Function):
         nws = lib.egnn_gat_layer_bwd_ws_floats(n, H, C)
         ws = torch.empty(nws, dtype=torch.float32, device=dev)
         desc = _gat_layer_desc(adj, True, n, nnz, H, C, xl, el, er, attn_l, attn_r, keep, mult, r, q, ctx.slope)
-        _lib.check(lib.egnn_gat_layer_bwd_f32(ctypes.byref(desc), _lib.ptr(att), _lib.ptr(g), HC, _lib.ptr(d_raw), _lib.ptr(d_er),
-                                              _lib.ptr(dxl), HC, _lib.ptr(d_attn), _lib.ptr(ws), nws, _lib.stream()),
-                   "egnn_gat_layer_bwd_f32")
-        d_r = d_attn[1].view(1, H, C) if ctx.has_r else None
-        return dxl, d_attn[0].view(1, H, C), d_r, None, None, None, None, None, None, None, None
+        _lib.check(lib.egnn_gat_layer_bwd_f32(ctypes.byref(desc), _lib.ptr(att), _lib.ptr(g), g.shape[1], int(ctx.mean_heads),
+                                              _lib.ptr(d_raw), _lib.ptr(d_er), _lib.ptr(dxl), HC, _lib.ptr(d_attn), _lib.ptr(ws), nws,
+                                              _lib.stream()), "egnn_gat_layer_bwd_f32")
+        d_r = d_attn[1].view(1, H, C) if er is not None else None
+        return (dxl, d_attn[0].view(1, H, C), d_r) + (None,) * 10
+
+
+def gat_attention(xl: Tensor, att_l: Tensor, att_r: Tensor, adj: SparseTensor, heads: int, concat: bool, negative_slope: float,
+                  mult: Tensor | None = None) -> Tensor:
+    """Differentiable attention + aggregation of one GATConv (``xl`` = x W^T [n, heads*C]); ``mult`` [heads, nnz]: the
+    attention-dropout multiplier (mask / (1 - p)) or None.  Returns [n, heads*C] (concat) or [n, C] (heads averaged)."""
+    _lib.require_gpu(xl)
+    H = heads
+    C = xl.shape[1] // H
+    if xl.shape[1] != H * C or att_l.numel() != H * C or att_r.numel() != H * C:
+        raise ValueError("gat_attention: xl [n, heads*C], att_l / att_r [1, heads, C]")
+    if H * C > 2048:
+        raise ValueError("gat_attention: heads * out_channels > 2048 is not supported by the backward (egnn_gat_layer_bwd_f32)")
+    if mult is not None:
+        mult = mult.contiguous()
+    return _GATAttention.apply(xl, att_l.contiguous(), att_r.contiguous(), adj, H, C, negative_slope, mult, concat, False,
+                               None, None, None)
 
 
 def dgl_gat_attention(xl: Tensor, attn_l: Tensor, attn_r: Tensor | None, adj: SparseTensor, heads: int, negative_slope: float,
@@ -402,5 +368,5 @@ def dgl_gat_attention(xl: Tensor, attn_l: Tensor, attn_r: Tensor | None, adj: Sp
             s = s.reshape(n).to(torch.float32).contiguous()
         scales.append(s)
     plain = adj.set_value(None) if adj.has_value() else adj
-    return _DGLGATAttention.apply(xl, attn_l.contiguous(), None if attn_r is None else attn_r.contiguous(), plain, H, C,
-                                  negative_slope, keep, mult, scales[0], scales[1])
+    return _GATAttention.apply(xl, attn_l.contiguous(), None if attn_r is None else attn_r.contiguous(), plain, H, C,
+                               negative_slope, mult, True, True, keep, scales[0], scales[1])

@@ -39,7 +39,7 @@ extern "C" {
 #define EGNN_EWORKSPACE (-3) /* caller-provided workspace too small */
 #define EGNN_EALIGN (-4)   /* pointer / leading dimension not aligned as the entry point requires */
 
-#define EGNN_ABI_VERSION 7
+#define EGNN_ABI_VERSION 8
 int egnn_abi_version(void);
 const char* egnn_error_string(int code);
 /* Number of distinct kernels-families compiled in; used by the loader's self check. */
@@ -420,60 +420,42 @@ int egnn_colsum_f32(const float* x, int64_t ld, int64_t n, int64_t C, float* out
  *   att[h,e] = exp(s - max over the row's entries) / (sum exp(..) + 1e-16)                     (edge softmax per target)
  * rowptr / col: CSR by target, int64; alpha_src [n_src,H], alpha_dst [n_rows,H] row-major; att is HEAD-major [H,nnz]
  * so that head h's values are a contiguous per-entry array for egnn_spmm_csr_*_f32 (u_mul_e_sum).  Backward:
- * egnn_gat_attention_bwd_f32 + egnn_gat_aggregate_bwd_f32 below. */
+ * egnn_gat_layer_bwd_f32 below. */
 int egnn_gat_attention_fwd_f32(const int64_t* rowptr, const int64_t* col, const float* alpha_src, const float* alpha_dst,
                                int64_t n_rows, int64_t nnz, int H, float negative_slope, float* att, void* stream);
 
-/* Backward of the GAT attention + aggregation of one GATConv in training (the PPI GAT student and teacher,
- * /root/reference/ppi_pyg/gnn.py:50-83 StudentNet, :23-47 TeacherNet trained by ppi_pyg/train_teacher.py; each step's
- * loss.backward() at gnn.py:262).  Forward per head h: att = egnn_gat_attention_fwd_f32, out[i,h,:] = sum_e att[h,e] mult[h,e]
- * xl[col e,h,:].  go[i,h,:] = go_scale * go_ptr[i * ld_go + h * go_head_stride + c]: the per-head output gradient (concatenated
- * heads: stride C, scale 1; averaged heads: stride 0, scale 1/H).  mult [H,nnz] nullable: the attention-dropout multiplier
- * (mask / (1 - p)).  csrc/gat.hip; deterministic (fixed summation orders, no atomics).
- *
- * Target side (one wavefront per target row, all heads in one launch):
- *   g_e = mult_e <go[i,h,:], xl[col e,h,:]>,  d_raw[h,e] = att_e (g_e - sum_row att g) * (s_e > 0 ? 1 : negative_slope),
- *   d_alpha_dst[i,h] = sum_row d_raw  (s_e recomputed from alpha_src / alpha_dst as the forward formed it).
- * xl [n, ld_xl >= H*C] row-major; d_raw [H,nnz]; d_alpha_dst [n_rows,H]. */
-int egnn_gat_attention_bwd_f32(const int64_t* rowptr, const int64_t* col, const float* alpha_src, const float* alpha_dst,
-                               const float* att, const float* mult, const float* xl, int64_t ld_xl, const float* go,
-                               int64_t ld_go, int64_t go_head_stride, float go_scale, int64_t n_rows, int64_t nnz, int H,
-                               int C, float negative_slope, float* d_raw, float* d_alpha_dst, void* stream);
-/* Source side over the transposed structure (colptr [n_src+1], t_col / perm [nnz]: entry q of source column j is CSR entry
- * perm[q] of target row t_col[q]; SparseTensor._transpose_meta), one wavefront per source row, all heads in one launch:
- *   d_a_src[j,h] = sum_q d_raw[h,perm q]
- *   dxl[j,h,:]   = go_scale sum_q att[h,perm q] mult[h,perm q] go[t_col q,h,:] + d_a_src[j,h] att_l[h,:] + d_alpha_dst[j,h] att_r[h,:]
- * att_r and d_alpha_dst nullable together (a layer without a target-side attention vector).  d_att [2,H*C] nullable:
- * d_att[0] = sum_j xl[j,h,:] d_a_src[j,h] (= d att_l), d_att[1] the same with d_alpha_dst (= d att_r), as per-block partials in
- * ws (egnn_gat_aggregate_bwd_ws_floats(n_src, H, C) floats) + a fixed-order finalize (a second launch); needs H*C <= 2048. */
-size_t egnn_gat_aggregate_bwd_ws_floats(int64_t n_src, int H, int C);
-int egnn_gat_aggregate_bwd_f32(const int64_t* colptr, const int64_t* t_col, const int64_t* perm, const float* att,
-                               const float* mult, const float* d_raw, const float* go, int64_t ld_go, int64_t go_head_stride,
-                               float go_scale, const float* xl, int64_t ld_xl, const float* att_l, const float* att_r,
-                               const float* d_alpha_dst, int64_t n_src, int64_t nnz, int H, int C, float* dxl, int64_t ld_dxl,
-                               float* d_att, float* ws, size_t ws_floats, void* stream);
-
-/* One layer of the arxiv GAT teacher in training and inference (the reference's own GATConv over DGL message passing,
- * /root/reference/arxiv_dgl/models.py:95-236; trained by arxiv_dgl/gat.py:116-148 with --use-norm --no-attn-dst --edge-drop=0.3,
- * arxiv_dgl/scripts/gat-teachers.sh).  The layer's operands travel as ONE descriptor, egnn_gat_layer_t, read only while the
- * call runs (it may live on the caller's stack).  Square message graph of n nodes, CSR by target (rowptr / col) and, for the
- * backward, its transposed structure (colptr / t_col / perm as in egnn_gat_aggregate_bwd_f32; not read by the forward).
- *   xl [n, ld_xl >= H*C]  the projected features fc(h), UNSCALED, read in place (any C: 16-, 8- or 4-byte aligned head blocks)
+/* One GAT layer's attention + aggregation in training, for both layer kinds; csrc/gat.hip, deterministic (fixed summation orders,
+ * no atomics).  The operands travel as ONE descriptor, egnn_gat_layer_t, read only while the call runs (it may live on the
+ * caller's stack).
+ *   - PyG <=1.7 GATConv (the PPI GAT student and teacher, /root/reference/ppi_pyg/gnn.py:50-83 StudentNet, :23-47 TeacherNet trained
+ *     by ppi_pyg/train_teacher.py): el / er are its alpha_src / alpha_dst, attn_l / attn_r its att_l / att_r; keep, src_scale
+ *     and dst_scale are NULL (read r = q = 1 below).  Its forward is egnn_gat_attention_fwd_f32 + one valued aggregation per head.
+ *   - the arxiv GAT teacher's layer (the reference's own GATConv over DGL message passing, /root/reference/arxiv_dgl/models.py:95-236;
+ *     trained by arxiv_dgl/gat.py:116-148 with --use-norm --no-attn-dst --edge-drop=0.3, arxiv_dgl/scripts/gat-teachers.sh): every
+ *     field in use; forward and backward through the two entry points below.
+ * Square message graph of n nodes, CSR by target (rowptr / col) and, for the backward, its transposed structure (colptr [n+1],
+ * t_col / perm [nnz]: entry p of source column j is CSR entry perm[p] of target row t_col[p]; SparseTensor._transpose_meta; not
+ * read by the forward).
+ *   xl [n, ld_xl >= H*C]  the projected features, UNSCALED, read in place (any C: 16-, 8- or 4-byte aligned head blocks)
  *   el [n,H]              <r_j xl[j,h,:], attn_l[h,:]> (from the scaled source features, models.py:179-196)
  *   er [n,H] nullable     <xl[i,h,:], attn_r[h,:]> (from the unscaled ones, :199-200); NULL together with attn_r (--no-attn-dst)
  *   keep [nnz] bytes, nullable      the entries edge_drop keeps (models.py:207-212); the softmax runs over the kept entries
  *   mult [H,nnz] nullable           the attention-dropout multiplier (mask / (1 - p))
  *   src_scale r [n], dst_scale q [n], nullable   out-degree^-1/2 and in-degree^1/2 of use_symmetric_norm (:179-184,220-225)
- * Forward, one launch for all heads (csrc/gat.hip):
+ * Forward, one launch for all heads:
  *   s_e = leaky_relu(el[col e,h] + er[i,h]);  att[h,e] = softmax of s over the kept entries of row i, exactly 0 at dropped
  *   entries (a row without a kept entry: all zeros);  out[i,h,:] = q_i sum_e att[h,e] mult[h,e] r_{col e} xl[col e,h,:]
  *   att [H,nnz] head-major; out [n, ld_out >= H*C].
- * Backward, three launches for all heads, fixed summation order, no atomics.  go [n, ld_go >= H*C] = d out; with go' = q_i go_i:
+ * Backward, three launches for all heads (target side: one wavefront per target row; source side: one wavefront per source row
+ * over the transposed structure; a fixed-order finalize of d_attn).  go = d out: [n, ld_go >= H*C] (mean_heads == 0), or, with
+ * mean_heads != 0, [n, ld_go >= C] = the gradient of the average over the heads, read by every head and scaled by 1/H.
+ * With go' = q_i go_i and s_e recomputed from el / er as the forward formed it:
  *   g_e = mult_e r_{col e} <go'_i, xl[col e]>;  d_raw[h,e] = att_e (g_e - sum_row att g) * (s_e > 0 ? 1 : negative_slope)
  *   d_er[i,h] = sum_row d_raw (NULL with er);  d_el[j,h] = sum_{col e = j} d_raw
  *   dxl[j,h,:] = r_j (sum_{col e = j} att_e mult_e go'_{row e} + d_el[j,h] attn_l[h,:]) + d_er[j,h] attn_r[h,:]
- *   d_attn [2,H*C] nullable: d_attn[0] = sum_j r_j xl_j d_el[j] (= d attn_l), d_attn[1] = sum_j xl_j d_er[j] (= d attn_r);
- *   needs H*C <= 2048 and ws of egnn_gat_layer_bwd_ws_floats(n, H, C) floats.  d_raw [H,nnz]: scratch of the call. */
+ *   d_attn [2,H*C] nullable: d_attn[0] = sum_j r_j xl_j d_el[j] (= d attn_l), d_attn[1] = sum_j xl_j d_er[j] (= d attn_r), as
+ *   per-block partials in ws + the finalize; needs H*C <= 2048 and ws of egnn_gat_layer_bwd_ws_floats(n, H, C) floats.
+ *   dxl [n, ld_dxl >= H*C];  d_raw [H,nnz]: scratch of the call. */
 typedef struct egnn_gat_layer {
   const int64_t* rowptr; const int64_t* col;
   const int64_t* colptr; const int64_t* t_col; const int64_t* perm;
@@ -486,8 +468,8 @@ typedef struct egnn_gat_layer {
 } egnn_gat_layer_t;
 int egnn_gat_layer_fwd_f32(const egnn_gat_layer_t* layer, float* att, float* out, int64_t ld_out, void* stream);
 size_t egnn_gat_layer_bwd_ws_floats(int64_t n, int H, int C);
-int egnn_gat_layer_bwd_f32(const egnn_gat_layer_t* layer, const float* att, const float* go, int64_t ld_go, float* d_raw, float* d_er,
-                           float* dxl, int64_t ld_dxl, float* d_attn, float* ws, size_t ws_floats, void* stream);
+int egnn_gat_layer_bwd_f32(const egnn_gat_layer_t* layer, const float* att, const float* go, int64_t ld_go, int mean_heads, float* d_raw,
+                           float* d_er, float* dxl, int64_t ld_dxl, float* d_attn, float* ws, size_t ws_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused BatchNorm1d (+ ReLU + dropout) over node rows -- SURVEY.md 8(f) rank 1; replaces the ATen BatchNorm /

@@ -43,17 +43,22 @@ def test_gat_layer_descriptor_matches_the_header_field_by_field():
                 assert _lib.SIGNATURES[name][1][i] is C.c_void_p, name
 
 
-def test_new_symbols_are_declared_exported_and_bound_and_the_abi_stays_7():
+REMOVED_SYMBOLS = ("egnn_gat_attention_bwd_f32", "egnn_gat_aggregate_bwd_f32", "egnn_gat_aggregate_bwd_ws_floats")
+
+
+def test_new_symbols_are_declared_exported_and_bound_and_the_abi_is_8():
     src = _header()
     lib = _lib.load()
     for s in NEW_SYMBOLS:
         assert re.search(r"\b%s\s*\(" % s, src), f"{s} is not declared in include/egnn_hip.h"
         assert s in _lib.SIGNATURES and hasattr(lib, s)
-    assert lib.egnn_abi_version() == 7 and re.search(r"#define\s+EGNN_ABI_VERSION\s+7\b", src)
-    # the three earlier GAT entry points keep their signatures
+    assert lib.egnn_abi_version() == 8 and re.search(r"#define\s+EGNN_ABI_VERSION\s+8\b", src)
+    # the coefficient forward keeps its signature; the positional backward pair is gone: one descriptor call for both layers
     assert len(_lib.SIGNATURES["egnn_gat_attention_fwd_f32"][1]) == 10
-    assert len(_lib.SIGNATURES["egnn_gat_attention_bwd_f32"][1]) == 20
-    assert len(_lib.SIGNATURES["egnn_gat_aggregate_bwd_f32"][1]) == 25
+    assert len(_lib.SIGNATURES["egnn_gat_layer_bwd_f32"][1]) == 13
+    whole = open(os.path.join(ROOT, "include", "egnn_hip.h")).read()
+    for s in REMOVED_SYMBOLS:
+        assert s not in _lib.SIGNATURES and s not in whole and not hasattr(lib, s), s
 
 
 def _desc(p, **kw):
@@ -67,17 +72,18 @@ def test_gat_layer_entry_points_refuse_bad_arguments_without_a_gpu():
     lib = _lib.load()
     buf = C.create_string_buffer(4096)
     p = C.addressof(buf)
-    assert lib.egnn_gat_layer_bwd_ws_floats(2, 2, 5) == lib.egnn_gat_aggregate_bwd_ws_floats(2, 2, 5) == 20
+    assert lib.egnn_gat_layer_bwd_ws_floats(2, 2, 5) == 20
     assert lib.egnn_gat_layer_bwd_ws_floats(-1, 2, 5) == 0
 
     def fwd(att=p, out=p, ld_out=10, **kw):
         return lib.egnn_gat_layer_fwd_f32(C.byref(_desc(p, **kw)), att, out, ld_out, None)
 
-    def bwd(att=p, go=p, ld_go=10, d_raw=p, d_er=p, dxl=p, ld_dxl=10, d_attn=p, ws=p, nws=20, **kw):
-        return lib.egnn_gat_layer_bwd_f32(C.byref(_desc(p, **kw)), att, go, ld_go, d_raw, d_er, dxl, ld_dxl, d_attn, ws, nws, None)
+    def bwd(att=p, go=p, ld_go=10, mean_heads=0, d_raw=p, d_er=p, dxl=p, ld_dxl=10, d_attn=p, ws=p, nws=20, **kw):
+        return lib.egnn_gat_layer_bwd_f32(C.byref(_desc(p, **kw)), att, go, ld_go, mean_heads, d_raw, d_er, dxl, ld_dxl, d_attn, ws, nws,
+                                          None)
 
     assert lib.egnn_gat_layer_fwd_f32(None, p, p, 10, None) == EINVAL
-    assert lib.egnn_gat_layer_bwd_f32(None, p, p, 10, p, p, p, 10, p, p, 20, None) == EINVAL
+    assert lib.egnn_gat_layer_bwd_f32(None, p, p, 10, 0, p, p, p, 10, p, p, 20, None) == EINVAL
     for bad in (dict(n=-1), dict(nnz=-1), dict(H=0), dict(H=65), dict(C=0), dict(ld_xl=9), dict(rowptr=None), dict(col=None),
                 dict(xl=None), dict(el=None)):
         assert fwd(**bad) == EINVAL, bad
@@ -86,7 +92,8 @@ def test_gat_layer_entry_points_refuse_bad_arguments_without_a_gpu():
         assert fwd(**bad) == EINVAL, bad
     for bad in (dict(ld_go=9), dict(ld_dxl=9), dict(attn_r=None), dict(er=None), dict(d_er=None), dict(nws=19), dict(ws=None),
                 dict(colptr=None), dict(attn_l=None), dict(dxl=None), dict(perm=None), dict(t_col=None), dict(d_raw=None),
-                dict(go=None), dict(att=None), dict(H=4, C=1024, ld_xl=4096, ld_go=4096, ld_dxl=4096, nws=1 << 20)):
+                dict(go=None), dict(att=None), dict(H=4, C=1024, ld_xl=4096, ld_go=4096, ld_dxl=4096, nws=1 << 20),
+                dict(mean_heads=1, ld_go=4)):
         assert bwd(**bad) == EINVAL, bad
     assert fwd(n=0) == 0 and bwd(n=0) == 0                            # nothing to do, nothing launched
 

@@ -23,14 +23,14 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(egnn_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_library_exports_every_declared_symbol_of_abi_7():
+def test_library_exports_every_declared_symbol_of_abi_8():
     syms = declared_symbols()
     assert len(syms) >= 30
     lib = ctypes.CDLL(E._lib.LIB_PATH)
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/egnn_hip.h but not exported"
     assert set(syms) == set(E._lib.SIGNATURES), "ctypes table and header disagree"
-    assert E._lib.load().egnn_abi_version() == 7
+    assert E._lib.load().egnn_abi_version() == 8
     assert "gfx950" in E._lib.build_info()
     assert E._lib.load().egnn_error_string(-3) == b"workspace too small"
 

@@ -90,7 +90,8 @@ def check_layer(F_in, H, C, concat, sparse_input, add_self_loops=True, seed=0):
 
 
 @pytest.mark.parametrize("sparse_input", [False, True], ids=["edge_index", "SparseTensor"])
-@pytest.mark.parametrize("H,C,concat", [(4, 256, True), (6, 121, False), (2, 68, True), (2, 68, False), (1, 7, True), (3, 5, True)])
+@pytest.mark.parametrize("H,C,concat", [(4, 256, True), (6, 121, False), (2, 68, True), (2, 68, False), (1, 7, True), (3, 5, True),
+                                        (3, 5, False), (2, 8, False)])   # averaged heads at the smallest scalar / float4 shapes
 def test_gatconv_gradients_match_oracle(H, C, concat, sparse_input):
     pc = check_layer(24, H, C, concat, sparse_input)
     adj = pc._structure(gat_graph(420).to(DEV) if not sparse_input else E.to_sparse_tensor(gat_graph(420).to(DEV), 420), 420)
@@ -152,14 +153,15 @@ def test_gatconv_attention_dropout_gradients_on_the_regenerated_mask(H, C, conca
 def test_gatconv_backward_is_deterministic():
     n = 420
     ei = gat_graph(n, seed=7).to(DEV)
-    g = torch.Generator().manual_seed(8)
-    x, w = torch.randn(n, 64, generator=g).to(DEV), torch.randn(n, 4 * 256, generator=g).to(DEV)
-    _, pc = layer_pair(64, 4, 256, True)
-    a = run_layer(pc, x, ei, w)
-    b = run_layer(pc, x, ei, w)
-    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
-    for k in GRADS:
-        assert torch.equal(a[2][k], b[2][k]), k
+    for H, C, concat in ((4, 256, True), (6, 121, False)):         # concatenated heads, and averaged heads on the scalar path
+        g = torch.Generator().manual_seed(8)
+        x, w = torch.randn(n, 64, generator=g).to(DEV), torch.randn(n, H * C if concat else C, generator=g).to(DEV)
+        _, pc = layer_pair(64, H, C, concat)
+        a = run_layer(pc, x, ei, w)
+        b = run_layer(pc, x, ei, w)
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+        for k in GRADS:
+            assert torch.equal(a[2][k], b[2][k]), (H, C, concat, k)
 
 
 def test_gatconv_eval_mode_still_refuses_gradients():

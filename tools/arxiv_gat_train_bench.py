@@ -3,7 +3,7 @@
 script-of-record configuration of arxiv_dgl/scripts/gat-teachers.sh: --use-norm --use-labels --n-label-iters=1 --no-attn-dst
 --edge-drop=0.3 --input-drop=0.25, RMSprop) on ``data.arxiv_like`` at full size, and -- in the same process, with HIP events -- the
 fused layer forward (egnn_gat_layer_fwd_f32) next to the launch sequence the inference forward makes for the same layer
-(egnn_gat_attention_fwd_f32, the source scaling, the [N, H*250] -> [N, H*252] pad, H valued SpMMs, the target scaling).
+(ops_edge.gat_coefficients, the source scaling, the [N, H*250] -> [N, H*252] pad, ops_edge.gat_aggregate, the target scaling).
 Prints one JSON line.
 
   --steps K      timed training steps (after --warmup W untimed ones)
@@ -24,7 +24,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (cap_cpu_threads)
 import efficient_gnns_amd.data as D  # noqa: E402
 import efficient_gnns_amd.models as PM  # noqa: E402
-from efficient_gnns_amd import _lib, ops, ops_edge  # noqa: E402
+from efficient_gnns_amd import _lib, ops_edge  # noqa: E402
 from efficient_gnns_amd.utils import dgl_bidirected_with_self_loops  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -97,11 +97,10 @@ in_sqrt, out_rsqrt, _ = conv._degrees(adj)
 r, q = out_rsqrt.reshape(n).contiguous(), in_sqrt.reshape(n).contiguous()
 attn_l = conv.attn_l.detach()
 nnz = adj.nnz()
-rowptr, col, _ = adj.csr()
 plain = adj.set_value(None) if adj.has_value() else adj
 conv.edge_drop = 0.3
 keep = conv._draw_edge_keep(nnz, dev).to(torch.uint8)
-el = (ops_edge._block_diag_logits(xl, attn_l, None, H, Fh)[:, :H] * out_rsqrt).contiguous()
+el = (ops_edge.gat_logits(xl, attn_l, None, H, Fh)[:, :H] * out_rsqrt).contiguous()
 er = torch.zeros(n, H, device=dev)
 
 
@@ -116,15 +115,11 @@ def fused(keep_mask):
 
 def sequence():
     """nn.DGLGATConv.forward (eval) from the attention launch on: attention, scaled source copy, pad, H SpMMs, target scale."""
-    att = torch.empty(H, nnz, dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().egnn_gat_attention_fwd_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(el), _lib.ptr(er), n, nnz, H, 0.2,
-                                                      _lib.ptr(att), _lib.stream()), "att")
+    att = ops_edge.gat_coefficients(adj, el, er, 0.2)
     src = xl * out_rsqrt
     Fp = (Fh + 3) // 4 * 4
     src_heads = F.pad(src.view(n, H, Fh), (0, Fp - Fh)).reshape(n, H * Fp)
-    out = torch.empty(n, H * Fp, dtype=torch.float32, device=dev)
-    for h in range(H):
-        ops.spmm_raw(plain.set_value(att[h]), src_heads[:, h * Fp:(h + 1) * Fp], "sum", out=out[:, h * Fp:(h + 1) * Fp])
+    out = ops_edge.gat_aggregate(plain, att, src_heads, Fp)
     return out.view(n, H, Fp)[:, :, :Fh] * in_sqrt.view(n, 1, 1)
 
 
