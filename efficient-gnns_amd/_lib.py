@@ -37,20 +37,29 @@ class GatLayer(C.Structure):
                 ("negative_slope", _f32)]
 
 
+class Spmm(C.Structure):
+    """egnn_spmm_t of include/egnn_hip.h, field for field: the operands of one neighbour aggregation, shared by its three schedules and
+    the combine step (the epilogue fields addend .. flags are the block schedule's and the combine step's)."""
+    _fields_ = [("n_rows", _i64), ("n_src", _i64), ("K", _i64),
+                ("rowptr", _p), ("col", _p), ("index_bits", _i32),
+                ("val", _p), ("src_scale", _p), ("bias", _p),
+                ("X", _p), ("ldx", _i64), ("Y", _p), ("ldy", _i64), ("reduce", _i32),
+                ("addend", _p), ("ld_addend", _i64), ("stat_part", _p), ("stat_shift", _p), ("flags", _i32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/egnn_hip.h declares
 SIGNATURES = {
     "egnn_abi_version": (_i32, []),
     "egnn_error_string": (C.c_char_p, [_i32]),
     "egnn_build_info": (_i32, [C.c_char_p, _sz]),
-    "egnn_spmm_csr_f32": (_i32, [_i64, _i64, _i64, _p, _p, _i32, _p, _p, _p, _p, _i64, _p, _i64, _i32, _p, _p, _i64, _p, _i64, _p, _i64, _p]),
-    "egnn_spmm_csr_seg_f32": (_i32, [_i64, _i64, _i64, _p, _p, _i32, _p, _p, _p, _p, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _i64, _p, _i64, _p]),
-    "egnn_spmm_csr_blk_f32": (_i32, [_i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _i64, _p, _p, _i64, _p,
-                                     _p, _i64, _p, _p, _i32, _p]),
+    "egnn_spmm_csr_f32": (_i32, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p]),
+    "egnn_spmm_csr_seg_f32": (_i32, [_p, _p, _i64, _p, _p, _i64, _p, _i64, _p]),
+    "egnn_spmm_csr_blk_f32": (_i32, [_p, _i32, _i32, _p, _i64, _p, _p, _i64, _p, _p]),
     "egnn_spmm_blk_stat_rows": (_i64, [_i64, _i32, _i32]),
     "egnn_spmm_blk_window_i32": (_i32, [_p, _p, _i64, _i32, _p, _i64, _p, _p]),
     "egnn_bn_stats_merge_ws_floats": (_sz, [_i64]),
     "egnn_bn_stats_merge_f32": (_i32, [_p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _sz, _p]),
-    "egnn_spmm_combine_f32": (_i32, [_i64, _i64, _p, _i32, _p, _p, _i64, _i32, _p, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i32, _p]),
+    "egnn_spmm_combine_f32": (_i32, [_p, _p, _p, _i64, _p, _i64, _p]),
     "egnn_spmm_csr_max_bwd_f32": (_i32, [_i64, _i64, _p, _i32, _p, _p, _p, _i64, _p, _i64, _p]),
     "egnn_spmm_algorithmic_bytes": (_i64, [_i64, _i64, _i64, _i64, _i32, _i32]),
     "egnn_csr_from_coo_ws_bytes": (_sz, [_i64, _i64, _i32]),
@@ -161,7 +170,7 @@ def load() -> C.CDLL:
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype, fn.argtypes = res, args
-    if lib.egnn_abi_version() != 8:
+    if lib.egnn_abi_version() != 9:
         raise HipExtensionError("libegnn_hip.so ABI version mismatch")
     _lib = lib
     return lib

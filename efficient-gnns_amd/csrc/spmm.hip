@@ -15,7 +15,7 @@
 //   * rows longer than `long_threshold` are reduced by a whole 1024-thread workgroup whose 16 waves
 //     each own a contiguous chunk and are combined through LDS in a fixed order (bit-stable);
 //   * fp32 accumulation order is fixed (lane-strided, then an xor tree), no atomics.
-#include "common.h"
+#include "spmm_desc.h"
 
 namespace {
 
@@ -515,18 +515,38 @@ int launch(SpmmArgs<IdxT> a, const RowPlan& plan, hipStream_t st) {
   return egnn_launch_status();
 }
 
+// The kernel arguments of a descriptor, by field name: the operands of the `parts` the caller reads; everything a launcher fills
+// in later (row list, segments, partial sums, slice geometry) and every part not read stays zero.
 template <typename IdxT>
-int dispatch(SpmmArgs<IdxT> a, int reduce, const RowPlan& plan, hipStream_t st) {
+SpmmArgs<IdxT> spmm_args(const egnn_spmm_t& op, unsigned parts) {
+  SpmmArgs<IdxT> a{};
+  a.n_rows = op.n_rows; a.K = op.K; a.rowptr = (const IdxT*)op.rowptr;
+  a.bias = op.bias; a.Y = op.Y; a.ldy = op.ldy; a.mean = op.reduce == EGNN_MEAN;
+  if (parts & kSpmmGather) {
+    a.col = (const IdxT*)op.col; a.val = op.val; a.src_scale = op.src_scale; a.X = op.X; a.ldx = op.ldx;
+  }
+  if (parts & kSpmmEpilogue) {   // the combine kernel's
+    a.addend = op.addend; a.ld_add = op.ld_addend; a.stat_part = op.stat_part; a.stat_shift = op.stat_shift;
+    a.relu = (op.flags & 8) ? 1 : 0;
+  }
+  return a;
+}
+
+template <typename IdxT>
+int dispatch(const egnn_spmm_t& op, int64_t* argmax, const RowPlan& plan, hipStream_t st) {
+  SpmmArgs<IdxT> a = spmm_args<IdxT>(op, kSpmmGather);
+  a.argmax = argmax;
   const bool vec4 = (a.K % 4 == 0) && (a.ldx % 4 == 0) && (a.ldy % 4 == 0) && egnn_aligned16(a.X) && egnn_aligned16(a.Y);
-  if (reduce == EGNN_MAX) return vec4 ? launch<IdxT, 4, true>(a, plan, st) : launch<IdxT, 1, true>(a, plan, st);
+  if (op.reduce == EGNN_MAX) return vec4 ? launch<IdxT, 4, true>(a, plan, st) : launch<IdxT, 1, true>(a, plan, st);
   return vec4 ? launch<IdxT, 4, false>(a, plan, st) : launch<IdxT, 1, false>(a, plan, st);
 }
 
 // segment schedule: every row is one or more entry ranges of at most ~64 entries, all of them walked by the
 // sub-group-per-row kernel; rows with several ranges are finished by spmm_combine_kernel
 template <typename IdxT>
-int launch_segments(SpmmArgs<IdxT> a, const int64_t* seg, int64_t n_seg, const int64_t* crow, const int64_t* cptr, int64_t n_comb,
+int launch_segments(const egnn_spmm_t& op, const int64_t* seg, int64_t n_seg, const int64_t* crow, const int64_t* cptr, int64_t n_comb,
                     float* partial, hipStream_t st) {
+  SpmmArgs<IdxT> a = spmm_args<IdxT>(op, kSpmmGather);
   const int64_t kv = a.K / 4;
   if (kv % 8 == 0) {
     a.logG = 3;
@@ -559,6 +579,19 @@ int launch_segments(SpmmArgs<IdxT> a, const int64_t* seg, int64_t n_seg, const i
   return egnn_launch_status();
 }
 
+// the combine step on its own (the hub rows of the row-block schedule): the epilogue of the descriptor applies, no entry is read
+template <typename IdxT>
+int launch_combine(const egnn_spmm_t& op, const int64_t* crow, const int64_t* cptr, int64_t n_comb, const float* partial,
+                   int64_t stat_base, hipStream_t st) {
+  SpmmArgs<IdxT> a = spmm_args<IdxT>(op, kSpmmEpilogue);
+  a.P = const_cast<float*>(partial);
+  a.stat_base = stat_base;
+  const int64_t kv = a.K / 4;
+  const int kvp_log = ilog2_ceil(kv < 256 ? kv : 256);
+  hipLaunchKernelGGL((spmm_combine_kernel<IdxT>), dim3((unsigned)n_comb), dim3(256), 0, st, a, crow, cptr, kvp_log);
+  return egnn_launch_status();
+}
+
 template <typename IdxT>
 __global__ void spmm_max_bwd_kernel(int64_t total, int64_t K, const IdxT* col, const float* val, const int64_t* argmax,
                                     const float* dY, int64_t ldy, float* dX, int64_t ldx) {
@@ -574,86 +607,54 @@ __global__ void spmm_max_bwd_kernel(int64_t total, int64_t K, const IdxT* col, c
 
 }  // namespace
 
-extern "C" int egnn_spmm_csr_f32(int64_t n_rows, int64_t n_src, int64_t K, const void* rowptr, const void* col,
-                                 int index_bits, const float* val, const float* src_scale, const float* bias, const float* X,
-                                 int64_t ldx, float* Y, int64_t ldy, int reduce, int64_t* argmax, const int64_t* short_rows,
-                                 int64_t n_short, const int64_t* mid_rows, int64_t n_mid, const int64_t* long_rows,
-                                 int64_t n_long, void* stream) {
-  EGNN_CHECK_ARG(n_rows >= 0 && n_src >= 0 && K >= 0 && ldx >= K && ldy >= K);
-  EGNN_CHECK_ARG(index_bits == 32 || index_bits == 64);
-  EGNN_CHECK_ARG(reduce == EGNN_SUM || reduce == EGNN_MEAN || reduce == EGNN_MAX);
-  if (n_rows == 0 || K == 0) return EGNN_OK;
-  EGNN_CHECK_ARG(rowptr && col && X && Y);
-  EGNN_CHECK_ARG(reduce != EGNN_MAX || argmax != nullptr);
-  EGNN_CHECK_ARG(bias == nullptr || (reduce != EGNN_MAX && (K % 4 != 0 || egnn_aligned16(bias))));
+extern "C" int egnn_spmm_csr_f32(const egnn_spmm_t* op, int64_t* argmax, const int64_t* short_rows, int64_t n_short,
+                                 const int64_t* mid_rows, int64_t n_mid, const int64_t* long_rows, int64_t n_long, void* stream) {
+  const int rc = spmm_check(op, kSpmmGather, /*max_ok=*/true);
+  if (rc != EGNN_OK) return rc;
+  const int64_t K = op->K;
+  if (op->n_rows == 0 || K == 0) return EGNN_OK;
+  EGNN_CHECK_ARG(op->rowptr && op->col && op->X && op->Y);
+  EGNN_CHECK_ARG(op->reduce != EGNN_MAX || argmax != nullptr);
+  EGNN_CHECK_ARG(op->bias == nullptr || (op->reduce != EGNN_MAX && (K % 4 != 0 || egnn_aligned16(op->bias))));
   EGNN_CHECK_ARG(n_short >= 0 && n_mid >= 0 && n_long >= 0);
   EGNN_CHECK_ARG((n_short == 0 || short_rows) && (n_mid == 0 || mid_rows) && (n_long == 0 || long_rows));
   const bool planned = short_rows || mid_rows || long_rows;
-  EGNN_CHECK_ARG(!planned || n_short + n_mid + n_long <= n_rows);
+  EGNN_CHECK_ARG(!planned || n_short + n_mid + n_long <= op->n_rows);
   const RowPlan plan{short_rows, n_short, mid_rows, n_mid, long_rows, n_long};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (index_bits == 32) {
-    SpmmArgs<int32_t> a{n_rows, K, (const int32_t*)rowptr, (const int32_t*)col, val, src_scale, bias, X, ldx, Y, ldy,
-                        reduce == EGNN_MEAN, argmax, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0};
-    return dispatch(a, reduce, plan, st);
-  }
-  SpmmArgs<int64_t> a{n_rows, K, (const int64_t*)rowptr, (const int64_t*)col, val, src_scale, bias, X, ldx, Y, ldy,
-                      reduce == EGNN_MEAN, argmax, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0};
-  return dispatch(a, reduce, plan, st);
+  return op->index_bits == 32 ? dispatch<int32_t>(*op, argmax, plan, st) : dispatch<int64_t>(*op, argmax, plan, st);
 }
 
-extern "C" int egnn_spmm_csr_seg_f32(int64_t n_rows, int64_t n_src, int64_t K, const void* rowptr, const void* col, int index_bits,
-                                     const float* val, const float* src_scale, const float* bias, const float* X, int64_t ldx,
-                                     float* Y, int64_t ldy, int reduce, const int64_t* seg, int64_t n_seg, const int64_t* comb_rows,
+extern "C" int egnn_spmm_csr_seg_f32(const egnn_spmm_t* op, const int64_t* seg, int64_t n_seg, const int64_t* comb_rows,
                                      const int64_t* comb_ptr, int64_t n_comb, float* partial, int64_t partial_slots, void* stream) {
-  EGNN_CHECK_ARG(n_rows >= 0 && n_src >= 0 && K >= 0 && ldx >= K && ldy >= K);
-  EGNN_CHECK_ARG(index_bits == 32 || index_bits == 64);
-  EGNN_CHECK_ARG(reduce == EGNN_SUM || reduce == EGNN_MEAN);
-  if (n_rows == 0 || K == 0) return EGNN_OK;
-  EGNN_CHECK_ARG(rowptr && col && X && Y && n_seg >= 0 && n_comb >= 0 && partial_slots >= 0);
+  const int rc = spmm_check(op, kSpmmGather);
+  if (rc != EGNN_OK) return rc;
+  if (op->n_rows == 0 || op->K == 0) return EGNN_OK;
+  EGNN_CHECK_ARG(op->rowptr && op->col && op->X && op->Y && n_seg >= 0 && n_comb >= 0 && partial_slots >= 0);
   EGNN_CHECK_ARG((n_seg == 0 || seg) && (n_comb == 0 || (comb_rows && comb_ptr && partial)));
-  if (K % 4 != 0 || ldx % 4 != 0 || ldy % 4 != 0 || !egnn_aligned16(X) || !egnn_aligned16(Y) || (bias && !egnn_aligned16(bias)) ||
-      (partial && !egnn_aligned16(partial)))
+  if (op->K % 4 != 0 || op->ldx % 4 != 0 || op->ldy % 4 != 0 || !egnn_aligned16(op->X) || !egnn_aligned16(op->Y) ||
+      (op->bias && !egnn_aligned16(op->bias)) || (partial && !egnn_aligned16(partial)))
     return EGNN_EALIGN;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (index_bits == 32) {
-    SpmmArgs<int32_t> a{n_rows, K, (const int32_t*)rowptr, (const int32_t*)col, val, src_scale, bias, X, ldx, Y, ldy,
-                        reduce == EGNN_MEAN, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0};
-    return launch_segments(a, seg, n_seg, comb_rows, comb_ptr, n_comb, partial, st);
-  }
-  SpmmArgs<int64_t> a{n_rows, K, (const int64_t*)rowptr, (const int64_t*)col, val, src_scale, bias, X, ldx, Y, ldy,
-                      reduce == EGNN_MEAN, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0};
-  return launch_segments(a, seg, n_seg, comb_rows, comb_ptr, n_comb, partial, st);
+  return op->index_bits == 32 ? launch_segments<int32_t>(*op, seg, n_seg, comb_rows, comb_ptr, n_comb, partial, st)
+                              : launch_segments<int64_t>(*op, seg, n_seg, comb_rows, comb_ptr, n_comb, partial, st);
 }
 
-// The combine step on its own (the hub rows of the row-block schedule, egnn_spmm_csr_blk_f32): Y[r] = (sum of the row's
-// partial slots, in slot order) * inv + bias; optionally one statistics partial row per combined row.
-extern "C" int egnn_spmm_combine_f32(int64_t n_rows, int64_t K, const void* rowptr, int index_bits, const float* bias, float* Y,
-                                     int64_t ldy, int reduce, const int64_t* comb_rows, const int64_t* comb_ptr, int64_t n_comb,
-                                     const float* partial, const float* addend, int64_t ld_addend, float* stat_part, int64_t stat_base,
-                                     const float* stat_shift, int flags, void* stream) {
-  EGNN_CHECK_ARG(n_rows >= 0 && K >= 0 && ldy >= K && n_comb >= 0 && stat_base >= 0);
-  EGNN_CHECK_ARG(index_bits == 32 || index_bits == 64);
-  EGNN_CHECK_ARG(reduce == EGNN_SUM || reduce == EGNN_MEAN);
+extern "C" int egnn_spmm_combine_f32(const egnn_spmm_t* op, const int64_t* comb_rows, const int64_t* comb_ptr, int64_t n_comb,
+                                     const float* partial, int64_t stat_base, void* stream) {
+  const int rc = spmm_check(op, kSpmmEpilogue);
+  if (rc != EGNN_OK) return rc;
+  EGNN_CHECK_ARG(n_comb >= 0 && stat_base >= 0);
+  const int64_t K = op->K;
   if (n_comb == 0 || K == 0) return EGNN_OK;
-  EGNN_CHECK_ARG(rowptr && Y && comb_rows && comb_ptr && partial && n_comb <= 0x7fffffffLL);
-  if (K % 4 != 0 || ldy % 4 != 0 || !egnn_aligned16(Y) || !egnn_aligned16(partial) || (bias && !egnn_aligned16(bias)) ||
-      (stat_part && !egnn_aligned16(stat_part)) || (stat_shift && !egnn_aligned16(stat_shift)) ||
-      (addend && (!egnn_aligned16(addend) || ld_addend % 4 != 0 || ld_addend < K)))
+  EGNN_CHECK_ARG(op->rowptr && op->Y && comb_rows && comb_ptr && partial && n_comb <= 0x7fffffffLL);
+  if (K % 4 != 0 || op->ldy % 4 != 0 || !egnn_aligned16(op->Y) || !egnn_aligned16(partial) || (op->bias && !egnn_aligned16(op->bias)) ||
+      (op->stat_part && !egnn_aligned16(op->stat_part)) || (op->stat_shift && !egnn_aligned16(op->stat_shift)) ||
+      (op->addend && (!egnn_aligned16(op->addend) || op->ld_addend % 4 != 0 || op->ld_addend < K)))
     return EGNN_EALIGN;
-  const int64_t kv = K / 4;
-  const int kvp_log = ilog2_ceil(kv < 256 ? kv : 256);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (index_bits == 32) {
-    SpmmArgs<int32_t> a{n_rows, K, (const int32_t*)rowptr, nullptr, nullptr, nullptr, bias, nullptr, 0, Y, ldy, reduce == EGNN_MEAN, nullptr,
-                        nullptr, 0, nullptr, const_cast<float*>(partial), addend, ld_addend, stat_part, stat_shift, stat_base, (flags & 8) ? 1 : 0, 0, 0, 0};
-    hipLaunchKernelGGL((spmm_combine_kernel<int32_t>), dim3((unsigned)n_comb), dim3(256), 0, st, a, comb_rows, comb_ptr, kvp_log);
-  } else {
-    SpmmArgs<int64_t> a{n_rows, K, (const int64_t*)rowptr, nullptr, nullptr, nullptr, bias, nullptr, 0, Y, ldy, reduce == EGNN_MEAN, nullptr,
-                        nullptr, 0, nullptr, const_cast<float*>(partial), addend, ld_addend, stat_part, stat_shift, stat_base, (flags & 8) ? 1 : 0, 0, 0, 0};
-    hipLaunchKernelGGL((spmm_combine_kernel<int64_t>), dim3((unsigned)n_comb), dim3(256), 0, st, a, comb_rows, comb_ptr, kvp_log);
-  }
-  return egnn_launch_status();
+  return op->index_bits == 32 ? launch_combine<int32_t>(*op, comb_rows, comb_ptr, n_comb, partial, stat_base, st)
+                              : launch_combine<int64_t>(*op, comb_rows, comb_ptr, n_comb, partial, stat_base, st);
 }
 
 extern "C" int egnn_spmm_csr_max_bwd_f32(int64_t n_rows, int64_t K, const void* col, int index_bits, const float* val,

@@ -22,7 +22,7 @@
 //     Y disappears.  (Measured alternatives: a workgroup-level reduction costs a barrier per 32 rows, +25 % kernel time;
 //     re-reading the block from L2 likewise.)
 // Accumulation order is fixed by the schedule => run-to-run bit-stable.
-#include "common.h"
+#include "spmm_desc.h"
 
 namespace {
 
@@ -479,28 +479,33 @@ extern "C" int egnn_spmm_blk_window_i32(const int32_t* rowptr, const int32_t* co
   return egnn_launch_status();
 }
 
-extern "C" int egnn_spmm_csr_blk_f32(int64_t n_rows, int64_t n_src, int64_t K, const int32_t* rowptr, const int32_t* col,
-                                     const float* val, const float* src_scale, const float* bias, const float* X, int64_t ldx,
-                                     float* Y, int64_t ldy, int reduce, int seg_max, int rows_per_blk, const int32_t* blk_ptr,
-                                     int64_t n_blk, const int32_t* win, const int32_t* hub_seg, int64_t n_hub_seg, float* partial,
-                                     const float* addend, int64_t ld_addend, float* stat_part, const float* stat_shift, int flags,
-                                     void* stream) {
-  EGNN_CHECK_ARG(n_rows >= 0 && n_src >= 0 && K >= 0 && ldx >= K && ldy >= K);
-  EGNN_CHECK_ARG(reduce == EGNN_SUM || reduce == EGNN_MEAN);
+extern "C" int egnn_spmm_csr_blk_f32(const egnn_spmm_t* op, int seg_max, int rows_per_blk, const int32_t* blk_ptr, int64_t n_blk,
+                                     const int32_t* win, const int32_t* hub_seg, int64_t n_hub_seg, float* partial, void* stream) {
+  const int rc = spmm_check(op, kSpmmGather | kSpmmEpilogue);
+  if (rc != EGNN_OK) return rc;
   EGNN_CHECK_ARG(rows_per_blk > 0 && rows_per_blk % 32 == 0 && seg_max > 0 && n_hub_seg >= 0);
+  const int64_t n_rows = op->n_rows, K = op->K;
   if (n_rows == 0 || K == 0) return EGNN_OK;
-  EGNN_CHECK_ARG(rowptr && col && X && Y && (n_hub_seg == 0 || (hub_seg && partial)));
-  if (K % 4 != 0 || ldx % 4 != 0 || ldy % 4 != 0 || !egnn_aligned16(X) || !egnn_aligned16(Y) || (bias && !egnn_aligned16(bias)) ||
-      (partial && !egnn_aligned16(partial)) || (addend && (!egnn_aligned16(addend) || ld_addend % 4 != 0 || ld_addend < K)))
+  EGNN_CHECK_ARG(op->rowptr && op->col && op->X && op->Y && (n_hub_seg == 0 || (hub_seg && partial)));
+  if (op->index_bits != 32) return EGNN_EALIGN;   // int32 indices only: the host uses the schedules of spmm.hip
+  if (K % 4 != 0 || op->ldx % 4 != 0 || op->ldy % 4 != 0 || !egnn_aligned16(op->X) || !egnn_aligned16(op->Y) ||
+      (op->bias && !egnn_aligned16(op->bias)) || (partial && !egnn_aligned16(partial)) ||
+      (op->addend && (!egnn_aligned16(op->addend) || op->ld_addend % 4 != 0 || op->ld_addend < K)))
     return EGNN_EALIGN;
-  const uint64_t xb = (uint64_t)n_src * (uint64_t)ldx * 4ull;
+  const uint64_t xb = (uint64_t)op->n_src * (uint64_t)op->ldx * 4ull;
   if (xb > 0x7FFFFFFFull) return EGNN_EALIGN;  // 32-bit descriptor offsets: the host uses the 64-bit kernels of spmm.hip
   if (blk_ptr == nullptr) n_blk = (n_rows + rows_per_blk - 1) / rows_per_blk;
   EGNN_CHECK_ARG(n_blk > 0);
   const bool lds = win != nullptr;
-  EGNN_CHECK_ARG(!lds || (n_src == n_rows && rows_per_blk <= 512 && rows_per_blk % 128 == 0));
-  BlkArgs a{n_rows, K, rowptr, col, val, src_scale, bias, X, ldx, Y, ldy, reduce == EGNN_MEAN, seg_max, rows_per_blk, blk_ptr, n_blk,
-            win, hub_seg, n_hub_seg, partial, addend, ld_addend, stat_part, stat_shift, 0, 0, (uint32_t)xb, flags};
+  EGNN_CHECK_ARG(!lds || (op->n_src == n_rows && rows_per_blk <= 512 && rows_per_blk % 128 == 0));
+  BlkArgs a{};
+  a.n_rows = n_rows; a.K = K; a.rowptr = (const int32_t*)op->rowptr; a.col = (const int32_t*)op->col;
+  a.val = op->val; a.src_scale = op->src_scale; a.bias = op->bias;
+  a.X = op->X; a.ldx = op->ldx; a.Y = op->Y; a.ldy = op->ldy; a.mean = op->reduce == EGNN_MEAN;
+  a.seg_max = seg_max; a.rows_per_blk = rows_per_blk; a.blk_ptr = blk_ptr; a.n_blk = n_blk; a.win = win;
+  a.hseg = hub_seg; a.n_hseg = n_hub_seg; a.P = partial;
+  a.addend = op->addend; a.ld_add = op->ld_addend; a.stat_part = op->stat_part; a.stat_shift = op->stat_shift;
+  a.x_bytes = (uint32_t)xb; a.flags = op->flags;
   a.NS = (int)((K + 31) / 32);
   a.map_mode = (a.NS <= 8 && 8 % a.NS == 0) ? 1 : (a.NS % 8 == 0 ? 2 : 0);
   const int nsub = lds ? 128 : 32;
@@ -514,7 +519,7 @@ extern "C" int egnn_spmm_csr_blk_f32(int64_t n_rows, int64_t n_src, int64_t K, c
   }
   if (grid > 0x7fffffffLL) return EGNN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const bool stats = stat_part != nullptr;
+  const bool stats = op->stat_part != nullptr;
   if (!lds) {   // ROWS = 1: the one-row-per-sub-group form (rows_per_blk == 32, the host default); ROWS = 0: the row loop
     if (rows_per_blk == 32)
       return stats ? launch_blk<false, true, 4, 1>(a, (unsigned)grid, 0, st) : launch_blk<false, false, 4, 1>(a, (unsigned)grid, 0, st);

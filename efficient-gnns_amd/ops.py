@@ -45,6 +45,14 @@ class HipStatsUnavailable(RuntimeError):
     separate egnn_bn_stats_f32 pass)."""
 
 
+def _spmm_desc(adj, rowptr, col, bits, x, y, red, src_scale, bias) -> ctypes.Structure:
+    """The egnn_spmm_t descriptor (include/egnn_hip.h) of one aggregation Y = REDUCE(adj, X), without an epilogue.  Built once per call
+    from the tensors at hand (the caller keeps them alive); the entry points read it only while they run."""
+    n_rows, n_src = adj.sparse_sizes()
+    return _lib.Spmm(n_rows, n_src, x.shape[1], _lib.ptr(rowptr), _lib.ptr(col), bits, _lib.ptr(adj._value), _lib.ptr(src_scale),
+                     _lib.ptr(bias), _lib.ptr(x), x.stride(0), _lib.ptr(y), y.stride(0), red)
+
+
 def spmm_raw(adj, x: Tensor, reduce: str = "sum", src_scale: Tensor | None = None, use_plan: bool = True,
              bias: Tensor | None = None, out: Tensor | None = None, stat_shift: Tensor | None = None, want_stats: bool = False,
              addend: Tensor | None = None, relu: bool = False):
@@ -100,6 +108,8 @@ def _spmm_raw(adj, x: Tensor, reduce: str = "sum", src_scale: Tensor | None = No
         return y, arg
     rowptr, col, bits = adj._index_arrays()
     lib = _lib.load()
+    op = _spmm_desc(adj, rowptr, col, bits, x, y, red, src_scale, bias)
+    op_ref = ctypes.byref(op)
     float4_ok = (use_plan and red != 2 and K % 4 == 0 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
                  and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0 and (bias is None or bias.data_ptr() % 16 == 0))
     add_fused = addend is not None and addend.stride(0) % 4 == 0 and addend.data_ptr() % 16 == 0
@@ -121,17 +131,15 @@ def _spmm_raw(adj, x: Tensor, reduce: str = "sum", src_scale: Tensor | None = No
         stat_part = adj._scratch("stat", (n_stat + n_hub, 2, K)) if want_stats else None   # one partial row per wave + per hub row
         if stat_shift is not None:
             stat_shift = stat_shift.detach().contiguous()
-        rc = lib.egnn_spmm_csr_blk_f32(n_rows, n_src, K, _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(adj._value), _lib.ptr(src_scale),
-                                       _lib.ptr(bias), _lib.ptr(x), x.stride(0), _lib.ptr(y), y.stride(0), red, SEG_MAX, rows_blk, None, 0,
-                                       _lib.ptr(loc[1]) if use_lds else None, _lib.ptr(hseg), hseg.shape[0], _lib.ptr(partial),
-                                       _lib.ptr(addend), 0 if addend is None else addend.stride(0),
-                                       _lib.ptr(stat_part), _lib.ptr(stat_shift) if want_stats else None, flags, _lib.stream())
+        # the epilogue: read by the block launch and by its combine step, which share the descriptor
+        op.addend, op.ld_addend = _lib.ptr(addend), 0 if addend is None else addend.stride(0)
+        op.stat_part, op.stat_shift, op.flags = _lib.ptr(stat_part), _lib.ptr(stat_shift) if want_stats else None, flags
+        rc = lib.egnn_spmm_csr_blk_f32(op_ref, SEG_MAX, rows_blk, None, 0, _lib.ptr(loc[1]) if use_lds else None, _lib.ptr(hseg),
+                                       hseg.shape[0], _lib.ptr(partial), _lib.stream())
         if rc == 0:
             if n_hub > 0:   # the hub rows: fixed-order sum of their partial slots (+ mean / bias, + their statistics rows)
-                _lib.check(lib.egnn_spmm_combine_f32(n_rows, K, _lib.ptr(rowptr), bits, _lib.ptr(bias), _lib.ptr(y), y.stride(0), red,
-                                                     _lib.ptr(crow), _lib.ptr(cptr), n_hub, _lib.ptr(partial), _lib.ptr(addend),
-                                                     0 if addend is None else addend.stride(0), _lib.ptr(stat_part), n_stat,
-                                                     _lib.ptr(stat_shift) if want_stats else None, flags, _lib.stream()), "egnn_spmm_combine_f32")
+                _lib.check(lib.egnn_spmm_combine_f32(op_ref, _lib.ptr(crow), _lib.ptr(cptr), n_hub, _lib.ptr(partial), n_stat, _lib.stream()),
+                           "egnn_spmm_combine_f32")
             if not want_stats:
                 if flags & 8 and relu_fused is not None:
                     relu_fused.append(True)
@@ -144,17 +152,18 @@ def _spmm_raw(adj, x: Tensor, reduce: str = "sum", src_scale: Tensor | None = No
                                                    _lib.ptr(stat_shift), n_rows, _lib.ptr(mean), _lib.ptr(var), _lib.ptr(ws), nws,
                                                    _lib.stream()), "egnn_bn_stats_merge_f32")
             return y, None, (mean, var)
-        if rc != -4:   # EGNN_EALIGN: shape outside the block kernel's forms -> the schedules below
+        if rc != -4:   # EGNN_EALIGN: shape outside the block kernel's forms -> the schedules below, which have no epilogue
             _lib.check(rc, "egnn_spmm_csr_blk_f32")
+        op.addend = op.stat_part = op.stat_shift = None
+        op.ld_addend = op.flags = 0
     if want_stats:
         raise HipStatsUnavailable()
     if float4_ok and _SPMM_SCHEDULE in ("blocks", "segments"):
         # every row as ranges of <= 64 entries through the sub-group-per-row kernel (hub rows get the bulk's parallelism)
         seg, crow, cptr, slots = adj._seg_plan()
         partial = adj._scratch("partial", (max(slots, 1), K))
-        rc = lib.egnn_spmm_csr_seg_f32(n_rows, n_src, K, _lib.ptr(rowptr), _lib.ptr(col), bits, _lib.ptr(adj._value), _lib.ptr(src_scale),
-                                       _lib.ptr(bias), _lib.ptr(x), x.stride(0), _lib.ptr(y), y.stride(0), red, _lib.ptr(seg),
-                                       seg.shape[0], _lib.ptr(crow), _lib.ptr(cptr), crow.numel(), _lib.ptr(partial), slots, _lib.stream())
+        rc = lib.egnn_spmm_csr_seg_f32(op_ref, _lib.ptr(seg), seg.shape[0], _lib.ptr(crow), _lib.ptr(cptr), crow.numel(), _lib.ptr(partial),
+                                       slots, _lib.stream())
         if rc == 0:
             if addend is not None:
                 y.add_(addend)
@@ -167,10 +176,7 @@ def _spmm_raw(adj, x: Tensor, reduce: str = "sum", src_scale: Tensor | None = No
         return (None, 0) if t is None or t.numel() == 0 else (_lib.ptr(t), t.numel())
 
     def launch(s, m, l, stream):
-        (ps, ns), (pm, nm), (pl, nl) = lst(s), lst(m), lst(l)
-        return lib.egnn_spmm_csr_f32(
-            n_rows, n_src, K, _lib.ptr(rowptr), _lib.ptr(col), bits, _lib.ptr(adj._value), _lib.ptr(src_scale), _lib.ptr(bias),
-            _lib.ptr(x), x.stride(0), _lib.ptr(y), y.stride(0), red, _lib.ptr(arg), ps, ns, pm, nm, pl, nl, stream)
+        return lib.egnn_spmm_csr_f32(op_ref, _lib.ptr(arg), *lst(s), *lst(m), *lst(l), stream)
 
     heavy = use_plan and short is not None and short.numel() > 0 and (mid.numel() + long_.numel()) > 0
     if heavy and _OVERLAP_HEAVY_ROWS:

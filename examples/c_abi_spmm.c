@@ -55,8 +55,11 @@ int main(void) {
   CK(hipMemcpy(d_val, val, nnz * sizeof(float), hipMemcpyHostToDevice));
   CK(hipMemcpy(d_X, X, n * K * sizeof(float), hipMemcpyHostToDevice));
 
-  /* Y = A X, every row through the one-wavefront path (no schedule lists), default stream */
-  EG(egnn_spmm_csr_f32(n, n, K, d_rowptr, d_col, 64, d_val, NULL, NULL, d_X, K, d_Y, K, EGNN_SUM, NULL, NULL, 0, NULL, 0, NULL, 0, NULL));
+  /* Y = A X, every row through the one-wavefront path (no schedule lists), default stream; the operands travel as one
+   * descriptor that the call reads only while it runs (fields not named are NULL / 0) */
+  egnn_spmm_t op = {.n_rows = n, .n_src = n, .K = K, .rowptr = d_rowptr, .col = d_col, .index_bits = 64, .val = d_val,
+                    .X = d_X, .ldx = K, .Y = d_Y, .ldy = K, .reduce = EGNN_SUM};
+  EG(egnn_spmm_csr_f32(&op, NULL, NULL, 0, NULL, 0, NULL, 0, NULL));
   CK(hipDeviceSynchronize());
   float* Y = (float*)malloc(n * K * sizeof(float));
   CK(hipMemcpy(Y, d_Y, n * K * sizeof(float), hipMemcpyDeviceToHost));
@@ -85,7 +88,8 @@ int main(void) {
   }
   printf("gcn_norm count: ok\n");
   /* argument errors come back as codes, nothing is launched */
-  if (egnn_spmm_csr_f32(n, n, K, NULL, d_col, 64, NULL, NULL, NULL, d_X, K, d_Y, K, EGNN_SUM, NULL, NULL, 0, NULL, 0, NULL, 0, NULL) >= 0) return 1;
+  op.rowptr = NULL;
+  if (egnn_spmm_csr_f32(&op, NULL, NULL, 0, NULL, 0, NULL, 0, NULL) >= 0) return 1;
   printf("ok\n");
   return 0;
 }

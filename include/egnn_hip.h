@@ -39,7 +39,7 @@ extern "C" {
 #define EGNN_EWORKSPACE (-3) /* caller-provided workspace too small */
 #define EGNN_EALIGN (-4)   /* pointer / leading dimension not aligned as the entry point requires */
 
-#define EGNN_ABI_VERSION 8
+#define EGNN_ABI_VERSION 9
 int egnn_abi_version(void);
 const char* egnn_error_string(int code);
 /* Number of distinct kernels-families compiled in; used by the loader's self check. */
@@ -54,13 +54,45 @@ int egnn_build_info(char* buf, size_t buf_bytes);
  *   adj_t.matmul(mean)   /root/reference/mag_pyg/gnn.py:162
  *   loss.backward()      /root/reference/arxiv_pyg/gnn.py:192     (same kernel on the transposed CSR)
  *
- * reduce: EGNN_SUM, EGNN_MEAN (sum / max(stored entries of the row, 1)), EGNN_MAX (argmax = index of
- * the FIRST maximal stored entry in CSR order, -1 and 0.0 for an empty row).
- * val        [nnz]    nullable (= 1.0)
- * src_scale  [n_src]  nullable; per-source-row factor, used for the backward of mean
- *                     (dX = A^T (dY / cnt)) without materialising a per-entry value array
- * bias       [K]      nullable; added to every written row (GCNConv `out += bias`, gnn.py:47); not with EGNN_MAX
- * argmax     [n_rows, K] int64, required for EGNN_MAX, ignored otherwise
+ * The operands travel as ONE descriptor, egnn_spmm_t, shared by the three schedules below and the combine step.  A call
+ * reads it only while it runs and never keeps the pointer (kernel arguments are copied at launch: the descriptor may live on
+ * the caller's stack, also while a hipGraph is captured).  op == NULL is EGNN_EINVAL; an entry point checks only what it reads.
+ *   val        [nnz]   nullable (= 1.0)
+ *   src_scale  [n_src] nullable; per-source-row factor, used for the backward of mean (dX = A^T (dY / cnt)) without
+ *                      materialising a per-entry value array
+ *   bias       [K]     nullable; added to every written row (GCNConv `out += bias`, gnn.py:47); not with EGNN_MAX
+ *   reduce             EGNN_SUM, EGNN_MEAN (sum / max(stored entries of the row, 1)), EGNN_MAX (egnn_spmm_csr_f32 only)
+ * The epilogue is read by egnn_spmm_csr_blk_f32 and egnn_spmm_combine_f32 only.  The other two schedules have none: there addend,
+ * stat_part or flags bit 3 set is EGNN_EINVAL (a fused add or ReLU is never silently dropped); the store hints are ignored.
+ *   addend     nullable [n_rows, ld_addend] fp32: added to every stored row (Y = A X + addend): the sharded run aggregates
+ *              its local and its halo columns in two calls, the second one accumulating onto the first
+ *   stat_part  nullable [*, 2, K] fp32 partials of sum_r (y_r - shift) and sum_r (y_r - shift)^2 -- BatchNorm statistics in
+ *              the aggregation epilogue (gnn.py:47-48), finished by egnn_bn_stats_merge_f32
+ *   stat_shift nullable [K] (any vector near the column means, e.g. BatchNorm's running_mean; exactness does not depend on
+ *              it, only the conditioning of the variance)
+ *   flags      bit 1 (2): non-temporal Y stores; bit 2 (4): write-through (sc1) Y stores (tuning knobs, results are identical);
+ *              bit 3 (8): Y = max(Y, 0) on the way out -- ReLU fused into the store (an eval-mode BatchNorm folded into the
+ *              weights / bias by egnn_bn_fold_f32 + ReLU, gnn.py:47-49 under model.eval()); not together with stat_part
+ * ---------------------------------------------------------------------------------------------- */
+#define EGNN_SUM 0
+#define EGNN_MEAN 1
+#define EGNN_MAX 2
+
+typedef struct egnn_spmm {
+  int64_t n_rows; int64_t n_src; int64_t K;
+  const void* rowptr; const void* col; int index_bits;      /* 32 | 64 */
+  const float* val; const float* src_scale; const float* bias;
+  const float* X; int64_t ldx;
+  float* Y; int64_t ldy;
+  int reduce;                                               /* EGNN_SUM | EGNN_MEAN | EGNN_MAX */
+  const float* addend; int64_t ld_addend;                   /* epilogue: block schedule + combine only */
+  float* stat_part; const float* stat_shift;
+  int flags;
+} egnn_spmm_t;
+
+/* The ROW-CLASS schedule, and the only one that offers EGNN_MAX.
+ *   argmax     [n_rows, K] int64, required for EGNN_MAX (index of the FIRST maximal stored entry in CSR order, -1 and 0.0
+ *              for an empty row), ignored otherwise
  * Row schedule (built once per sparsity structure by the caller; integer preprocessing):
  *   short_rows [n_short]  row ids whose entry count is small; a wavefront walks 64/G of them at once (one
  *                         G-lane sub-group per row, G = lanes per 128-byte column slice), so list neighbours
@@ -70,19 +102,9 @@ int egnn_build_info(char* buf, size_t buf_bytes);
  * A call writes exactly the rows it lists (each at most once); with all three lists NULL every row of
  * [0, n_rows) takes the one-wavefront path.  The host normally covers all rows with one call, or with two calls
  * on two streams (short rows | mid + long rows) so the few heavy rows overlap the bulk.  The accumulation order
- * is fixed by the schedule, so results are run-to-run bit-stable for every degree distribution.
- * ---------------------------------------------------------------------------------------------- */
-#define EGNN_SUM 0
-#define EGNN_MEAN 1
-#define EGNN_MAX 2
-
-int egnn_spmm_csr_f32(int64_t n_rows, int64_t n_src, int64_t K,
-                      const void* rowptr, const void* col, int index_bits,
-                      const float* val, const float* src_scale, const float* bias,
-                      const float* X, int64_t ldx, float* Y, int64_t ldy,
-                      int reduce, int64_t* argmax,
-                      const int64_t* short_rows, int64_t n_short, const int64_t* mid_rows, int64_t n_mid,
-                      const int64_t* long_rows, int64_t n_long, void* stream);
+ * is fixed by the schedule, so results are run-to-run bit-stable for every degree distribution. */
+int egnn_spmm_csr_f32(const egnn_spmm_t* op, int64_t* argmax, const int64_t* short_rows, int64_t n_short,
+                      const int64_t* mid_rows, int64_t n_mid, const int64_t* long_rows, int64_t n_long, void* stream);
 
 /* The same aggregation (EGNN_SUM / EGNN_MEAN) under a SEGMENT schedule: every row is cut into entry ranges of at most
  * ~64 entries and ALL ranges go through the sub-group-per-row kernel, so the few hub rows of a power-law graph (8 % of the
@@ -94,43 +116,26 @@ int egnn_spmm_csr_f32(int64_t n_rows, int64_t n_src, int64_t K,
  *   partial   [partial_slots, K] fp32 workspace (16-byte aligned)
  * Requires K % 4 == 0 and 16-byte aligned X / Y / bias (else EGNN_EALIGN: use egnn_spmm_csr_f32).  Every row of
  * [0, n_rows) must be covered exactly once by the schedule (rows with no entries as an empty direct range). */
-int egnn_spmm_csr_seg_f32(int64_t n_rows, int64_t n_src, int64_t K,
-                          const void* rowptr, const void* col, int index_bits,
-                          const float* val, const float* src_scale, const float* bias,
-                          const float* X, int64_t ldx, float* Y, int64_t ldy, int reduce,
-                          const int64_t* seg, int64_t n_seg, const int64_t* comb_rows, const int64_t* comb_ptr, int64_t n_comb,
-                          float* partial, int64_t partial_slots, void* stream);
+int egnn_spmm_csr_seg_f32(const egnn_spmm_t* op, const int64_t* seg, int64_t n_seg, const int64_t* comb_rows,
+                          const int64_t* comb_ptr, int64_t n_comb, float* partial, int64_t partial_slots, void* stream);
 
 /* The same aggregation (EGNN_SUM / EGNN_MEAN) under the ROW-BLOCK schedule (csrc/spmm_blk.hip), the default of the host
  * layer: ONE launch walks, per 128-byte column slice, first the hub segments and then blocks of `rows_per_blk`
  * consecutive rows (or rows [blk_ptr[b], blk_ptr[b+1]) when blk_ptr != NULL; every block at most rows_per_blk rows);
- * int32 indices; any K % 4 == 0; X addressed through a 32-bit buffer descriptor (n_src * ldx * 4 < 2^31 bytes, else
- * EGNN_EALIGN).
+ * int32 indices (index_bits == 64 is EGNN_EALIGN); any K % 4 == 0; X addressed through a 32-bit buffer descriptor
+ * (n_src * ldx * 4 < 2^31 bytes, else EGNN_EALIGN).  EGNN_EALIGN = shape not taken: the caller uses another schedule.
  *   hub_seg    [n_hub_seg,4] int32 (first entry, end entry, partial slot, 0): the entry ranges (<= seg_max entries each) of
  *              the rows with MORE than seg_max entries; their sums go to partial[slot,:] ([slots,K] fp32, 16-byte aligned)
- *              and the caller finishes those rows with egnn_spmm_combine_f32.
+ *              and the caller finishes those rows with egnn_spmm_combine_f32 on the SAME descriptor.
  *              Rows with at most seg_max entries are written here, completely.
  *   win        nullable [n_rows,2] int32 from egnn_spmm_blk_window_i32: entries [win[2r], win[2r+1]) of row r have their
  *              source inside row r's own block.  When given (square adjacency, X rows in node order, rows_per_blk a multiple
  *              of 128, <= 512) the block's X rows are streamed into LDS (LDS-DMA) while the out-of-block entries are
  *              gathered, and the in-block entries read LDS instead of L2 (graphs in a locality order).
- *   addend     nullable [n_rows, ld_addend] fp32: added to every row this call stores (Y = A X + addend): the sharded run
- *              aggregates its local and its halo columns in two calls, the second one accumulating onto the first
- *   stat_part  nullable [egnn_spmm_blk_stat_rows(n_rows, rows_per_blk, win != NULL), 2, K] fp32: per WAVE of every row block
- *              sum_r (y_r - shift) and sum_r (y_r - shift)^2 over the rows that wave stored -- BatchNorm statistics in the
- *              aggregation epilogue (gnn.py:47-48), finished by egnn_bn_stats_merge_f32 (n_blk = that row count);
- *              stat_shift: nullable [K] (any vector near the column means, e.g. BatchNorm's running_mean; exactness does
- *              not depend on it, only the conditioning of the variance)
- *   flags      bit 1 (2): non-temporal Y stores; bit 2 (4): write-through (sc1) Y stores (tuning knobs, results are identical);
- *              bit 3 (8): Y = max(Y, 0) on the way out -- ReLU fused into the store (an eval-mode BatchNorm folded into the
- *              weights / bias by egnn_bn_fold_f32 + ReLU, gnn.py:47-49 under model.eval()); not together with stat_part */
-int egnn_spmm_csr_blk_f32(int64_t n_rows, int64_t n_src, int64_t K,
-                          const int32_t* rowptr, const int32_t* col, const float* val, const float* src_scale, const float* bias,
-                          const float* X, int64_t ldx, float* Y, int64_t ldy, int reduce,
-                          int seg_max, int rows_per_blk, const int32_t* blk_ptr, int64_t n_blk, const int32_t* win,
-                          const int32_t* hub_seg, int64_t n_hub_seg, float* partial,
-                          const float* addend, int64_t ld_addend,
-                          float* stat_part, const float* stat_shift, int flags, void* stream);
+ *   stat_part  here [egnn_spmm_blk_stat_rows(n_rows, rows_per_blk, win != NULL), 2, K]: one partial row per WAVE of every row
+ *              block, over the rows that wave stored (egnn_bn_stats_merge_f32's n_blk = that row count) */
+int egnn_spmm_csr_blk_f32(const egnn_spmm_t* op, int seg_max, int rows_per_blk, const int32_t* blk_ptr, int64_t n_blk,
+                          const int32_t* win, const int32_t* hub_seg, int64_t n_hub_seg, float* partial, void* stream);
 int64_t egnn_spmm_blk_stat_rows(int64_t n_rows, int rows_per_blk, int lds);
 int egnn_spmm_blk_window_i32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int rows_per_blk,
                              const int32_t* blk_ptr, int64_t n_blk, int32_t* win, void* stream);
@@ -143,15 +148,12 @@ int egnn_bn_stats_merge_f32(const float* stat_part, int64_t n_blk, int64_t C, co
                             float* mean, float* var, float* ws, size_t ws_floats, void* stream);
 
 /* The combine step on its own -- the hub rows of egnn_spmm_csr_blk_f32: Y[r] = (sum of partial slots comb_ptr[i] .. comb_ptr[i+1]-1
- * of row r = comb_rows[i], added in slot order) * (1 / rowcount for EGNN_MEAN) + bias (+ addend[r], nullable).  K % 4 == 0,
- * 16-byte aligned rows.
+ * of row r = comb_rows[i], added in slot order) * (1 / rowcount for EGNN_MEAN) + bias (+ addend[r]).  K % 4 == 0, 16-byte
+ * aligned rows.  Reads neither col, val, src_scale, X, ldx nor n_src (they may be unset); of flags only bit 3 (ReLU).
  * stat_part != NULL: row (stat_base + i) of the [*, 2, K] statistics partials receives (y - shift) and (y - shift)^2 of
- * combined row i (one partial row per hub row, folded by egnn_bn_stats_merge_f32 together with the block kernel's).
- * flags: bit 3 (8) = ReLU on the way out, as in egnn_spmm_csr_blk_f32. */
-int egnn_spmm_combine_f32(int64_t n_rows, int64_t K, const void* rowptr, int index_bits, const float* bias, float* Y, int64_t ldy,
-                          int reduce, const int64_t* comb_rows, const int64_t* comb_ptr, int64_t n_comb, const float* partial,
-                          const float* addend, int64_t ld_addend, float* stat_part, int64_t stat_base, const float* stat_shift,
-                          int flags, void* stream);
+ * combined row i (one partial row per hub row, folded by egnn_bn_stats_merge_f32 together with the block kernel's). */
+int egnn_spmm_combine_f32(const egnn_spmm_t* op, const int64_t* comb_rows, const int64_t* comb_ptr, int64_t n_comb,
+                          const float* partial, int64_t stat_base, void* stream);
 
 /* Backward of EGNN_MAX: dX[col[argmax[i,k]], k] += val * dY[i,k].  dX must be zero-filled by the
  * caller.  Uses float atomics (the only entry point that does); max-aggregation is never exercised

@@ -46,13 +46,13 @@ def test_gat_layer_descriptor_matches_the_header_field_by_field():
 REMOVED_SYMBOLS = ("egnn_gat_attention_bwd_f32", "egnn_gat_aggregate_bwd_f32", "egnn_gat_aggregate_bwd_ws_floats")
 
 
-def test_new_symbols_are_declared_exported_and_bound_and_the_abi_is_8():
+def test_new_symbols_are_declared_exported_and_bound_and_the_abi_is_9():
     src = _header()
     lib = _lib.load()
     for s in NEW_SYMBOLS:
         assert re.search(r"\b%s\s*\(" % s, src), f"{s} is not declared in include/egnn_hip.h"
         assert s in _lib.SIGNATURES and hasattr(lib, s)
-    assert lib.egnn_abi_version() == 8 and re.search(r"#define\s+EGNN_ABI_VERSION\s+8\b", src)
+    assert lib.egnn_abi_version() == 9 and re.search(r"#define\s+EGNN_ABI_VERSION\s+9\b", src)
     # the coefficient forward keeps its signature; the positional backward pair is gone: one descriptor call for both layers
     assert len(_lib.SIGNATURES["egnn_gat_attention_fwd_f32"][1]) == 10
     assert len(_lib.SIGNATURES["egnn_gat_layer_bwd_f32"][1]) == 13

@@ -23,14 +23,14 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(egnn_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_library_exports_every_declared_symbol_of_abi_8():
+def test_library_exports_every_declared_symbol_of_abi_9():
     syms = declared_symbols()
     assert len(syms) >= 30
     lib = ctypes.CDLL(E._lib.LIB_PATH)
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/egnn_hip.h but not exported"
     assert set(syms) == set(E._lib.SIGNATURES), "ctypes table and header disagree"
-    assert E._lib.load().egnn_abi_version() == 8
+    assert E._lib.load().egnn_abi_version() == 9
     assert "gfx950" in E._lib.build_info()
     assert E._lib.load().egnn_error_string(-3) == b"workspace too small"
 
@@ -157,13 +157,36 @@ def test_c_abi_and_bn_descriptor_argument_errors_are_reported_before_any_launch(
     buf = (ctypes.c_float * 64)()
     ibuf = (ctypes.c_int64 * 16)()
     p, ip = ctypes.addressof(buf), ctypes.addressof(ibuf)
-    # segment SpMM: max is not offered; missing combine arrays; negative sizes
-    assert lib.egnn_spmm_csr_seg_f32(4, 4, 4, ip, ip, 64, None, None, None, p, 4, p, 4, 2, ip, 1, None, None, 0, None, 0, None) < 0
-    assert lib.egnn_spmm_csr_seg_f32(4, 4, 4, ip, ip, 64, None, None, None, p, 4, p, 4, 0, ip, 1, None, None, 2, None, 0, None) < 0
-    assert lib.egnn_spmm_csr_seg_f32(4, 4, 4, ip, ip, 16, None, None, None, p, 4, p, 4, 0, ip, 1, None, None, 0, None, 0, None) < 0
-    assert lib.egnn_spmm_csr_seg_f32(0, 0, 4, None, None, 64, None, None, None, None, 4, None, 4, 0, None, 0, None, None, 0, None, 0, None) == 0
+    # SpMM, operands in one egnn_spmm_t descriptor.  Segment schedule: max is not offered; missing combine arrays; a bad index width
+    def spmm(**kw):
+        f = dict(n_rows=4, n_src=4, K=4, rowptr=ip, col=ip, index_bits=64, X=p, ldx=4, Y=p, ldy=4)
+        f.update(kw)
+        return ctypes.byref(_lib.Spmm(**f))
+    seg_call = lambda op, n_comb=0: lib.egnn_spmm_csr_seg_f32(op, ip, 1, None, None, n_comb, None, 0, None)   # noqa: E731
+    cls_call = lambda op, argmax=None: lib.egnn_spmm_csr_f32(op, argmax, None, 0, None, 0, None, 0, None)      # noqa: E731
+    blk_call = lambda op: lib.egnn_spmm_csr_blk_f32(op, 64, 32, None, 0, None, None, 0, None, None)            # noqa: E731
+    comb_call = lambda op, n_comb=1: lib.egnn_spmm_combine_f32(op, ip, ip, n_comb, p, 0, None)                 # noqa: E731
+    assert seg_call(spmm(reduce=2)) < 0
+    assert seg_call(spmm(), n_comb=2) < 0
+    assert seg_call(spmm(index_bits=16)) < 0
+    empty = ctypes.byref(_lib.Spmm(n_rows=0, n_src=0, K=4, index_bits=64, ldx=4, ldy=4))
+    assert lib.egnn_spmm_csr_seg_f32(empty, None, 0, None, None, 0, None, 0, None) == 0
     # unaligned leading dimension -> EGNN_EALIGN (-4): the host falls back to egnn_spmm_csr_f32
-    assert lib.egnn_spmm_csr_seg_f32(4, 4, 4, ip, ip, 64, None, None, None, p, 5, p, 5, 0, ip, 1, None, None, 0, None, 0, None) == -4
+    assert seg_call(spmm(ldx=5, ldy=5)) == -4
+    # no descriptor at all
+    assert cls_call(None) == EINVAL and seg_call(None) == EINVAL and blk_call(None) == EINVAL and comb_call(None) == EINVAL
+    # the class and segment schedules have no epilogue: a fused add / statistics / ReLU is refused, never dropped
+    for epilogue in (dict(addend=p, ld_addend=4), dict(stat_part=p), dict(flags=8)):
+        assert cls_call(spmm(**epilogue)) == EINVAL and seg_call(spmm(**epilogue)) == EINVAL
+    # the block schedule takes int32 indices only: 64 is "shape not taken" (-4), the host's cue for the other schedules
+    assert blk_call(spmm(index_bits=64)) == -4
+    # max needs its argmax
+    assert cls_call(spmm(reduce=2)) == EINVAL
+    # the combine step: nothing to combine is fine; it reads neither X nor col, so their absence is not an error (the unaligned ldy
+    # is what stops this call, before any launch)
+    assert comb_call(spmm(), n_comb=0) == 0
+    assert comb_call(spmm(X=None, col=None, ldy=5)) == -4
+    assert comb_call(spmm(X=None, col=None, val=None, src_scale=None, ldx=0, n_src=-1, ldy=5)) == -4
     # fused-gather GEMM: at most one gather, and only on an untransposed operand
     assert lib.egnn_gemm_rows_f32(0, 1, 4, 4, 4, 1.0, p, 4, ip, p, 4, ip, None, p, 4, 1, None, 0, None) < 0
     assert lib.egnn_gemm_rows_f32(1, 1, 4, 4, 4, 1.0, p, 4, ip, p, 4, None, None, p, 4, 1, None, 0, None) < 0
@@ -281,25 +304,31 @@ def test_subgraph_property(case, seed, as_mask):
 
 
 def test_integration_md_ctypes_snippet_matches_the_header():
-    """The binding shown in INTEGRATION.md must have exactly the parameters include/egnn_hip.h declares (doc rot guard)."""
+    """The binding shown in INTEGRATION.md must have exactly the parameters include/egnn_hip.h declares, and its egnn_spmm_t Structure
+    the fields of the ctypes mirror the package uses (doc rot guard)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     md = open(os.path.join(root, "INTEGRATION.md")).read()
     block = md[md.index("```python\nimport ctypes, torch"):]
     block = block[len("```python\n"):block.index("```", 10)]
-    stmt = block[block.index("lib.egnn_spmm_csr_f32.argtypes"):block.index("def spmm_sum")]
+    stmt = block[block.index("class Spmm(ctypes.Structure)"):block.index("def spmm_sum")]
 
     class _Fn:
         pass
 
     class _Lib:
         egnn_spmm_csr_f32 = _Fn()
-    exec(stmt, {"ctypes": ctypes, "lib": _Lib})
+    ns = {"ctypes": ctypes, "lib": _Lib}
+    exec(stmt, ns)
+    assert [(n, ctypes.sizeof(t), t is ctypes.c_void_p) for n, t in ns["Spmm"]._fields_] == \
+        [(n, ctypes.sizeof(t), t is ctypes.c_void_p) for n, t in _lib.Spmm._fields_]
     shown = _Lib.egnn_spmm_csr_f32.argtypes
     table = _lib.SIGNATURES["egnn_spmm_csr_f32"][1]
     assert len(shown) == len(table)
     assert [ctypes.sizeof(a) for a in shown] == [ctypes.sizeof(a) for a in table]
     call = block[block.index("rc = lib.egnn_spmm_csr_f32("):block.index("assert rc == 0")]
     assert call.count(",") + 1 == len(table), "the example call passes a different number of arguments"
+    made = block[block.index("op = Spmm("):block.index("rc = lib.egnn_spmm_csr_f32(")]
+    assert set(re.findall(r"(\w+)=", made)) <= {n for n, _ in _lib.Spmm._fields_}, "the example names a field the descriptor lacks"
 
 
 def test_teacher_artifact_round_trip(tmp_path):
@@ -493,30 +522,45 @@ def test_ctypes_table_matches_the_header_argument_by_argument():
     assert seen == set(_lib.SIGNATURES)
 
 
-def test_ctypes_bn_descriptor_matches_the_header_field_by_field():
-    """egnn_bn_act_t of include/egnn_hip.h parsed and compared with efficient-gnns_amd/_lib.py::BnAct: same fields in the same order and
-    of the same kind (pointer / int64 / int / float / uint64) -- a layout mismatch would not fail at load time either, the kernels would
-    read shifted operands."""
+def _descriptor_matches_header(tag, struct, n_fields):
+    """``typedef struct <tag> {...} <tag>_t`` of include/egnn_hip.h parsed and compared with its ctypes mirror: same fields in the same
+    order and of the same kind (pointer / int64 / int / float / uint64); every prototype naming the type takes it as ``const <tag>_t*`` and
+    is bound as a pointer argument."""
     import ctypes as C
     from efficient_gnns_amd import _lib
     src = open(os.path.join(ROOT, "include", "egnn_hip.h")).read()
     src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    body = re.search(r"typedef\s+struct\s+egnn_bn_act\s*\{([^}]*)\}\s*egnn_bn_act_t\s*;", src).group(1)
+    body = re.search(r"typedef\s+struct\s+%s\s*\{([^}]*)\}\s*%s_t\s*;" % (tag, tag), src).group(1)
 
     def kind(t):
         t = t.replace("const", "").strip()
         return "p" if t.endswith("*") else {"int64_t": "i64", "int": "i32", "float": "f32", "uint64_t": "u64"}[t]
     want = [(m.group(2), kind(m.group(1))) for m in (re.match(r"(.*?)(\w+)$", d.strip(), flags=re.S) for d in body.split(";") if d.strip())]
-    assert len(want) == 15
+    assert len(want) == n_fields
     kinds = {C.c_void_p: "p", C.c_int64: "i64", C.c_int: "i32", C.c_float: "f32", C.c_uint64: "u64"}
-    got = [(name, kinds[t]) for name, t in _lib.BnAct._fields_]
-    assert got == want, f"egnn_bn_act_t: ctypes {got} vs header {want}"
-    # every entry point that takes the descriptor binds it as a pointer argument
+    got = [(name, kinds[t]) for name, t in struct._fields_]
+    assert got == want, f"{tag}_t: ctypes {got} vs header {want}"
+    takers = 0
     for ret, name, args in re.findall(r"\b(int64_t|size_t|int)\s+(egnn_\w+)\s*\(([^;{]*)\)\s*;", src):
         for i, a in enumerate(args.split(",")):
-            if "egnn_bn_act_t" in a:
-                assert re.fullmatch(r"\s*const\s+egnn_bn_act_t\s*\*\s*\w+\s*", a), f"{name}: {a}"
+            if tag + "_t" in a:
+                assert re.fullmatch(r"\s*const\s+%s_t\s*\*\s*\w+\s*" % tag, a), f"{name}: {a}"
                 assert _lib.SIGNATURES[name][1][i] is C.c_void_p, name
+                takers += 1
+    return takers
+
+
+def test_ctypes_bn_descriptor_matches_the_header_field_by_field():
+    """egnn_bn_act_t against efficient-gnns_amd/_lib.py::BnAct -- a layout mismatch would not fail at load time either, the kernels
+    would read shifted operands."""
+    assert _descriptor_matches_header("egnn_bn_act", _lib.BnAct, 15) == 7
+
+
+def test_ctypes_spmm_descriptor_matches_the_header_field_by_field():
+    """egnn_spmm_t against efficient-gnns_amd/_lib.py::Spmm, and its four entry points take it first, as a pointer."""
+    assert _descriptor_matches_header("egnn_spmm", _lib.Spmm, 19) == 4
+    for name in ("egnn_spmm_csr_f32", "egnn_spmm_csr_seg_f32", "egnn_spmm_csr_blk_f32", "egnn_spmm_combine_f32"):
+        assert _lib.SIGNATURES[name][1][0] is ctypes.c_void_p
 
 
 def test_student_layer_form_table():

@@ -61,7 +61,7 @@ def test_saint_symbols_are_declared_exported_and_bound():
         assert hasattr(lib, s), f"{s} is not exported"
         assert s in _lib.SIGNATURES
     assert "mag_pyg/gnn.py:361-366" in src
-    assert _lib.load().egnn_abi_version() == 8 and "#define EGNN_ABI_VERSION 8" in src
+    assert _lib.load().egnn_abi_version() == 9 and "#define EGNN_ABI_VERSION 9" in src
     g = _lib.load().egnn_saint_induced_geometry
     assert g(0) == 64 and g(1) % 64 == 0 and g(2) >= g(1) and g(3) < 0
 

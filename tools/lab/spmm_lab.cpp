@@ -228,18 +228,20 @@ int main(int argc, char** argv) {
       inblk = (double)in / (double)g.nnz;
     }
     const int64_t nb = v.comm_blocks ? n_blk : (n + v.R - 1) / std::max(v.R, 1);
+    // one descriptor for the variant: the block launch and its combine step read the same operands and epilogue
+    egnn_spmm_t op = {};
+    op.n_rows = op.n_src = n; op.K = K; op.rowptr = d_rp; op.col = d_col; op.index_bits = 32; op.val = d_val;
+    op.X = d_x; op.ldx = K; op.Y = d_y; op.ldy = K; op.reduce = EGNN_SUM;
+    if (v.kind != 0) { op.stat_part = v.stats ? d_stat : nullptr; op.stat_shift = v.stats ? d_shift : nullptr; op.flags = v.flags; }
     auto run = [&]() -> int {
       if (v.kind == 0)
-        return egnn_spmm_csr_seg_f32(n, n, K, d_rp, d_col, 32, d_val, nullptr, nullptr, d_x, K, d_y, K, EGNN_SUM, d_seg_all,
-                                     (int64_t)sp.seg_all.size() / 3, d_crow, d_cptr, (int64_t)sp.crow.size(), d_partial, sp.slots, st);
-      int rc = egnn_spmm_csr_blk_f32(n, n, K, d_rp, d_col, d_val, nullptr, nullptr, d_x, K, d_y, K, EGNN_SUM, seg_max, v.R, d_blk, n_blk,
-                                     v.lds ? d_win : nullptr, d_hseg, n_hseg, d_partial, nullptr, 0, v.stats ? d_stat : nullptr,
-                                     v.stats ? d_shift : nullptr, v.flags, st);
+        return egnn_spmm_csr_seg_f32(&op, d_seg_all, (int64_t)sp.seg_all.size() / 3, d_crow, d_cptr, (int64_t)sp.crow.size(), d_partial,
+                                     sp.slots, st);
+      int rc = egnn_spmm_csr_blk_f32(&op, seg_max, v.R, d_blk, n_blk, v.lds ? d_win : nullptr, d_hseg, n_hseg, d_partial, st);
       if (rc) return rc;
       const int64_t n_stat = v.stats ? egnn_spmm_blk_stat_rows(n, v.R, v.lds) : 0;
       if (!sp.crow.empty())   // the hub rows: fixed-order sum of the partial slots the block kernel's launch filled
-        rc = egnn_spmm_combine_f32(n, K, d_rp, 32, nullptr, d_y, K, EGNN_SUM, d_crow, d_cptr, (int64_t)sp.crow.size(), d_partial, nullptr, 0,
-                                   v.stats ? d_stat : nullptr, n_stat, v.stats ? d_shift : nullptr, 0, st);
+        rc = egnn_spmm_combine_f32(&op, d_crow, d_cptr, (int64_t)sp.crow.size(), d_partial, n_stat, st);
       if (rc) return rc;
       if (v.stats)
         rc = egnn_bn_stats_merge_f32(d_stat, n_stat + (int64_t)sp.crow.size(), K, nullptr, 0, nullptr, 0, d_shift, n, d_mean, d_var, d_fold,

@@ -1,5 +1,5 @@
 """Time the three row classes of the SpMM schedule separately (tools only): is a K=128 / K=40 call bound by the hubs?"""
-import os, sys
+import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 import efficient_gnns_amd as E, efficient_gnns_amd.data as D
@@ -24,8 +24,8 @@ for K in (256, 128, 40):
     def call(s, m, l):
         def p(v): return (None, 0) if v is None else (_lib.ptr(v), v.numel())
         (ps, ns), (pm, nm), (pl, nl) = p(s), p(m), p(l)
-        rc = lib.egnn_spmm_csr_f32(n, n, K, _lib.ptr(rowptr), _lib.ptr(col), bits, _lib.ptr(adj._value), None, None, _lib.ptr(x), K,
-                                   _lib.ptr(y), K, 0, None, ps, ns, pm, nm, pl, nl, _lib.stream())
+        op = _lib.Spmm(n, n, K, _lib.ptr(rowptr), _lib.ptr(col), bits, _lib.ptr(adj._value), None, None, _lib.ptr(x), K, _lib.ptr(y), K, 0)
+        rc = lib.egnn_spmm_csr_f32(ctypes.byref(op), None, ps, ns, pm, nm, pl, nl, _lib.stream())
         assert rc == 0
     print(f"K={K:3d}  short {t(lambda: call(short, None, None)):7.1f} us   mid {t(lambda: call(None, mid, None)):7.1f} us   "
           f"long {t(lambda: call(None, None, long_)):7.1f} us   all-in-one-stream {t(lambda: call(short, mid, long_)):7.1f} us   "
