@@ -47,6 +47,16 @@ class Spmm(C.Structure):
                 ("addend", _p), ("ld_addend", _i64), ("stat_part", _p), ("stat_shift", _p), ("flags", _i32)]
 
 
+class SignSeg(C.Structure):
+    """egnn_sign_seg_t of include/egnn_hip.h, field for field: the operands of one hop-batched SIGN kernel call (csrc/sign.hip).  seed,
+    slope, src and ld_src point at HOST arrays of H entries (ctypes arrays the caller keeps alive for the call)."""
+    _fields_ = [("B", _i64), ("Cs", _i64), ("H", _i32),
+                ("p", _f32), ("seed", _p), ("seed_dev", _p),
+                ("slope", _p),
+                ("src", _p), ("ld_src", _p), ("n_src", _i64),
+                ("batch", _p)]
+
+
 # name -> (restype, argtypes); must list every symbol include/egnn_hip.h declares
 SIGNATURES = {
     "egnn_abi_version": (_i32, []),
@@ -147,6 +157,10 @@ SIGNATURES = {
     "egnn_saint_induced_count_i64": (_i32, [_p, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _p, _sz, _p]),
     "egnn_saint_induced_fill_i64": (_i32, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _p, _p, _p]),
     "egnn_saint_gather_i64": (_i32, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p]),
+    "egnn_sign_gather_drop_f32": (_i32, [_p, _p, _i64, _p]),
+    "egnn_prelu_drop_fwd_f32": (_i32, [_p, _p, _i64, _p, _i64, _p]),
+    "egnn_prelu_drop_ws_floats": (_sz, [_i64, _i64, _i32]),
+    "egnn_prelu_drop_bwd_f32": (_i32, [_p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _sz, _p]),
     "egnn_probe_gather_lines_f32":(_i32, [_p, _i64, _i64, _i64, _p, _i64, _i32, _i32, _p, _p]),
 }
 

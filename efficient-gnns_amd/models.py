@@ -962,3 +962,198 @@ def mag_test(model, x_dict, edge_index_dict, key2int, y_paper, split_idx):
         idx = (idx["paper"] if isinstance(idx, dict) else idx).to(y_pred.device)
         accs.append(accuracy(y_true[idx], y_pred[idx]))
     return tuple(accs)
+
+
+# ------------------------------------------------------------------------------------------------
+# SIGN student (/root/reference/arxiv_dgl/sign.py): graph-agnostic MLP over pre-averaged hop features
+# ------------------------------------------------------------------------------------------------
+class FeedForwardNet(nn.Module):
+    """sign.py:105-133: ``n_layers`` Linear layers with one shared PReLU + dropout between them (same constructor, attribute names,
+    state_dict keys and initial values under a torch seed).  The forward runs the MFMA GEMM and the fused PReLU + dropout kernel."""
+
+    def __init__(self, in_feats, hidden, out_feats, n_layers, dropout):
+        super().__init__()
+        self.layers = nn.ModuleList()
+        self.n_layers = n_layers
+        if n_layers == 1:
+            self.layers.append(nn.Linear(in_feats, out_feats))
+        else:
+            self.layers.append(nn.Linear(in_feats, hidden))
+            for i in range(n_layers - 2):
+                self.layers.append(nn.Linear(hidden, hidden))
+            self.layers.append(nn.Linear(hidden, out_feats))
+        if self.n_layers > 1:
+            self.prelu = nn.PReLU()
+            self.dropout = nn.Dropout(dropout)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain("relu")
+        for layer in self.layers:
+            nn.init.xavier_uniform_(layer.weight, gain=gain)
+            nn.init.zeros_(layer.bias)
+
+    def forward(self, x):
+        for layer_id, layer in enumerate(self.layers):
+            x = ops.linear(x, layer.weight, layer.bias)
+            if layer_id < self.n_layers - 1:
+                x = ops.prelu_drop(x, [self.prelu.weight], x.shape[1], self.dropout.p, self.training)
+        return x
+
+
+class SIGN(nn.Module):
+    """sign.py:136-162.  ``forward(feats)`` is the reference's call (a list of already-gathered [B, F] hop features);
+    ``forward_rows(feats, batch)`` takes the full [N, F] hop features and the batch's row ids and never materialises ``x[batch]``.
+    The level-l activations of ALL hops live in one [B, H*hidden] buffer: every hop's GEMM writes its column block, one
+    ``ops.prelu_drop`` launch per level serves all hops, the last per-hop GEMMs write the concatenation itself (no torch.cat).
+    Dropout seeds are drawn in the reference's dropout call order: input drop of hops 0..H-1; hop by hop, that hop's hidden levels
+    in layer order; the concatenation; ``project``'s hidden levels."""
+
+    def __init__(self, in_feats, hidden, out_feats, num_hops, n_layers, dropout, input_drop):
+        super().__init__()
+        self.dropout = nn.Dropout(dropout)
+        self.prelu = nn.PReLU()
+        self.inception_ffs = nn.ModuleList()
+        self.input_drop = nn.Dropout(input_drop)
+        for hop in range(num_hops):
+            self.inception_ffs.append(FeedForwardNet(in_feats, hidden, hidden, n_layers, dropout))
+        self.project = FeedForwardNet(num_hops * hidden, hidden, out_feats, n_layers, dropout)
+
+    def reset_parameters(self):
+        for ff in self.inception_ffs:
+            ff.reset_parameters()
+        self.project.reset_parameters()
+
+    def forward(self, feats):
+        return self.forward_rows(feats, None)
+
+    def forward_rows(self, feats, batch):
+        """``self([x[batch] for x in feats])``.  ``batch``: int64 row ids on the device, a ``range`` (contiguous rows: a slice), or
+        None (every row).  Training with ``input_drop > 0``: gather + input dropout of all hops in one launch
+        (``ops.sign_gather_drop``); otherwise the first GEMM of every hop gathers in its operand load and no gather pass runs."""
+        feats = list(feats)
+        ffs = list(self.inception_ffs)
+        H = len(ffs)
+        if len(feats) != H:
+            raise ValueError(f"SIGN: expected {H} hop feature matrices, got {len(feats)}")
+        _lib.require_gpu(*feats)
+        training = self.training
+        if training and self.input_drop.p > 0:
+            if batch is None or isinstance(batch, range):
+                lo, hi = (0, feats[0].shape[0]) if batch is None else (batch.start, batch.stop)
+                batch = torch.arange(lo, hi, dtype=torch.int64, device=feats[0].device)
+            x, rows = ops.sign_gather_drop(feats, batch, self.input_drop.p, True), None
+        else:
+            x, rows = feats, batch
+        L = ffs[0].n_layers
+        drop = training and L > 1 and ffs[0].dropout.p > 0
+        seeds = [[ops._draw_dropout_seed() for _ in range(L - 1)] for _ in range(H)] if drop else None
+        cat_seed = [ops._draw_dropout_seed()] if training and self.dropout.p > 0 else None
+        for l in range(L):
+            z = ops.linear_blocks(x, [ff.layers[l].weight for ff in ffs], [ff.layers[l].bias for ff in ffs], rows)
+            rows = None
+            if l < L - 1:
+                x = ops.prelu_drop(z, [ff.prelu.weight for ff in ffs], z.shape[1] // H, ffs[0].dropout.p, training,
+                                   seeds=[s[l] for s in seeds] if drop else None)
+        self.out_feat = ops.prelu_drop(z, [self.prelu.weight], z.shape[1], self.dropout.p, training, seeds=cat_seed)
+        return self.project(self.out_feat)
+
+
+def make_sign_projections(num_hidden, num_hops, proj_dim, teacher_dim=750):
+    """(student_proj, teacher_proj) of sign.py:421-432: Linear + BatchNorm1d + ReLU heads over the concatenated hop features
+    (``num_hidden * num_hops`` wide) and over the teacher's features; same construction order, so the same values under a torch seed."""
+    return ProjectionHead(num_hidden * num_hops, proj_dim), ProjectionHead(teacher_dim, proj_dim)
+
+
+SIGN_MODES = ("supervised", "kd", "fitnet", "at", "gpw", "nce")
+
+
+def sign_batch_loss(model, feats, labels, batch, mode, hp, teacher_out_feat=None, teacher_logits=None, student_proj=None,
+                    teacher_proj=None, kd_and_aux=True):
+    """``(loss, loss_cls, loss_aux)`` of one mini-batch: the loop body of sign.py:307-369 (``kd_and_aux``: the KD loss plus
+    ``beta * loss_aux``, what ``run`` calls) or of :235-277.  ``loss_cls`` / ``loss_aux`` are None where the reference leaves them so."""
+    if mode not in SIGN_MODES:
+        raise NotImplementedError(mode)
+    logits = model.forward_rows(feats, batch)
+    y = labels.view(-1)[batch]
+    if mode == "supervised":
+        return ops.cross_entropy(logits, y), None, None
+    kd = lambda: C.kd_criterion(logits, y, teacher_logits[batch], hp["alpha"], hp["kd_T"])   # noqa: E731
+    if mode == "kd":
+        return kd()
+    if mode == "at":
+        f, t = model.out_feat, teacher_out_feat[batch]
+        res = C.at_criterion(logits, y, f, t, hp["beta"])
+    else:
+        f = student_proj(model.out_feat)
+        t = teacher_proj.forward_rows(teacher_out_feat, batch) if hasattr(teacher_proj, "forward_rows") else teacher_proj(teacher_out_feat[batch])
+        if mode == "fitnet":
+            res = C.fitnet_criterion(logits, y, f, t, hp["beta"])
+        elif mode == "gpw":
+            res = C.gpw_criterion(logits, y, f, t, hp["kernel"], hp["beta"], hp["max_samples"])
+        else:
+            res = C.nce_criterion(logits, y, f, t, hp["beta"], hp["nce_T"], hp["max_samples"])
+    if not kd_and_aux:
+        return res
+    loss_aux = res[2]
+    loss, loss_cls, _ = kd()
+    return loss + hp["beta"] * loss_aux, loss_cls, loss_aux
+
+
+def sign_train_epoch(model, feats, labels, optimizer, batches, mode, hp, teacher_out_feat=None, teacher_logits=None,
+                     student_proj=None, teacher_proj=None, kd_and_aux=True):
+    """One SIGN training epoch: one optimisation step per index tensor of ``batches`` (the reference's ``train_loader``).
+    ``kd_and_aux=True``: ``train_kd_and_aux`` (sign.py:293-382, what ``run`` calls); False: ``train`` (:221-290).  Returns the
+    reference's three means over the steps (unweighted; ``loss_cls`` / ``loss_aux`` count as 0 where the reference leaves them None).
+    The per-step scalars stay on the device and are read once, at the end of the epoch."""
+    if mode not in SIGN_MODES:
+        raise NotImplementedError(mode)
+    model.train()
+    for m in (student_proj, teacher_proj):
+        if m is not None:
+            m.train()
+    dev = labels.device
+    _lib.require_gpu(labels, *feats)
+    steps = []
+    for batch in batches:
+        batch = batch.to(dev)
+        loss, loss_cls, loss_aux = sign_batch_loss(model, feats, labels, batch, mode, hp, teacher_out_feat, teacher_logits,
+                                                   student_proj, teacher_proj, kd_and_aux)
+        optimizer.zero_grad()
+        loss.backward(gradient=_one_like(loss))
+        optimizer.step()
+        zero = loss.detach() * 0
+        steps.append(torch.stack([loss.detach(), zero if loss_cls is None else loss_cls.detach(),
+                                  zero if loss_aux is None else loss_aux.detach()]))
+    if not steps:
+        raise ValueError("sign_train_epoch: `batches` is empty")
+    a, b, c = torch.stack(steps).double().mean(0).tolist()
+    return a, b, c
+
+
+def _as_range(batch):
+    """``range(start, stop)`` for a HOST index tensor that lists consecutive rows (the reference's test_loader over ``torch.arange``:
+    checked on the host, no device read), else None."""
+    if torch.is_tensor(batch) and not batch.is_cuda and batch.dim() == 1 and batch.numel() > 0:
+        start, n = int(batch[0]), batch.numel()
+        if int(batch[-1]) == start + n - 1 and bool((batch[1:] - batch[:-1] == 1).all()):
+            return range(start, start + n)
+    return None
+
+
+@torch.no_grad()
+def sign_test(model, feats, labels, eval_batches, train_nid, val_nid, test_nid):
+    """``test()`` of sign.py:385-401: batch-wise eval-mode forward over ``eval_batches`` (the reference's ``test_loader``, which covers
+    rows 0..N-1 in order; a batch of consecutive rows is read as a slice), the logits written batch by batch into one [N, classes]
+    tensor, then argmax + the three accuracies in one pass (``ops.split_accuracy``).  Returns ``(logits, (train, val, test))``."""
+    model.eval()
+    dev = labels.device
+    _lib.require_gpu(labels, *feats)
+    parts = []
+    for batch in eval_batches:
+        rng = batch if isinstance(batch, range) else _as_range(batch)
+        parts.append(model.forward_rows(feats, rng if rng is not None else batch.to(dev)))
+    logits = torch.cat(parts, dim=0)
+    split = {"train": train_nid.to(dev), "valid": val_nid.to(dev), "test": test_nid.to(dev)}
+    accs = ops.split_accuracy(logits, labels.view(-1), split)
+    return logits, tuple(accs.tolist())

@@ -376,11 +376,13 @@ def pad_pitch(t: Tensor) -> Tensor:
 
 def gemm_raw(a: Tensor, b: Tensor, trans_a: bool = False, trans_b: bool = False, bias: Tensor | None = None,
              alpha: float = 1.0, split_k: int | None = None, a_rows: Tensor | None = None, b_rows: Tensor | None = None,
-             relu: bool = False, addend: Tensor | None = None) -> Tensor:
+             relu: bool = False, addend: Tensor | None = None, out: Tensor | None = None) -> Tensor:
     """C = alpha * op(a) @ op(b) (+ bias) (+ addend [M,N], added in the kernel's store) via egnn_gemm_f32 / egnn_gemm_rows_f32.
 
     a_rows [M] (trans_a False): op(a) = a[a_rows];  b_rows [K] (trans_b False): b = b[b_rows] -- the gather is fused
-    into the operand load."""
+    into the operand load.
+    ``out``: a caller-owned float32 [M, N] view with unit column stride and ``out.stride(0) >= N`` (a column block of a wider
+    buffer) that receives the product and is returned; None allocates."""
     _lib.require_gpu(a, b)
     a, b = _gemm_operand(a), _gemm_operand(b)
     if a_rows is not None:
@@ -393,6 +395,11 @@ def gemm_raw(a: Tensor, b: Tensor, trans_a: bool = False, trans_b: bool = False,
         Kb, N = (b.shape[1], b.shape[0]) if trans_b else b.shape
     if K != Kb:
         raise ValueError(f"gemm: inner dimensions differ ({K} vs {Kb})")
+    if out is not None:
+        _lib.require_gpu(out)
+        if (out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (M, N) or out.device != a.device
+                or (N > 1 and out.stride(1) != 1) or (M > 1 and out.stride(0) < N)):
+            raise ValueError(f"gemm_raw: `out` must be a float32 [{M}, {N}] view with unit column stride and a row pitch >= {N}")
     if K == 0 or M == 0 or N == 0:
         # an empty reduction (dW = dY^T X[rows] on a shard that owns no train row) or an empty output: exact zeros (+ bias / addend),
         # no launch -- the entry points take non-null operands only
@@ -401,8 +408,10 @@ def gemm_raw(a: Tensor, b: Tensor, trans_a: bool = False, trans_b: bool = False,
             c += bias
         if addend is not None:
             c += addend
-        return c.clamp_(min=0) if relu else c
-    c = torch.empty(M, N, dtype=torch.float32, device=a.device)
+        c = c.clamp_(min=0) if relu else c
+        return c if out is None else out.copy_(c)
+    c = torch.empty(M, N, dtype=torch.float32, device=a.device) if out is None else out
+    ldc = c.stride(0) if M > 1 else max(c.stride(0), N)
     if split_k is None:
         # reductions over many rows into a small output (dW = X^T dY): spread K over the chip
         # (two workgroups per CU = 512 slots: 2 or 4 output tiles take 128 ranges -- 163 vs 178 us on 256 x 256 x 169 343, 106 vs 140 us on
@@ -422,18 +431,18 @@ def gemm_raw(a: Tensor, b: Tensor, trans_a: bool = False, trans_b: bool = False,
             raise ValueError("gemm_raw: `addend` is an [M, N] matrix (no fused gather, no ReLU)")
         addend = _rowmajor(addend)
         rc = lib.egnn_gemm_add_f32(int(trans_a), int(trans_b), M, N, K, float(alpha), _lib.ptr(a), a.stride(0), _lib.ptr(b), b.stride(0),
-                                   _lib.ptr(bias), _lib.ptr(addend), addend.stride(0), _lib.ptr(c), c.stride(0), split_k, _lib.ptr(ws),
+                                   _lib.ptr(bias), _lib.ptr(addend), addend.stride(0), _lib.ptr(c), ldc, split_k, _lib.ptr(ws),
                                    0 if ws is None else ws.numel() * 4, _lib.stream())
         _lib.check(rc, "egnn_gemm_add_f32")
     elif a_rows is None and b_rows is None:
         rc = lib.egnn_gemm_ex_f32(int(trans_a), int(trans_b), M, N, K, float(alpha), _lib.ptr(a), a.stride(0), _lib.ptr(b),
-                                  b.stride(0), _lib.ptr(bias), _lib.ptr(c), c.stride(0), split_k, _lib.ptr(ws),
+                                  b.stride(0), _lib.ptr(bias), _lib.ptr(c), ldc, split_k, _lib.ptr(ws),
                                   0 if ws is None else ws.numel() * 4, 1 if relu else 0, _lib.stream())
         _lib.check(rc, "egnn_gemm_ex_f32")
     else:
         _lib.require_gpu(*(t for t in (a_rows, b_rows) if t is not None))
         rc = lib.egnn_gemm_rows_f32(int(trans_a), int(trans_b), M, N, K, float(alpha), _lib.ptr(a), a.stride(0), _lib.ptr(a_rows),
-                                    _lib.ptr(b), b.stride(0), _lib.ptr(b_rows), _lib.ptr(bias), _lib.ptr(c), c.stride(0), split_k,
+                                    _lib.ptr(b), b.stride(0), _lib.ptr(b_rows), _lib.ptr(bias), _lib.ptr(c), ldc, split_k,
                                     _lib.ptr(ws), 0 if ws is None else ws.numel() * 4, _lib.stream())
         _lib.check(rc, "egnn_gemm_rows_f32")
         if relu:
@@ -481,8 +490,18 @@ class _MatMul(torch.autograd.Function):
         return _fresh(gx, ctx.tap_box), gw, gb, None
 
 
-def matmul(x: Tensor, w: Tensor, bias: Tensor | None = None) -> Tensor:
-    """x [M,K] @ w [K,N] (+ bias [N], added in the GEMM's store)."""
+def _matmul_into(x, w, bias, transposed, out):
+    """The ``out=`` form of matmul / linear: the product lands in the caller's view.  Forward-only, like ``spmm(addend=...)``: an
+    autograd node cannot hand out a view of somebody else's buffer; the hop-batched Functions (``linear_blocks``) own theirs."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, bias)):
+        raise NotImplementedError("matmul / linear (out=...) is a forward-only form")
+    return gemm_raw(x, w, False, transposed, bias, out=out)
+
+
+def matmul(x: Tensor, w: Tensor, bias: Tensor | None = None, out: Tensor | None = None) -> Tensor:
+    """x [M,K] @ w [K,N] (+ bias [N], added in the GEMM's store); ``out``: see ``gemm_raw`` (forward-only)."""
+    if out is not None:
+        return _matmul_into(x, w, bias, False, out)
     return _MatMul.apply(x, w, bias, False)
 
 
@@ -781,8 +800,10 @@ def linear_rows(x: Tensor, idx: Tensor, weight: Tensor, bias: Tensor | None = No
     return _LinearRows.apply(x, idx, weight, bias, getattr(x, "_egnn_tap", None) if torch.is_grad_enabled() else None, const_input)
 
 
-def linear(x: Tensor, weight: Tensor, bias: Tensor | None = None) -> Tensor:
-    """x @ weight^T + bias with ``weight`` in nn.Linear layout [out, in]."""
+def linear(x: Tensor, weight: Tensor, bias: Tensor | None = None, out: Tensor | None = None) -> Tensor:
+    """x @ weight^T + bias with ``weight`` in nn.Linear layout [out, in]; ``out``: see ``gemm_raw`` (forward-only)."""
+    if out is not None:
+        return _matmul_into(x, weight, bias, True, out)
     return _MatMul.apply(x, weight, bias, True)
 
 
@@ -1440,3 +1461,211 @@ def sync_bn_act_linear(x: Tensor, bn, w: Tensor, relu: bool, p: float, training:
 
 def bn_shape_ok(x: Tensor) -> bool:
     return _bn_shape_ok(_rowmajor(x))
+
+
+# ------------------------------------------------------------------------------------------------
+# SIGN: hop-batched Linear -> PReLU -> dropout (csrc/sign.hip; /root/reference/arxiv_dgl/sign.py:105-162)
+# ------------------------------------------------------------------------------------------------
+_SIGN_MAX_SEG = 16
+
+
+def _sign_seeds(H: int, p: float, training: bool, seeds):
+    """One dropout seed per segment, drawn in segment order -- and only when a mask is drawn at all (``training and p > 0``);
+    ``seeds``: the caller drew them already (models.SIGN draws in the reference's dropout call order)."""
+    if not (training and p > 0):
+        return None
+    if seeds is None:
+        seeds = [_draw_dropout_seed() for _ in range(H)]
+    if len(seeds) != H:
+        raise ValueError(f"expected {H} dropout seeds, got {len(seeds)}")
+    return tuple(int(s) for s in seeds)
+
+
+def _sign_desc(B, Cs, H, p, seeds, slopes=None, srcs=None, batch=None):
+    """The egnn_sign_seg_t descriptor (include/egnn_hip.h) and the host arrays it points at (kept alive by the returned tuple)."""
+    u64 = (ctypes.c_uint64 * H)(*(seeds if seeds is not None else [0] * H))
+    keep = [u64]
+    d = _lib.SignSeg()
+    d.B, d.Cs, d.H = B, Cs, H
+    d.p = float(p) if seeds is not None else 0.0
+    d.seed = ctypes.addressof(u64) if seeds is not None else None
+    d.seed_dev = _lib.ptr(_DROPOUT_SEED_DEV) if seeds is not None else None
+    if slopes is not None:
+        arr = (ctypes.c_void_p * H)(*[t.data_ptr() for t in slopes])
+        keep.append(arr)
+        d.slope = ctypes.addressof(arr)
+    if srcs is not None:
+        arr = (ctypes.c_void_p * H)(*[t.data_ptr() for t in srcs])
+        lds = (ctypes.c_int64 * H)(*[t.stride(0) for t in srcs])
+        keep += [arr, lds]
+        d.src, d.ld_src, d.n_src = ctypes.addressof(arr), ctypes.addressof(lds), srcs[0].shape[0]
+        d.batch = _lib.ptr(batch)
+    return d, keep
+
+
+def sign_gather_drop(feats, batch: Tensor, p: float, training: bool, seeds=None) -> Tensor:
+    """``torch.cat([F.dropout(x[batch], p, training) for x in feats], 1)`` -> [B, H*F] in ONE launch (egnn_sign_gather_drop_f32): the
+    batch gather, ``input_drop`` and the layout the first Linear of every hop reads (sign.py:236,151).  The hop features are
+    constants: no backward.  One seed per hop from ``_draw_dropout_seed``, in hop order (``training and p > 0`` only)."""
+    feats = [_rowmajor(_lib.real(f)) for f in feats]
+    _lib.require_gpu(batch, *feats)
+    H = len(feats)
+    if any(f.requires_grad for f in feats) and torch.is_grad_enabled():
+        raise NotImplementedError("sign_gather_drop: the hop features are constants (no backward)")
+    if H == 0 or any(f.shape != feats[0].shape for f in feats):
+        raise ValueError("sign_gather_drop: expected hop feature matrices of one shape")
+    if H > _SIGN_MAX_SEG:
+        raise _lib.HipExtensionError(f"sign_gather_drop: at most {_SIGN_MAX_SEG} hops per call")
+    if batch.dtype != torch.int64 or batch.dim() != 1:
+        raise TypeError("sign_gather_drop: `batch` must be an int64 vector of row ids")
+    batch = batch.contiguous()
+    N, Fdim = feats[0].shape
+    B = batch.numel()
+    seeds = _sign_seeds(H, p, training, seeds)
+    out = torch.empty(B, H * Fdim, dtype=torch.float32, device=feats[0].device)
+    if B > 0 and Fdim > 0:
+        d, keep = _sign_desc(B, Fdim, H, p, seeds, srcs=feats, batch=batch)
+        _lib.check(_lib.load().egnn_sign_gather_drop_f32(ctypes.byref(d), _lib.ptr(out), out.stride(0), _lib.stream()),
+                   "egnn_sign_gather_drop_f32")
+    return out
+
+
+class _PreluDrop(torch.autograd.Function):
+    """y = drop(prelu(z, a_h)) per column segment of z [B, H*Cs]; saves z (never a mask).  The backward forms dz, every slope gradient
+    and the column sums of dz in one pass; dz carries the column sums (``_egnn_colsum``) for the Linear that produced z."""
+
+    @staticmethod
+    def forward(ctx, z, Cs, p, seeds, *slopes):
+        z = _rowmajor(z)
+        B, HC = z.shape
+        H = len(slopes)
+        y = torch.empty(B, HC, dtype=torch.float32, device=z.device)
+        if B > 0:
+            d, keep = _sign_desc(B, Cs, H, p, seeds, slopes=slopes)
+            _lib.check(_lib.load().egnn_prelu_drop_fwd_f32(ctypes.byref(d), _lib.ptr(z), z.stride(0), _lib.ptr(y), y.stride(0),
+                                                           _lib.stream()), "egnn_prelu_drop_fwd_f32")
+        ctx.save_for_backward(z, *slopes)
+        ctx.cfg = (int(Cs), float(p), seeds)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        z, *slopes = ctx.saved_tensors
+        Cs, p, seeds = ctx.cfg
+        gy = _rowmajor(gy)
+        B, HC = z.shape
+        H, dev = len(slopes), z.device
+        lib = _lib.load()
+        dz = torch.empty(B, HC, dtype=torch.float32, device=dev)
+        if B == 0:
+            return (dz, None, None, None, *[torch.zeros_like(a) for a in slopes])
+        da = torch.empty(H, dtype=torch.float32, device=dev)
+        cs = torch.empty(HC, dtype=torch.float32, device=dev)
+        nws = lib.egnn_prelu_drop_ws_floats(B, Cs, H)
+        ws = torch.empty(nws, dtype=torch.float32, device=dev)
+        d, keep = _sign_desc(B, Cs, H, p, seeds, slopes=slopes)
+        _lib.check(lib.egnn_prelu_drop_bwd_f32(ctypes.byref(d), _lib.ptr(z), z.stride(0), _lib.ptr(gy), gy.stride(0), _lib.ptr(dz),
+                                               dz.stride(0), _lib.ptr(da), _lib.ptr(cs), _lib.ptr(ws), nws, _lib.stream()),
+                   "egnn_prelu_drop_bwd_f32")
+        dz._egnn_colsum = (cs, dz._version)
+        return (dz, None, None, None, *[da[h:h + 1].view(a.shape) for h, a in enumerate(slopes)])
+
+
+def prelu_drop(z: Tensor, slopes, Cs: int, p: float, training: bool, seeds=None) -> Tensor:
+    """``F.dropout(F.prelu(z_h, a_h), p, training)`` for every column segment z_h = z[:, h*Cs:(h+1)*Cs] in ONE launch
+    (egnn_prelu_drop_fwd_f32 / _bwd_f32; sign.py:132,155).  ``slopes``: one learnable one-element tensor per segment, read from
+    device memory by every launch.  One seed per segment from ``_draw_dropout_seed`` in segment order, only when ``training and
+    p > 0`` (``seeds``: already drawn by the caller).  Gradients: z and every slope."""
+    z = _lib.real(z)
+    slopes = list(slopes)
+    _lib.require_gpu(z, *slopes)
+    H = len(slopes)
+    if z.dim() != 2 or H < 1 or z.shape[1] != H * Cs:
+        raise ValueError(f"prelu_drop: z must be [B, {H} * {Cs}]")
+    if any(a.numel() != 1 or a.dtype != torch.float32 for a in slopes):
+        raise ValueError("prelu_drop: every slope is a one-element float32 tensor (nn.PReLU())")
+    if H > _SIGN_MAX_SEG:
+        raise _lib.HipExtensionError(f"prelu_drop: at most {_SIGN_MAX_SEG} segments per call")
+    return _PreluDrop.apply(z, int(Cs), float(p), _sign_seeds(H, p, training, seeds), *slopes)
+
+
+def _block_operand(x, h: int, H: int, rows):
+    """(A operand, a_rows) of hop h: a column block of the shared [B, H*Cin] buffer, or hop h's own matrix with the rows ``rows``
+    (int64 ids: gathered in the GEMM's operand load; a ``range``: a slice; None: all)."""
+    if torch.is_tensor(x):
+        Cin = x.shape[1] // H
+        return x[:, h * Cin:(h + 1) * Cin], None
+    if isinstance(rows, range):
+        return x[h][rows.start:rows.stop], None
+    return x[h], rows
+
+
+class _LinearBlocks(torch.autograd.Function):
+    """z[:, h*Cout:(h+1)*Cout] = x_h @ W_h^T + b_h for H hops as ONE autograd node over ONE [B, H*Cout] buffer: every GEMM writes its
+    column block (``gemm_raw(out=)``: no torch.cat), the backward reads the blocks of dz as strided operands (no split copy), writes
+    dX into the blocks of one buffer, and takes the bias gradients from the column sums dz carries (``colsum``)."""
+
+    @staticmethod
+    def forward(ctx, x, rows, H, *tensors):
+        feats, ws, bs = tensors[:len(tensors) - 2 * H], tensors[len(tensors) - 2 * H:len(tensors) - H], tensors[len(tensors) - H:]
+        src = x if x is not None else [_gemm_operand(f) for f in feats]
+        a0, r0 = _block_operand(src, 0, H, rows)
+        B = a0.shape[0] if r0 is None else r0.numel()
+        Cout = ws[0].shape[0]
+        z = torch.empty(B, H * Cout, dtype=torch.float32, device=ws[0].device)
+        for h in range(H):
+            a, r = _block_operand(src, h, H, rows)
+            gemm_raw(a, ws[h], False, True, bs[h], a_rows=r, out=z[:, h * Cout:(h + 1) * Cout])
+        ctx.save_for_backward(*([x] if x is not None else []), *([rows] if torch.is_tensor(rows) else []), *feats, *ws)
+        ctx.cfg = (H, x is not None, rows if not torch.is_tensor(rows) else "tensor", len(feats))
+        ctx.tap_box = getattr(x, "_egnn_tap", None) if x is not None else None
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        H, has_x, rows, n_feat = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        x = saved.pop(0) if has_x else None
+        if rows == "tensor":
+            rows = saved.pop(0)
+        feats, ws = saved[:n_feat], saved[n_feat:]
+        src = x if has_x else feats
+        gz = _rowmajor(gz)
+        Cout = ws[0].shape[0]
+        need_w, need_b = ctx.needs_input_grad[3 + n_feat:3 + n_feat + H], ctx.needs_input_grad[3 + n_feat + H:]
+        cs = colsum(gz) if any(need_b) else None
+        gx = torch.empty_like(x) if has_x and ctx.needs_input_grad[0] else None
+        gws, gbs = [], []
+        for h in range(H):
+            g = gz[:, h * Cout:(h + 1) * Cout]
+            a, r = _block_operand(src, h, H, rows)
+            if gx is not None:
+                Cin = x.shape[1] // H
+                gemm_raw(g, ws[h], False, False, out=gx[:, h * Cin:(h + 1) * Cin])        # dX_h = dZ_h W_h
+            gws.append(gemm_raw(g, a, True, False, b_rows=r) if need_w[h] else None)      # dW_h = dZ_h^T X_h
+            gbs.append(cs[h * Cout:(h + 1) * Cout] if need_b[h] else None)
+        return (_fresh(gx, ctx.tap_box), None, None, *([None] * n_feat), *gws, *gbs)
+
+
+def linear_blocks(x, weights, biases, rows=None) -> Tensor:
+    """H independent ``nn.Linear`` layers over the H hops into ONE [B, H*out] buffer (block-diagonal product; sign.py:130 for every hop
+    of one level).  ``x``: the previous level's [B, H*in] buffer, or a list of the H constant hop feature matrices [N, in] whose rows
+    ``rows`` are used (int64 ids, fused into the operand load; a ``range``: a slice; None: all rows).  ``weights`` [out, in] and
+    ``biases`` [out] per hop, all of one shape."""
+    weights, biases = list(weights), list(biases)
+    H = len(weights)
+    if H < 1 or len(biases) != H or any(w.shape != weights[0].shape for w in weights) or any(b is None for b in biases):
+        raise ValueError("linear_blocks: one [out, in] weight and one bias per hop, all of one shape")
+    if torch.is_tensor(x):
+        x = _lib.real(x)
+        _lib.require_gpu(x)
+        if x.dim() != 2 or x.shape[1] != H * weights[0].shape[1] or rows is not None:
+            raise ValueError("linear_blocks: a shared input buffer is [B, H * in] and takes no `rows`")
+        return _LinearBlocks.apply(_rowmajor(x), None, H, *weights, *biases)
+    feats = [_lib.real(f) for f in x]
+    _lib.require_gpu(*feats)
+    if len(feats) != H or any(f.requires_grad for f in feats):
+        raise ValueError("linear_blocks: one constant feature matrix per hop")
+    if torch.is_tensor(rows):
+        _lib.require_gpu(rows)
+    return _LinearBlocks.apply(None, rows, H, *feats, *weights, *biases)

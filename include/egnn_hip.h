@@ -659,6 +659,45 @@ int egnn_saint_gather_i64(const int64_t* node_idx, int64_t n_sub, const int64_t*
                           const uint8_t* train_mask, int64_t* o_node_type, int64_t* o_local_idx, int64_t* o_y, uint8_t* o_train_mask,
                           const int64_t* edge_idx, int64_t e_sub, const int64_t* edge_attr, int64_t* o_edge_attr, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * SIGN student (/root/reference/arxiv_dgl/sign.py:105-162): Linear -> PReLU -> dropout with a learnable scalar slope, replicated
+ * over the R + 1 hops and concatenated; csrc/sign.hip.  Each entry point is ONE launch for all hops (the backward adds a
+ * fixed-order finalize launch); deterministic, no float atomics.
+ * "Segment" h = the columns [h*Cs, (h+1)*Cs) of a row-major [B, H*Cs] matrix with leading dimension ld >= H*Cs; H <= 16
+ * (more: EGNN_EINVAL, no launch).  The operands travel as ONE descriptor, egnn_sign_seg_t, read only while the call runs (it
+ * may live on the caller's stack).  seed, slope, src and ld_src are HOST arrays of H entries: the entry point copies them into
+ * the kernel arguments (no device allocation, no host-to-device copy besides the kernel arguments), so the pointers in `slope`
+ * are read by the kernel on every launch -- slopes are parameters, nothing is baked in.
+ *   dropout: the convention of the fused BatchNorm above; the uniform of element (r, c) of segment h is a counter hash of
+ *   (seed[h] + *seed_dev, r * Cs + (c - h*Cs)), keep where u >= p, kept values scaled 1 / (1 - p); seed_dev nullable (0).
+ *   p == 0: no mask (seed may be NULL).  Masks are recomputed by the backward, never stored.
+ * 16-byte vector path when Cs % 4 == 0, every ld % 4 == 0 and every matrix pointer is 16-byte aligned; a scalar path in the
+ * same entry point otherwise (any Cs, any ld).
+ *   egnn_sign_gather_drop_f32   out[i, h*Cs + c] = drop_h(src[h][batch[i], c]), i < B: the `[x[batch] for x in feats]` gather,
+ *                               `input_drop` and the operand of the first Linear of every hop (sign.py:236,308 and :151) in one
+ *                               pass; src[h] [n_src, ld_src[h] >= Cs]; batch int64 [B] with ids in [0, n_src); no backward (the hop
+ *                               features are constants).  Reads src, ld_src, n_src, batch; slope is not read.
+ *   egnn_prelu_drop_fwd_f32     y = drop(prelu(z, *slope[h])), prelu(z, a) = z > 0 ? z : a*z: `self.dropout(self.prelu(x))` of
+ *                               sign.py:132 for all hops of one level, and :155 over the concatenation.  p == 0: eval mode.
+ *   egnn_prelu_drop_bwd_f32     from z, dy and the same seeds, one pass:  dz = dy * m * (z > 0 ? 1 : a_h);
+ *                               da [H]: da[h] = sum over segment h of dy * m * (z > 0 ? 0 : z)  (the PReLU weight gradient);
+ *                               dbias [H*Cs]: dbias[c] = sum_r dz[r, c]  (the bias gradient of the nn.Linear that formed z,
+ *                               sign.py:130 -- ATen: a second pass, dz.sum(0)).  B >= 1.
+ *                               ws: egnn_prelu_drop_ws_floats(B, Cs, H) floats (else EGNN_EWORKSPACE).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct egnn_sign_seg {
+  int64_t B; int64_t Cs; int H;                          /* B rows, H segments of Cs columns */
+  float p; const uint64_t* seed; const uint64_t* seed_dev;   /* seed: host [H]; seed_dev: device scalar, nullable */
+  const float* const* slope;                             /* prelu: host [H] of device pointers to the scalar slopes */
+  const float* const* src; const int64_t* ld_src; int64_t n_src;   /* gather: host [H] source matrices [n_src, ld_src[h]] */
+  const int64_t* batch;                                  /* gather: device int64 [B] row ids */
+} egnn_sign_seg_t;
+int egnn_sign_gather_drop_f32(const egnn_sign_seg_t* seg, float* out, int64_t ld_out, void* stream);
+int egnn_prelu_drop_fwd_f32(const egnn_sign_seg_t* seg, const float* z, int64_t ld_z, float* y, int64_t ld_y, void* stream);
+size_t egnn_prelu_drop_ws_floats(int64_t B, int64_t Cs, int H);
+int egnn_prelu_drop_bwd_f32(const egnn_sign_seg_t* seg, const float* z, int64_t ld_z, const float* dy, int64_t ld_dy, float* dz,
+                            int64_t ld_dz, float* da, float* dbias, float* ws, size_t ws_floats, void* stream);
+
 /* DIAGNOSTIC (measurement only; bench.py's roofline.gather_ceiling_GBs): replays the gather stream of one aggregation call and
  * nothing else -- for every stored entry e, the 128-byte slice s of row col[e] of X [n_src, K] is read by an 8-lane sub-group,
  * slice s by the workgroups with blockIdx % (K / 32) == s (the aggregation kernel's slice <-> XCD binding,
