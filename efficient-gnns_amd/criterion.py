@@ -5,6 +5,9 @@ so ``from criterion import *`` in the reference's train loops resolves unchanged
 Paper names: LSP = ``lpw_criterion``, GSP = ``gpw_criterion``, G-CRD = ``nce_criterion``.
 ``loss_aux`` carries its own autograd graph (gnn_kd_and_aux.py:121-127 recombines it).
 Host-RNG coupling is preserved: one ``np.random.choice(n, S, replace=False)`` per gpw/nce call when S < n.
+
+``distill`` is the package's single mode table: the training loops of models.py (arxiv, PPI, MAG, SIGN) name a mode and hand
+it their prepared features; it picks the criterion, reads the ``hp`` keys and forms the KD + auxiliary sum.
 """
 from __future__ import annotations
 
@@ -13,7 +16,7 @@ import torch
 
 from . import ops
 
-__all__ = ["kd_criterion", "fitnet_criterion", "at_criterion", "gpw_criterion", "lpw_criterion", "nce_criterion",
+__all__ = ["distill", "kd_criterion", "fitnet_criterion", "at_criterion", "gpw_criterion", "lpw_criterion", "nce_criterion",
            "loss_kd_only", "ppi_kd_criterion", "ppi_fitnet_criterion", "ppi_at_criterion", "ppi_gpw_criterion", "ppi_lpw_criterion",
            "ppi_nce_criterion"]
 
@@ -207,3 +210,45 @@ def ppi_kd_criterion(logits, labels, teacher_logits, alpha=0.5, T=1):
     from .ops_pairwise import bce_with_logits_pair
     loss_cls, loss_kd = bce_with_logits_pair(_plain(logits), _plain(labels), _plain(teacher_logits))
     return loss_kd * (alpha * T * T) + loss_cls * (1 - alpha), loss_cls, loss_kd
+
+
+def presample(mode, n, hp, device):
+    """The one host draw of a sampled criterion (``gpw`` / ``nce``) made ahead of it, for a caller whose projection heads then form
+    only the drawn rows (``distill(..., presampled=True)``).  None: the mode keeps every row."""
+    return _sample_rows(n, hp["max_samples"], device) if mode in ("gpw", "nce") else None
+
+
+def distill(mode, logits, labels, feat, teacher_feat, hp, *, teacher_logits=None, rows=None, edge_index=None, presampled=False,
+            multilabel=False, kd_and_aux=False):
+    """The mode table of every training loop outside dist.py: ``(loss, loss_cls, loss_aux)`` of distillation mode ``mode`` with the
+    hyper-parameters ``hp`` (alpha / kd_T: kd; beta; kernel: gpw / lpw; max_samples: gpw / nce; nce_T: nce).  ``feat`` /
+    ``teacher_feat`` arrive prepared (rows, projection heads and ``edge_index`` are the caller's business); ``rows``: ``logits`` /
+    ``labels`` / ``teacher_logits`` are full size and the classification / KD terms read these rows.  ``multilabel``: the BCE
+    classification term of the PPI scripts.  ``kd_and_aux`` (gnn_kd_and_aux.py:121-127): the KD loss plus ``beta * loss_aux``."""
+    cls = _bce_term if multilabel else None
+
+    def kd():
+        if not multilabel:
+            return rows_kd_criterion(logits, labels, teacher_logits, hp["alpha"], hp["kd_T"], rows=rows)
+        picked = (logits, labels, teacher_logits) if rows is None else (logits[rows], labels[rows], teacher_logits[rows])
+        return ppi_kd_criterion(*picked, hp["alpha"], hp["kd_T"])
+    if mode == "kd":
+        return kd()
+    if mode == "fitnet":
+        res = rows_fitnet_criterion(logits, labels, feat, teacher_feat, hp["beta"], rows=rows, _cls=cls)
+    elif mode == "at":
+        res = rows_at_criterion(logits, labels, feat, teacher_feat, hp["beta"], rows=rows, _cls=cls)
+    elif mode == "gpw":
+        res = rows_gpw_criterion(logits, labels, feat, teacher_feat, hp["kernel"], hp["beta"], hp["max_samples"], rows=rows,
+                                 presampled=presampled, _cls=cls)
+    elif mode == "lpw":
+        res = rows_lpw_criterion(logits, labels, feat, teacher_feat, edge_index, hp["kernel"], hp["beta"], rows=rows, _cls=cls)
+    elif mode in ("nce", "gcd"):
+        res = rows_nce_criterion(logits, labels, feat, teacher_feat, hp["beta"], hp["nce_T"], hp["max_samples"], rows=rows,
+                                 presampled=presampled, _cls=cls)
+    else:
+        raise NotImplementedError(mode)
+    if not kd_and_aux:
+        return res
+    loss, loss_cls, _ = kd()
+    return loss + hp["beta"] * res[2], loss_cls, res[2]

@@ -26,9 +26,7 @@ _EVAL_BN_FOLD = True   # (no environment switch any more; tests flip the attribu
 # Fusions measured in round 3 (profiles/r03_bench_line_r02_paths.json: all five off = 130.5 vs 144.3 epochs/s); module attributes, no
 # environment switches -- tests flip them to compare each fused form with its composed one.
 _TRAIN_ROWS = True        # [train_idx] row picks inside the CE / KD kernels
-_LSP_FULL_ROWS = True     # LSP on the full tensors through composed edge ids
 _FUSED_TAIL = True        # ops.bn_act_linear for the last hidden layer of a GCN
-_SAMPLED_HEADS = True     # projection heads form only the rows a sampled criterion keeps
 
 
 class _Student(nn.Module):
@@ -187,26 +185,24 @@ def distill_loss(mode, model, out, labels, train_idx, teacher_out_feat, teacher_
                  student_proj=None, teacher_proj=None, edge_index=None, adj_t=None, kd_and_aux=False, rows=None):
     """``rows`` = None: ``out`` / ``labels`` are the compact train rows (gnn.py:109-110).  ``rows`` = train_idx: they are the FULL
     logits / labels and the criteria pick the rows inside their kernels (criterion.py's ``rows`` keyword)."""
-    kd_teacher = (lambda: teacher_logits) if rows is not None else (lambda: _const_rows(teacher_logits, train_idx))
     if mode == "supervised":
         loss = ops.cross_entropy(out, labels, rows)
         return loss, loss, loss * 0
-    if mode == "kd":
-        return C.rows_kd_criterion(out, labels, kd_teacher(), hp["alpha"], hp["kd_T"], rows=rows)
+    if rows is None and (mode == "kd" or kd_and_aux):      # the only modes that form a KD term: no gather launch in the others
+        teacher_logits = _const_rows(teacher_logits, train_idx)
+    f = t = None
     picked = False
     if mode in ("fitnet", "gpw", "nce"):
         if hasattr(student_proj, "forward_rows") and hasattr(teacher_proj, "forward_rows") and not _CACHE_CONST_ROWS:
-            pick = None
-            if mode in ("gpw", "nce") and _SAMPLED_HEADS:
-                # the criterion's one host draw (criterion.py:62-65,134-137), made here: the heads then form only the sampled rows
-                pick = C._sample_rows(train_idx.numel(), hp["max_samples"], model.out_feat.device)
-                picked = pick is not None
+            # the criterion's one host draw (criterion.py:62-65,134-137), made here: the heads then form only the sampled rows
+            pick = C.presample(mode, train_idx.numel(), hp, model.out_feat.device)
+            picked = pick is not None
             f = student_proj.forward_rows(model.out_feat, train_idx, pick=pick)   # proj(feat[train_idx]) without the copies
             t = teacher_proj.forward_rows(teacher_out_feat, train_idx, pick=pick, const_input=True)   # the teacher's features never change (gnn.py:155)
         else:
             f = student_proj(ops.take_rows(model.out_feat, train_idx))
             t = teacher_proj(_const_rows(teacher_out_feat, train_idx))
-    elif mode == "lpw" and _LSP_FULL_ROWS and edge_index is not None:
+    elif mode == "lpw" and edge_index is not None:
         # LSP reads rows only through the edge list (criterion.py:100-104): the train-subgraph ids of gnn.py:274 are composed with
         # train_idx once, and the edge kernels then address the FULL feature tensors -- feat[train_idx] / teacher_feat[train_idx] (366 MB of
         # copies per step) and the zero-fill + scatter of their backward never exist; the loss is a mean over the same edges.
@@ -216,23 +212,8 @@ def distill_loss(mode, model, out, labels, train_idx, teacher_out_feat, teacher_
     elif mode == "gcd":
         f = student_proj(model.out_feat, adj_t)[train_idx]
         t = teacher_proj(teacher_out_feat, adj_t)[train_idx]
-    else:
-        raise NotImplementedError(mode)
-    if mode == "fitnet":
-        res = C.rows_fitnet_criterion(out, labels, f, t, hp["beta"], rows=rows)
-    elif mode == "at":
-        res = C.rows_at_criterion(out, labels, f, t, hp["beta"], rows=rows)
-    elif mode == "gpw":
-        res = C.rows_gpw_criterion(out, labels, f, t, hp["kernel"], hp["beta"], hp["max_samples"], rows=rows, presampled=picked)
-    elif mode == "lpw":
-        res = C.rows_lpw_criterion(out, labels, f, t, edge_index, hp["kernel"], hp["beta"], rows=rows)
-    else:
-        res = C.rows_nce_criterion(out, labels, f, t, hp["beta"], hp["nce_T"], hp["max_samples"], rows=rows, presampled=picked)
-    if not kd_and_aux:
-        return res
-    loss_aux = res[2]
-    loss, loss_cls, _ = C.rows_kd_criterion(out, labels, kd_teacher(), hp["alpha"], hp["kd_T"], rows=rows)
-    return loss + hp["beta"] * loss_aux, loss_cls, loss_aux
+    return C.distill(mode, out, labels, f, t, hp, teacher_logits=teacher_logits, rows=rows, edge_index=edge_index, presampled=picked,
+                     kd_and_aux=kd_and_aux)
 
 
 _ONES: dict = {}
@@ -248,15 +229,22 @@ def _one_like(t):
     return one
 
 
+def train_mode(model, student_proj=None, teacher_proj=None, teacher_model=None):
+    """What every training loop sets before its first step: student and projection heads train, the frozen teacher evaluates."""
+    model.train()
+    for p in (student_proj, teacher_proj):
+        if p is not None:
+            p.train()
+    if teacher_model is not None:
+        teacher_model.eval()
+
+
 def train_step_tensors(model, x, adj_t, y, train_idx, optimizer, mode, hp, teacher_out_feat=None, teacher_logits=None,
                        student_proj=None, teacher_proj=None, edge_index=None, kd_and_aux=False, out=None):
     """One full-graph optimisation step (gnn.py:102-195) WITHOUT the host reads: returns the device tensor
     [loss, loss_cls, loss_aux] (written into ``out`` -- float32 [3] -- when given).  (``train_step`` adds the reads; ``GraphedEpoch``
     captures this function.)"""
-    model.train()
-    for p in (student_proj, teacher_proj):
-        if p is not None:
-            p.train()
+    train_mode(model, student_proj, teacher_proj)
     logits = model(x, adj_t)
     if _TRAIN_ROWS and logits.is_cuda and y.dim() == 2 and y.shape[1] == 1 and y.dtype == torch.int64:
         # gnn.py:109-110 `out = model(...)[train_idx]`, `y.squeeze(1)[train_idx]` (and `teacher_logits[train_idx]`): the row picks
@@ -264,9 +252,9 @@ def train_step_tensors(model, x, adj_t, y, train_idx, optimizer, mode, hp, teach
         loss, loss_cls, loss_aux = distill_loss(mode, model, logits, y.view(-1), train_idx, teacher_out_feat, teacher_logits, hp,
                                                 student_proj, teacher_proj, edge_index, adj_t, kd_and_aux, rows=train_idx)
     else:
-        out = ops.take_rows(logits, train_idx)   # == model(...)[train_idx] (split ids are unique)
+        picked = ops.take_rows(logits, train_idx)   # == model(...)[train_idx] (split ids are unique)
         labels = y.squeeze(1)[train_idx]
-        loss, loss_cls, loss_aux = distill_loss(mode, model, out, labels, train_idx, teacher_out_feat, teacher_logits, hp,
+        loss, loss_cls, loss_aux = distill_loss(mode, model, picked, labels, train_idx, teacher_out_feat, teacher_logits, hp,
                                                 student_proj, teacher_proj, edge_index, adj_t, kd_and_aux)
     optimizer.zero_grad()
     loss.backward(gradient=_one_like(loss) if loss.is_cuda and loss.dim() == 0 else None)
@@ -822,12 +810,7 @@ def ppi_train_epoch(model, teacher_model, graphs, optimizer, mode, hp, student_p
     Returns the epoch means (loss, loss_cls, loss_aux) like the reference."""
     if mode not in PPI_MODES:
         raise NotImplementedError(mode)
-    model.train()
-    for m in (student_proj, teacher_proj):
-        if m is not None:
-            m.train()
-    if teacher_model is not None:
-        teacher_model.eval()
+    train_mode(model, student_proj, teacher_proj, teacher_model)
     tot = [0.0, 0.0, 0.0]
     for g in graphs:
         out = model(g.x, g.edge_index)
@@ -838,22 +821,11 @@ def ppi_train_epoch(model, teacher_model, graphs, optimizer, mode, hp, student_p
             with torch.no_grad():
                 teacher_out = teacher_model(g.x, g.edge_index)
                 teacher_out_feat = teacher_model.out_feat
-            if mode == "kd":
-                loss, loss_cls, loss_aux = C.ppi_kd_criterion(out, g.y, teacher_out, hp["alpha"], hp["kd_T"])
-            elif mode == "fitnet":
-                loss, loss_cls, loss_aux = C.ppi_fitnet_criterion(out, g.y, student_proj(model.out_feat),
-                                                                  teacher_proj(teacher_out_feat), hp["beta"])
-            elif mode == "at":
-                loss, loss_cls, loss_aux = C.ppi_at_criterion(out, g.y, model.out_feat, teacher_out_feat, hp["beta"])
-            elif mode == "gpw":
-                loss, loss_cls, loss_aux = C.ppi_gpw_criterion(out, g.y, model.out_feat, teacher_out_feat, hp["kernel"], hp["beta"],
-                                                               hp["max_samples"])
-            elif mode == "lpw":
-                loss, loss_cls, loss_aux = C.ppi_lpw_criterion(out, g.y, model.out_feat, teacher_out_feat, g.edge_index, hp["kernel"],
-                                                               hp["beta"])
-            else:   # nce
-                loss, loss_cls, loss_aux = C.ppi_nce_criterion(out, g.y, student_proj(model.out_feat), teacher_proj(teacher_out_feat),
-                                                               hp["beta"], hp["nce_T"], hp["max_samples"])
+            f, t = model.out_feat, teacher_out_feat
+            if mode in ("fitnet", "nce"):
+                f, t = student_proj(f), teacher_proj(t)
+            loss, loss_cls, loss_aux = C.distill(mode, out, g.y, f, t, hp, teacher_logits=teacher_out, edge_index=g.edge_index,
+                                                 multilabel=True)
         optimizer.zero_grad()
         loss.backward()
         optimizer.step()
@@ -902,21 +874,15 @@ def mag_batch_loss(model, batch, x_dict, mode, hp, teacher_model=None, student_p
     with torch.no_grad():
         teacher_out = teacher_model(*args, relations=rel)
         teacher_feat = ops.take_rows(teacher_model.out_feat, rows)
-    if mode == "kd":
-        return C.rows_kd_criterion(out, labels, teacher_out, hp["alpha"], hp["kd_T"], rows=rows)
-    feat = ops.take_rows(model.out_feat, rows)
-    if mode == "fitnet":
-        return C.rows_fitnet_criterion(out, labels, student_proj(feat), teacher_proj(teacher_feat), hp["beta"], rows=rows)
-    if mode == "at":
-        return C.rows_at_criterion(out, labels, feat, teacher_feat, hp["beta"], rows=rows)
-    if mode == "gpw":
-        return C.rows_gpw_criterion(out, labels, feat, teacher_feat, hp["kernel"], hp["beta"], hp["max_samples"], rows=rows)
-    if mode == "lpw":
+    feat, edge_index = None, None
+    if mode != "kd":
+        feat = ops.take_rows(model.out_feat, rows)
+    if mode in ("fitnet", "nce"):
+        feat, teacher_feat = student_proj(feat), teacher_proj(teacher_feat)
+    elif mode == "lpw":
         from .utils import subgraph
         edge_index = subgraph(rows, batch.edge_index, relabel_nodes=True, num_nodes=batch.num_nodes)[0]
-        return C.rows_lpw_criterion(out, labels, feat, teacher_feat, edge_index, hp["kernel"], hp["beta"], rows=rows)
-    return C.rows_nce_criterion(out, labels, student_proj(feat), teacher_proj(teacher_feat), hp["beta"], hp["nce_T"], hp["max_samples"],
-                                rows=rows)
+    return C.distill(mode, out, labels, feat, teacher_feat, hp, teacher_logits=teacher_out, rows=rows, edge_index=edge_index)
 
 
 def mag_train_epoch(model, loader, x_dict, optimizer, mode, hp, teacher_model=None, student_proj=None, teacher_proj=None):
@@ -925,12 +891,7 @@ def mag_train_epoch(model, loader, x_dict, optimizer, mode, hp, teacher_model=No
     by the number of train rows of each batch, like the reference."""
     if mode not in MAG_MODES:
         raise NotImplementedError(mode)
-    model.train()
-    for m in (student_proj, teacher_proj):
-        if m is not None:
-            m.train()
-    if teacher_model is not None:
-        teacher_model.eval()
+    train_mode(model, student_proj, teacher_proj, teacher_model)
     tot, examples = [0.0, 0.0, 0.0], 0
     dev = next(model.parameters()).device
     for batch in loader:
@@ -1078,26 +1039,14 @@ def sign_batch_loss(model, feats, labels, batch, mode, hp, teacher_out_feat=None
     y = labels.view(-1)[batch]
     if mode == "supervised":
         return ops.cross_entropy(logits, y), None, None
-    kd = lambda: C.kd_criterion(logits, y, teacher_logits[batch], hp["alpha"], hp["kd_T"])   # noqa: E731
-    if mode == "kd":
-        return kd()
+    f = t = None
     if mode == "at":
         f, t = model.out_feat, teacher_out_feat[batch]
-        res = C.at_criterion(logits, y, f, t, hp["beta"])
-    else:
+    elif mode != "kd":
         f = student_proj(model.out_feat)
         t = teacher_proj.forward_rows(teacher_out_feat, batch) if hasattr(teacher_proj, "forward_rows") else teacher_proj(teacher_out_feat[batch])
-        if mode == "fitnet":
-            res = C.fitnet_criterion(logits, y, f, t, hp["beta"])
-        elif mode == "gpw":
-            res = C.gpw_criterion(logits, y, f, t, hp["kernel"], hp["beta"], hp["max_samples"])
-        else:
-            res = C.nce_criterion(logits, y, f, t, hp["beta"], hp["nce_T"], hp["max_samples"])
-    if not kd_and_aux:
-        return res
-    loss_aux = res[2]
-    loss, loss_cls, _ = kd()
-    return loss + hp["beta"] * loss_aux, loss_cls, loss_aux
+    kd_term = mode == "kd" or kd_and_aux
+    return C.distill(mode, logits, y, f, t, hp, teacher_logits=teacher_logits[batch] if kd_term else None, kd_and_aux=kd_and_aux)
 
 
 def sign_train_epoch(model, feats, labels, optimizer, batches, mode, hp, teacher_out_feat=None, teacher_logits=None,
@@ -1108,10 +1057,7 @@ def sign_train_epoch(model, feats, labels, optimizer, batches, mode, hp, teacher
     The per-step scalars stay on the device and are read once, at the end of the epoch."""
     if mode not in SIGN_MODES:
         raise NotImplementedError(mode)
-    model.train()
-    for m in (student_proj, teacher_proj):
-        if m is not None:
-            m.train()
+    train_mode(model, student_proj, teacher_proj)
     dev = labels.device
     _lib.require_gpu(labels, *feats)
     steps = []

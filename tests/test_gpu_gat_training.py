@@ -253,6 +253,54 @@ def test_ppi_gat_student_distillation_step_with_frozen_teacher(mode):
         close(a, b, rtol=2e-4, atol_scale=0)
 
 
+def _oracle_aux_step(mode, om, ot, g, opt, sp, tp, hp):
+    """``_oracle_nce_step`` for the other feature criteria: ``fitnet`` through the projection heads, ``at`` / ``gpw`` / ``lpw`` on the
+    hidden features themselves (ppi_pyg/gnn.py:213-262)."""
+    om.train(); ot.eval()
+    out = om(g.x, g.edge_index)
+    with torch.no_grad():
+        ot(g.x, g.edge_index)
+        t_feat = ot.out_feat
+    if mode == "fitnet":
+        sp.train(); tp.train()
+        loss, lc, la = OC.ppi_fitnet_criterion(out, g.y, sp(om.out_feat), tp(t_feat), hp["beta"])
+    elif mode == "at":
+        loss, lc, la = OC.ppi_at_criterion(out, g.y, om.out_feat, t_feat, hp["beta"])
+    elif mode == "gpw":
+        loss, lc, la = OC.ppi_gpw_criterion(out, g.y, om.out_feat, t_feat, hp["kernel"], hp["beta"], hp["max_samples"])
+    else:
+        loss, lc, la = OC.ppi_lpw_criterion(out, g.y, om.out_feat, t_feat, g.edge_index, hp["kernel"], hp["beta"])
+    opt.zero_grad(); loss.backward(); opt.step()
+    return loss.item(), lc.item(), la.item()
+
+
+@pytest.mark.parametrize("mode,kernel", [("fitnet", None), ("at", None), ("gpw", "rbf"), ("lpw", "cosine")])
+def test_ppi_gat_student_feature_distillation_step_with_frozen_teacher(mode, kernel):
+    """The ``fitnet`` / ``at`` / ``gpw`` / ``lpw`` rungs of ``ppi_train_epoch``: one step against the oracle's ``ppi_*_criterion``."""
+    train, _, _ = D.ppi_like(seed=6, n_train=1, total_train_nodes=1400)
+    hp = dict(alpha=0.5, kd_T=1.0, beta=0.5, nce_T=0.075, max_samples=8192, kernel=kernel)   # max_samples > n: no draw
+    om, pm = _student_pair(seed=1)
+    torch.manual_seed(2)
+    ot = OM.TeacherNet(50, 121)
+    pt = PM.TeacherNet(50, 121).to(DEV)
+    pt.load_state_dict(ot.state_dict())
+    torch.manual_seed(3)
+    osp, otp = OM.make_projection(136, 64), OM.make_projection(1024, 64)
+    psp, ptp = PM.make_projection(136, 64).to(DEV), PM.make_projection(1024, 64).to(DEV)
+    psp.load_state_dict(osp.state_dict()); ptp.load_state_dict(otp.state_dict())
+    assert train[0].x.shape[0] < hp["max_samples"]
+
+    def adam(m, a, b):
+        return torch.optim.Adam([{"params": m.parameters(), "lr": 0.005}, {"params": a.parameters(), "lr": 0.005},
+                                 {"params": b.parameters(), "lr": 0.005}])
+    ref = _oracle_aux_step(mode, om, ot, train[0], adam(om, osp, otp), osp, otp, hp)
+    got = PM.ppi_train_epoch(pm, pt, _gpu_graphs(train), adam(pm, psp, ptp), mode, hp, psp, ptp)
+    print(f"ppi {mode}: got {got} oracle {ref}")
+    assert ref[2] > 0
+    for a, b in zip(got, ref):
+        close(a, b, rtol=2e-4, atol_scale=0)
+
+
 # ------------------------------------------------------------------------------------------------
 # drop-in: a PyG-API training loop through the torch_geometric.nn shim, and the same loop on the oracle
 # ------------------------------------------------------------------------------------------------

@@ -413,3 +413,39 @@ def test_captured_epoch_graph_is_a_chain_of_kernel_nodes(small, gnn, mode):
     assert set(kinds) <= {"kernel", "edges", "chain"}, kinds
     losses, accs = ge.step()
     assert all(np.isfinite(v) for v in losses)
+
+
+@pytest.mark.parametrize("mode", ["supervised", "kd"])
+def test_compact_rows_route_equals_the_row_picks_inside_the_kernels(mode):
+    """``models._TRAIN_ROWS`` off: ``model(...)[train_idx]`` is gathered and the criteria run on the compact rows.  Same losses and
+    the same parameters after one step, bit for bit, as with the row picks inside the CE / KD kernels (the criteria's two forms are
+    bit-equal, test_criteria_rows_twins_equal_the_compact_call, and everything behind the logits gradient is the same code); a
+    caller's ``out=`` buffer receives the three losses on both routes."""
+    d = to_dev(D.arxiv_like(scale=0.004, seed=2))
+    tr = d.split_idx["train"]
+    hp = dict(alpha=0.9, kd_T=4.0)
+    torch.manual_seed(0)
+    init = PM.GCN(d.num_features, 64, d.num_classes, 3, 0.0).state_dict()
+    runs = {}
+    prev = PM._TRAIN_ROWS
+    try:
+        for flag in (True, False):
+            PM._TRAIN_ROWS = flag
+            model = PM.GCN(d.num_features, 64, d.num_classes, 3, 0.0).to(DEV)
+            model.load_state_dict(init)
+            opt = torch.optim.Adam(model.parameters(), lr=0.01)
+            out = torch.zeros(3, device=DEV)
+            ret = PM.train_step_tensors(model, d.x, d.adj_t, d.y, tr, opt, mode, hp, teacher_logits=d.teacher_logits, out=out)
+            assert ret.data_ptr() == out.data_ptr() and ret.shape == (3,)
+            loss, loss_cls, loss_aux = out.tolist()
+            assert math.isfinite(loss) and loss_cls > 0
+            if mode == "supervised":
+                assert loss == loss_cls and loss_aux == 0
+            else:
+                assert loss_aux > 0 and loss == pytest.approx(loss_aux * (0.9 * 4.0 * 4.0) + loss_cls * (1 - 0.9), rel=1e-6)
+            runs[flag] = (out.clone(), [p.detach().clone() for p in model.parameters()])
+    finally:
+        PM._TRAIN_ROWS = prev
+    assert torch.equal(runs[True][0], runs[False][0]), (runs[True][0].tolist(), runs[False][0].tolist())
+    for a, b in zip(runs[True][1], runs[False][1]):
+        assert torch.equal(a, b)

@@ -140,8 +140,7 @@ elif variant == "scalars":
     report = report_scalars
 else:
     report = lambda step, vals: print(f"step {step:2d} loss {vals[0]:.5f} cls {vals[1]:.5f} aux {vals[2]:.4e}", flush=True)
-print(f"# variant={variant} model={model_name} kernel={kernel} dropout={p_drop} graph={graph} N={d.num_nodes} E_tr={ei.shape[1]} "
-      f"EGNN_LSP_FULL_ROWS={os.environ.get('EGNN_LSP_FULL_ROWS', '1')}", flush=True)
+print(f"# variant={variant} model={model_name} kernel={kernel} dropout={p_drop} graph={graph} N={d.num_nodes} E_tr={ei.shape[1]}", flush=True)
 if graph:
     opt = torch.optim.Adam(m.parameters(), lr=0.01, fused=True, capturable=True)
     split = {k: v.to(dev) for k, v in d.split_idx.items()}
