@@ -11,5 +11,8 @@ from efficient_gnns_amd.utils import softmax, subgraph  # noqa: F401
 from efficient_gnns_amd.criterion import (  # noqa: F401
     kd_criterion, fitnet_criterion, at_criterion, gpw_criterion, lpw_criterion, nce_criterion, loss_kd_only,
     ppi_kd_criterion)
+from efficient_gnns_amd.similarity import (  # noqa: F401
+    structural_correlation, local_structural_correlation, linear_cka, representation_similarity, pair_moments,
+    pearson_from_moments)
 
 __version__ = "0.1.0"

@@ -161,6 +161,10 @@ SIGNATURES = {
     "egnn_prelu_drop_fwd_f32": (_i32, [_p, _p, _i64, _p, _i64, _p]),
     "egnn_prelu_drop_ws_floats": (_sz, [_i64, _i64, _i32]),
     "egnn_prelu_drop_bwd_f32": (_i32, [_p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _sz, _p]),
+    "egnn_pair_moments_ws_bytes": (_sz, [_i64]),
+    "egnn_pair_moments_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _sz, _p]),
+    "egnn_pearson_moments_ws_bytes": (_sz, [_i64]),
+    "egnn_pearson_moments_f32": (_i32, [_p, _p, _i64, _p, _p, _sz, _p]),
     "egnn_probe_gather_lines_f32":(_i32, [_p, _i64, _i64, _i64, _p, _i64, _i32, _i32, _p, _p]),
 }
 

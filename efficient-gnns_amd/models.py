@@ -297,6 +297,24 @@ def evaluate(model, x, adj_t, y, split_idx):
     return out, tuple(accs.tolist())
 
 
+@torch.no_grad()
+def student_similarity(model, x, adj_t, teacher_out_feat, idx, edge_index=None):
+    """How much of the teacher's structure the student's hidden space keeps over the rows ``idx`` (arxiv_pyg/correlation.py:200-214):
+    one eval-mode forward, then ``similarity.representation_similarity(model.out_feat, teacher_out_feat, idx, edge_index)`` --
+    ``dict(global_=..., local=..., cka=...)``.  The model comes back in the mode it was in; eval mode leaves the BatchNorm running
+    statistics as they are."""
+    from .similarity import representation_similarity
+    _lib.require_gpu(x, teacher_out_feat)
+    flags = [(m, m.training) for m in model.modules()]
+    model.eval()
+    try:
+        model(x, adj_t)
+        return representation_similarity(model.out_feat, teacher_out_feat, idx, edge_index)
+    finally:
+        for m, was_training in flags:
+            m.training = was_training
+
+
 class ReplayedEpoch:
     """An epoch captured ONCE as a hipGraph and replayed, with the per-step host randomness staged around the replays -- the part
     ``GraphedEpoch`` (one GPU) and ``dist.ShardedGraphedEpoch`` (a rank's shard) share.  The host draws of a step (the criterion's

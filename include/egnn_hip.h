@@ -698,6 +698,27 @@ size_t egnn_prelu_drop_ws_floats(int64_t B, int64_t Cs, int H);
 int egnn_prelu_drop_bwd_f32(const egnn_sign_seg_t* seg, const float* z, int64_t ld_z, const float* dy, int64_t ld_dy, float* dz,
                             int64_t ld_dz, float* da, float* dbias, float* ws, size_t ws_floats, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Structure-preservation metrics, arxiv_pyg/correlation.py (csrc/similarity.hip)
+ * ---------------------------------------------------------------------------------------------- */
+/* All-pairs Pearson moments behind the global structural correlation (Mantel), correlation.py:178-181, 205-208, 212: for the N unit
+ * rows of xs [N,Ps] and xt [N,Pt] (the caller normalises, as for GSP cosine) and every unordered pair i < j, with
+ * a = <xs_i, xs_j>, b = <xt_i, xt_j>:
+ *   out6 = (n, sum a, sum b, sum a^2, sum b^2, sum ab)   in float64, n = N (N-1) / 2.
+ * The reference correlates the cosine DISTANCES 1 - a, 1 - b; Pearson r is invariant under a -> 1 - a on both sides, so the
+ * similarities are accumulated.  Neither N x N matrix is formed: only the T (T+1) / 2 upper 128 x 128 tiles are computed, each lane
+ * sums its accumulator entries in fp32 ABOUT THE TILE'S MEAN (the tile's raw moments are restored in float64, so a narrow band of
+ * cosines far from 0 costs no digits), everything after that is float64 in a fixed order (per-tile partials in ws, one finalising
+ * launch, no atomics: two calls are bit-equal).  N < 2 or ld < P: EGNN_EINVAL; ws (8-byte aligned) shorter than
+ * egnn_pair_moments_ws_bytes(N): EGNN_EWORKSPACE. */
+size_t egnn_pair_moments_ws_bytes(int64_t N);
+int egnn_pair_moments_f32(const float* xs, int64_t ld_s, int64_t Ps, const float* xt, int64_t ld_t, int64_t Pt, int64_t N,
+                          double* out6, void* ws, size_t ws_bytes, void* stream);
+/* The same six float64 moments of two length-n vectors (the per-edge cosines of the local structural correlation,
+ * correlation.py:182, 209, 213); fixed order, two launches.  ws: egnn_pearson_moments_ws_bytes(n) bytes. */
+size_t egnn_pearson_moments_ws_bytes(int64_t n);
+int egnn_pearson_moments_f32(const float* a, const float* b, int64_t n, double* out6, void* ws, size_t ws_bytes, void* stream);
+
 /* DIAGNOSTIC (measurement only; bench.py's roofline.gather_ceiling_GBs): replays the gather stream of one aggregation call and
  * nothing else -- for every stored entry e, the 128-byte slice s of row col[e] of X [n_src, K] is read by an 8-lane sub-group,
  * slice s by the workgroups with blockIdx % (K / 32) == s (the aggregation kernel's slice <-> XCD binding,
