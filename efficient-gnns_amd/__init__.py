@@ -13,6 +13,6 @@ from efficient_gnns_amd.criterion import (  # noqa: F401
     ppi_kd_criterion)
 from efficient_gnns_amd.similarity import (  # noqa: F401
     structural_correlation, local_structural_correlation, linear_cka, representation_similarity, pair_moments,
-    pearson_from_moments)
+    pearson_from_moments, kernel_cka, rbf_bandwidth)
 
 __version__ = "0.1.0"

@@ -165,6 +165,10 @@ SIGNATURES = {
     "egnn_pair_moments_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _sz, _p]),
     "egnn_pearson_moments_ws_bytes": (_sz, [_i64]),
     "egnn_pearson_moments_f32": (_i32, [_p, _p, _i64, _p, _p, _sz, _p]),
+    "egnn_sqdist_median_ws_bytes": (_sz, [_i64]),
+    "egnn_sqdist_median_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _sz, _p]),
+    "egnn_rbf_cka_ws_bytes": (_sz, [_i64]),
+    "egnn_rbf_cka_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
     "egnn_probe_gather_lines_f32":(_i32, [_p, _i64, _i64, _i64, _p, _i64, _i32, _i32, _p, _p]),
 }
 

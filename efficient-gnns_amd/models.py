@@ -298,18 +298,18 @@ def evaluate(model, x, adj_t, y, split_idx):
 
 
 @torch.no_grad()
-def student_similarity(model, x, adj_t, teacher_out_feat, idx, edge_index=None):
+def student_similarity(model, x, adj_t, teacher_out_feat, idx, edge_index=None, kernel_cka=False):
     """How much of the teacher's structure the student's hidden space keeps over the rows ``idx`` (arxiv_pyg/correlation.py:200-214):
     one eval-mode forward, then ``similarity.representation_similarity(model.out_feat, teacher_out_feat, idx, edge_index)`` --
-    ``dict(global_=..., local=..., cka=...)``.  The model comes back in the mode it was in; eval mode leaves the BatchNorm running
-    statistics as they are."""
+    ``dict(global_=..., local=..., cka=...)``, plus ``kcka`` (RBF CKA, :70-75) with ``kernel_cka=True``.  The model comes back in the
+    mode it was in; eval mode leaves the BatchNorm running statistics as they are."""
     from .similarity import representation_similarity
     _lib.require_gpu(x, teacher_out_feat)
     flags = [(m, m.training) for m in model.modules()]
     model.eval()
     try:
         model(x, adj_t)
-        return representation_similarity(model.out_feat, teacher_out_feat, idx, edge_index)
+        return representation_similarity(model.out_feat, teacher_out_feat, idx, edge_index, kernel_cka=kernel_cka)
     finally:
         for m, was_training in flags:
             m.training = was_training

@@ -5,10 +5,13 @@ embedding space keep the teacher's structure?  Three numbers per (student, teach
 * local structural correlation: Pearson r between the per-edge cosine distances of the induced sub-graph (:104-106, 182, 209, 213),
 * linear CKA of the row-normalised features (:78-85, 214).
 
-Kernels in csrc/similarity.hip.  No N x N object is formed on any of the three paths.  The functions return Python floats: each metric
+* kernel (RBF) CKA with a median-heuristic bandwidth (:41-53, 70-75): ``kernel_cka``, ``rbf_bandwidth``.
+
+Kernels in csrc/similarity.hip.  No N x N object is formed on any of the paths.  The functions return Python floats: each metric
 costs one host read of its result (the six moments, or CKA's three Frobenius sums); the local metric reads the range of ``edge_index``
 first, because the edge kernel addresses rows by those ids, and ``representation_similarity`` is the three metrics one after the other
-plus the reads inside ``utils.subgraph``.  Nothing here is differentiable or captured.  CPU tensors raise ``_lib.HipExtensionError``.
+plus the reads inside ``utils.subgraph``.  Kernel CKA with its own bandwidths reads its three float64 sums and nothing before them: the
+medians stay on the device.  Nothing here is differentiable or captured.  CPU tensors raise ``_lib.HipExtensionError``.
 """
 from __future__ import annotations
 
@@ -175,10 +178,80 @@ def linear_cka(feat: Tensor, teacher_feat: Tensor, idx: Tensor | None = None, no
     return _cka(_rows(feat, idx), _rows(teacher_feat, idx))
 
 
-def representation_similarity(feat: Tensor, teacher_feat: Tensor, idx: Tensor | None, edge_index: Tensor | None = None) -> dict:
+def _sqdist_median(x: Tensor, out2: Tensor) -> None:
+    """out2 (two float64 on the device) = (median of |x_i - x_j|^2 over the pairs i < j, the pair count) (egnn_sqdist_median_f32)."""
+    lib, N = _lib.load(), x.shape[0]
+    nws = lib.egnn_sqdist_median_ws_bytes(N)
+    ws = torch.empty(nws // 8, dtype=torch.float64, device=x.device)
+    rc = lib.egnn_sqdist_median_f32(_lib.ptr(x), x.stride(0), x.shape[1], N, _lib.ptr(out2), _lib.ptr(ws), nws, _lib.stream())
+    _lib.check(rc, "egnn_sqdist_median_f32")
+
+
+def _kernel_rows(x: Tensor, idx: Tensor | None, normalize: bool) -> Tensor:
+    """The rows the RBF kernels read: unit rows behind a padded pitch, or the rows as they are (a strided row-major view is kept)."""
+    if x.dtype != torch.float32:
+        raise TypeError("expected float32 features")
+    x = _unit_rows(x, idx) if normalize else ops._gemm_operand(_rows(x, idx))
+    if x.shape[0] < 2:
+        raise ValueError("at least 2 rows are needed")
+    return x
+
+
+def rbf_bandwidth(x: Tensor, idx: Tensor | None = None, normalize: bool = True) -> float:
+    """The median-heuristic bandwidth sigma of the reference's ``rbf(X, None)``: the square root of the median of |x_i - x_j|^2 over
+    the N (N-1) / 2 pairs i < j of the rows ``idx`` (row-normalised first with ``normalize``), the mean of the two middle values when
+    that count is even.  The selection is exact over the fp32 distances the kernels form.  The reference takes
+    ``np.median(KX[KX != 0])`` over the full symmetric matrix: the same number whenever no two rows coincide.  Where rows do coincide
+    its filter depends on whether float64 rounding left an exact zero; here every pair is kept, zeros included.  One host read."""
+    _lib.require_gpu(x, idx)
+    if x.dim() != 2:
+        raise ValueError("rbf_bandwidth: features are [N, D]")
+    x = _kernel_rows(x, _index(idx), normalize)
+    out2 = torch.empty(2, dtype=torch.float64, device=x.device)
+    _sqdist_median(x, out2)
+    return math.sqrt(out2.tolist()[0])
+
+
+def _kcka(xs: Tensor, xt: Tensor, sigma) -> float:
+    dev, N = xs.device, xs.shape[0]
+    if sigma is None:
+        med = torch.empty(2, 2, dtype=torch.float64, device=dev)
+        _sqdist_median(xs, med[0])
+        _sqdist_median(xt, med[1])
+        sigma2 = med[:, 0].contiguous()          # stays on the device: the kernels read it through a pointer
+    else:
+        ss, st = (float(v) for v in (sigma if isinstance(sigma, (tuple, list)) else (sigma, sigma)))
+        if not (ss > 0.0 and st > 0.0):
+            return math.nan
+        sigma2 = torch.tensor([ss * ss, st * st], dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    out3 = torch.empty(3, dtype=torch.float64, device=dev)
+    nws = lib.egnn_rbf_cka_ws_bytes(N)
+    ws = torch.empty(nws // 8, dtype=torch.float64, device=dev)
+    rc = lib.egnn_rbf_cka_f32(_lib.ptr(xs), xs.stride(0), xs.shape[1], _lib.ptr(xt), xt.stride(0), xt.shape[1], N, _lib.ptr(sigma2),
+                              _lib.ptr(out3), _lib.ptr(ws), nws, _lib.stream())
+    _lib.check(rc, "egnn_rbf_cka_f32")
+    xy, xx, yy = out3.tolist()
+    den = math.sqrt(xx * yy) if xx > 0.0 and yy > 0.0 else 0.0     # a zero bandwidth arrives as nan sums
+    return xy / den if den > 0.0 else math.nan
+
+
+def kernel_cka(feat: Tensor, teacher_feat: Tensor, idx: Tensor | None = None, sigma=None, normalize: bool = True) -> float:
+    """CKA under the Gaussian kernel K_ij = exp(-|x_i - x_j|^2 / (2 sigma^2)), the reference's ``kernel_CKA``, over the rows ``idx``
+    (row-normalised first with ``normalize``, as ``linear_cka``).  ``sigma`` None: each side takes its own median bandwidth
+    (``rbf_bandwidth``), as two ``rbf(., None)`` calls do, and nothing is read back before the final three sums; a float: both sides
+    use it; a pair: (student, teacher).  nan when a bandwidth is 0 or a side's centred kernel matrix vanishes."""
+    _check_pair(feat, teacher_feat, idx)
+    idx = _index(idx)
+    return _kcka(_kernel_rows(feat, idx, normalize), _kernel_rows(teacher_feat, idx, normalize), sigma)
+
+
+def representation_similarity(feat: Tensor, teacher_feat: Tensor, idx: Tensor | None, edge_index: Tensor | None = None,
+                              kernel_cka: bool = False) -> dict:
     """The three metrics of one (student, teacher) pair over the rows ``idx``: ``dict(global_=..., local=..., cka=...)``.
     ``edge_index`` is in the index space of ALL rows; the sub-graph induced by ``idx`` is taken and relabelled here
-    (``utils.subgraph(idx, edge_index, relabel_nodes=True)``).  ``local`` is None without edges."""
+    (``utils.subgraph(idx, edge_index, relabel_nodes=True)``).  ``local`` is None without edges.  ``kernel_cka=True`` adds ``kcka``,
+    the RBF CKA of the same unit rows with each side's median bandwidth."""
     from .utils import subgraph
     _check_pair(feat, teacher_feat, idx)
     idx = _index(idx)
@@ -189,4 +262,9 @@ def representation_similarity(feat: Tensor, teacher_feat: Tensor, idx: Tensor | 
         if idx is not None:
             edge_index = subgraph(idx, edge_index, relabel_nodes=True, num_nodes=feat.shape[0])[0]
         local = _local_r(xs, xt, edge_index)
-    return dict(global_=_global_r(xs, xt), local=local, cka=_cka(xs, xt))
+    out = dict(global_=_global_r(xs, xt), local=local, cka=_cka(xs, xt))
+    if kernel_cka:
+        if xs.dtype != torch.float32 or xt.dtype != torch.float32:
+            raise TypeError("kernel CKA: expected float32 features")
+        out["kcka"] = _kcka(xs, xt, None)
+    return out

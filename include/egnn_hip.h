@@ -719,6 +719,28 @@ int egnn_pair_moments_f32(const float* xs, int64_t ld_s, int64_t Ps, const float
 size_t egnn_pearson_moments_ws_bytes(int64_t n);
 int egnn_pearson_moments_f32(const float* a, const float* b, int64_t n, double* out6, void* ws, size_t ws_bytes, void* stream);
 
+/* Kernel (RBF) CKA, correlation.py:41-53 (rbf, kernel_HSIC) and :70-75 (kernel_CKA), without an N x N object.
+ * Device distance, one definition for every pass: d_ij = max(n_i + n_j - 2 g_ij, +0) in fp32, g_ij from the fp32 MFMA, n_i = |x_i|^2.
+ *
+ * Median bandwidth (correlation.py:45-46): out2 = (median of d_ij over the N (N-1) / 2 pairs i < j, that pair count), float64; the
+ * mean of the two middle order statistics when the count is even.  Every pair is kept, coincident rows (d = 0) included; the
+ * reference's KX[KX != 0] over the symmetric matrix is the same number whenever no two rows coincide.  Exact: a radix select over the
+ * 31 value bits in three histogram passes that recompute the Gram tiles; 64-bit integer counts (order-independent), the bin and the
+ * residual rank are chosen on the device between the passes.  N < 2 or ld < P: EGNN_EINVAL; ws (8-byte aligned) shorter than
+ * egnn_sqdist_median_ws_bytes(N): EGNN_EWORKSPACE; out2 8-byte aligned. */
+size_t egnn_sqdist_median_ws_bytes(int64_t N);
+int egnn_sqdist_median_f32(const float* x, int64_t ld, int64_t P, int64_t N, double* out2, void* ws, size_t ws_bytes, void* stream);
+/* The three sums of kernel_CKA (correlation.py:52-53, 70-75) for K_ij = exp(-d_ij / (2 sigma2_dev[0])) over xs [N,Ps] and
+ * L_ij = exp(-d_ij / (2 sigma2_dev[1])) over xt [N,Pt], K_ii = L_ii = 1 exactly:
+ *   out3 = (sum Kc Lc, sum Kc^2, sum Lc^2) over all N^2 entries, Kc_ij = K_ij - rowmean_i - rowmean_j + mean   (= centering(K), :30-37),
+ * CKA = out3[0] / sqrt(out3[1] out3[2]).  sigma2_dev: two float64 SQUARED bandwidths in device memory (the medians above can feed it
+ * without a host read); one that is not > 0 makes out3 NaN.  Row sums over the full matrix in float64 (workspace O(N), fixed order),
+ * entries centred before the products, per-tile partials and one finalising launch: no atomics, two calls are bit-equal.
+ * Errors as for egnn_pair_moments_f32; ws: egnn_rbf_cka_ws_bytes(N) bytes; sigma2_dev and out3 8-byte aligned. */
+size_t egnn_rbf_cka_ws_bytes(int64_t N);
+int egnn_rbf_cka_f32(const float* xs, int64_t ld_s, int64_t Ps, const float* xt, int64_t ld_t, int64_t Pt, int64_t N,
+                     const double* sigma2_dev, double* out3, void* ws, size_t ws_bytes, void* stream);
+
 /* DIAGNOSTIC (measurement only; bench.py's roofline.gather_ceiling_GBs): replays the gather stream of one aggregation call and
  * nothing else -- for every stored entry e, the 128-byte slice s of row col[e] of X [n_src, K] is read by an 8-lane sub-group,
  * slice s by the workgroups with blockIdx % (K / 32) == s (the aggregation kernel's slice <-> XCD binding,
