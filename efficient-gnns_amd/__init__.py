@@ -14,5 +14,6 @@ from efficient_gnns_amd.criterion import (  # noqa: F401
 from efficient_gnns_amd.similarity import (  # noqa: F401
     structural_correlation, local_structural_correlation, linear_cka, representation_similarity, pair_moments,
     pearson_from_moments, kernel_cka, rbf_bandwidth)
+from efficient_gnns_amd.optim import LazyRowAdam  # noqa: F401
 
 __version__ = "0.1.0"

@@ -57,6 +57,21 @@ class SignSeg(C.Structure):
                 ("batch", _p)]
 
 
+ADAM_MAX_LAG = 64   # EGNN_ADAM_MAX_LAG of include/egnn_hip.h
+
+
+class AdamRows(C.Structure):
+    """egnn_adam_rows_t of include/egnn_hip.h, field for field: one embedding table under the row-lazy Adam (csrc/adam_rows.hip) with its
+    per-row step stamps and the two rings of per-step scalars (index tau % ADAM_MAX_LAG), formed on the host in double."""
+    _fields_ = [("p", _p), ("m", _p), ("v", _p), ("last", _p),
+                ("n_rows", _i64), ("D", _i64), ("ld", _i64),
+                ("beta1", _f32), ("beta2", _f32), ("eps", _f32),
+                ("one_minus_beta1", _f32), ("one_minus_beta2", _f32),
+                ("step", _i32), ("flushed", _i32),
+                ("step_size", _f32 * ADAM_MAX_LAG), ("bc2_sqrt", _f32 * ADAM_MAX_LAG),
+                ("dup_count", _p)]
+
+
 # name -> (restype, argtypes); must list every symbol include/egnn_hip.h declares
 SIGNATURES = {
     "egnn_abi_version": (_i32, []),
@@ -169,6 +184,10 @@ SIGNATURES = {
     "egnn_sqdist_median_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _sz, _p]),
     "egnn_rbf_cka_ws_bytes": (_sz, [_i64]),
     "egnn_rbf_cka_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "egnn_group_input_f32": (_i32, [_p, _p, _i32, _p, _p, _i64, _i64, _p, _i64, _p, _p]),
+    "egnn_adam_rows_catchup_f32": (_i32, [_p, _i32, _p, _p, _i64, _p]),
+    "egnn_adam_rows_flush_f32": (_i32, [_p, _p]),
+    "egnn_adam_rows_step_f32": (_i32, [_p, _i32, _p, _p, _i64, _p, _i64, _p]),
     "egnn_probe_gather_lines_f32":(_i32, [_p, _i64, _i64, _i64, _p, _i64, _i32, _i32, _p, _p]),
 }
 

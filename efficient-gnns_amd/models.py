@@ -777,6 +777,12 @@ class RGCN(nn.Module):
             conv.reset_parameters()
 
     def group_input(self, x_dict, node_type, local_node_idx):
+        from .optim import row_state
+        if any([row_state(emb) is not None for emb in self.emb_dict.values()]):
+            # tables under optim.LazyRowAdam: one gather launch that first catches the rows it reads up (their data is otherwise behind)
+            sources = {int(k): x for k, x in x_dict.items()}
+            sources.update((int(k), emb) for k, emb in self.emb_dict.items())
+            return ops.group_input(sources, node_type, local_node_idx, self.in_channels)
         h = torch.zeros((node_type.size(0), self.in_channels), device=node_type.device)
         for key, x in x_dict.items():
             mask = node_type == key
@@ -799,6 +805,10 @@ class RGCN(nn.Module):
     def inference(self, x_dict, edge_index_dict, key2int):
         x_dict = dict(x_dict)
         for key, emb in self.emb_dict.items():
+            from .optim import row_state
+            rows = row_state(emb)
+            if rows is not None:
+                rows.flush()            # a table under optim.LazyRowAdam is read whole here: bring every row up to the current step
             x_dict[int(key)] = emb
         adj_t_dict = {}
         for key, (row, col) in edge_index_dict.items():
@@ -923,7 +933,19 @@ def mag_train_epoch(model, loader, x_dict, optimizer, mode, hp, teacher_model=No
         for i in range(3):
             tot[i] += vals[i] * n
         examples += n
+    flush = getattr(optimizer, "flush", None)
+    if flush is not None:
+        flush()                         # optim.LazyRowAdam: after the epoch the tables are what dense Adam would hold
     return tuple(v / max(1, examples) for v in tot)
+
+
+def mag_optimizer(model, lr):
+    """The reference's ``torch.optim.Adam(model.parameters(), lr=lr)`` (mag_pyg/gnn.py:424) with the embedding tables stepped row-lazily
+    (``optim.LazyRowAdam``): same parameters, but a step moves the ~55 k rows of the batch instead of all 1.2 M, and no dense table
+    gradient is formed.  Between flushes ``emb.data`` holds rows that are behind; ``RGCN.forward`` / ``inference`` / ``mag_train_epoch``
+    catch up or flush what they read."""
+    from .optim import LazyRowAdam
+    return LazyRowAdam(model.parameters(), lr=lr, lazy=list(model.emb_dict.values()))
 
 
 @torch.no_grad()

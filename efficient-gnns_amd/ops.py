@@ -1669,3 +1669,98 @@ def linear_blocks(x, weights, biases, rows=None) -> Tensor:
     if torch.is_tensor(rows):
         _lib.require_gpu(rows)
     return _LinearBlocks.apply(None, rows, H, *feats, *weights, *biases)
+
+
+# ------------------------------------------------------------------------------------------------
+# MAG group_input (mag_pyg/gnn.py:117-127) in one launch; the read side of the row-lazy Adam (optim.py)
+# ------------------------------------------------------------------------------------------------
+_GROUP_INPUT_MAX_TYPES = 8
+_GROUP_OOB: dict = {}     # device -> int32 [1]: rows group_input wrote as zeros because their type / index was out of range
+
+
+def group_input_oob(device, reset: bool = True) -> int:
+    """How many rows ``group_input`` zero-filled on ``device`` because their node type or index was out of range, since the last reset.
+    A host read: ``LazyRowAdam.flush`` asks (and raises), next to its own counter reads."""
+    c = _GROUP_OOB.get(torch.device(device))
+    if c is None:
+        return 0
+    n = int(c.item())
+    if reset and n:
+        c.zero_()
+    return n
+
+
+def _group_input_fwd(tables, node_type: Tensor, local_idx: Tensor, D: int, oob: Tensor | None = None) -> Tensor:
+    """``tables``: list indexed by node type (None: no table, zeros).  One egnn_group_input_f32 launch, no host read."""
+    n, T = node_type.numel(), len(tables)
+    dev = node_type.device
+    if oob is None:
+        oob = _GROUP_OOB.get(dev)
+        if oob is None:
+            oob = _GROUP_OOB[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+    h = torch.empty((n, D), dtype=torch.float32, device=dev)
+    ptrs = (ctypes.c_void_p * T)(*[None if t is None else t.data_ptr() for t in tables])
+    rows = (ctypes.c_int64 * T)(*[0 if t is None else t.shape[0] for t in tables])
+    _lib.check(_lib.load().egnn_group_input_f32(ctypes.addressof(ptrs), ctypes.addressof(rows), T, _lib.ptr(node_type), _lib.ptr(local_idx),
+                                                n, D, _lib.ptr(h), h.stride(0), _lib.ptr(oob), _lib.stream()), "egnn_group_input_f32")
+    return h
+
+
+class _GroupInput(torch.autograd.Function):
+    """h[i] = tables[node_type[i]][local_idx[i]].  A table under the row-lazy Adam (``t._egnn_rows``) is caught up on the rows about to
+    be read before the gather, and its backward leaves the gradient rows with that state instead of forming a dense gradient."""
+
+    @staticmethod
+    def forward(ctx, node_type, local_idx, D, oob, keys, states, *tensors):
+        tables = [None] * (max(keys) + 1)
+        for k, t, st in zip(keys, tensors, states):
+            if st is not None:
+                st.catch_up(k, node_type, local_idx)
+            tables[k] = t.detach()
+        ctx.keys, ctx.states, ctx.shapes = keys, states, [t.shape for t in tensors]
+        ctx.save_for_backward(node_type, local_idx)
+        return _group_input_fwd(tables, node_type, local_idx, D, oob)
+
+    @staticmethod
+    def backward(ctx, g):
+        node_type, local_idx = ctx.saved_tensors
+        g = g.contiguous()
+        grads = []
+        for j, (k, st, shape) in enumerate(zip(ctx.keys, ctx.states, ctx.shapes)):
+            if st is not None:
+                st.deposit(g, node_type, local_idx, k)
+                grads.append(None)
+            elif ctx.needs_input_grad[6 + j]:
+                # the forward's own range test: rows it zero-filled (and counted) carry no gradient; no nonzero, no host wait
+                ok = (node_type == k) & (local_idx >= 0) & (local_idx < shape[0])
+                gt = torch.zeros(shape, dtype=g.dtype, device=g.device)
+                if shape[0] > 0:
+                    gt.index_add_(0, local_idx.clamp(0, shape[0] - 1), g * ok.unsqueeze(1).to(g.dtype))
+                grads.append(gt)
+            else:
+                grads.append(None)
+        return (None, None, None, None, None, None, *grads)
+
+
+def group_input(sources: dict, node_type: Tensor, local_idx: Tensor, D: int, oob: Tensor | None = None) -> Tensor:
+    """``h[i] = sources[node_type[i]][local_idx[i]]`` -> [n, D] in ONE launch: ``RGCN.group_input`` (mag_pyg/gnn.py:117-127) without a
+    mask, a ``nonzero`` or a host wait per node type.  ``sources``: {node type id (0..7): contiguous fp32 [rows, D] tensor}; a type
+    without a source gives zero rows, like the mask form.  A type or an index out of range gives a zero row and is counted in ``oob``
+    (int32 [1] on the device; default: a per-device counter that ``group_input_oob`` reads and ``LazyRowAdam.flush`` raises on).  Sources stepped by ``optim.LazyRowAdam``
+    are first caught up on the rows read (also under ``no_grad``) and get their gradient rows deposited for the optimiser's step;
+    ``param.grad`` stays None.  Other sources that require grad get a dense gradient."""
+    keys = tuple(int(k) for k in sources)
+    tensors = [_lib.real(sources[k]) for k in sources]
+    _lib.require_gpu(node_type, local_idx, *tensors)
+    if not keys or min(keys) < 0 or max(keys) >= _GROUP_INPUT_MAX_TYPES or len(set(keys)) != len(keys):
+        raise ValueError(f"group_input: node type ids must be distinct and in [0, {_GROUP_INPUT_MAX_TYPES})")
+    if D % 4 != 0:
+        raise _lib.HipExtensionError("group_input: D must be a multiple of 4")
+    for t in tensors:
+        if t.dim() != 2 or t.shape[1] != D or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"group_input: every source must be a contiguous fp32 [rows, {D}] tensor")
+    if node_type.dtype != torch.int64 or local_idx.dtype != torch.int64 or node_type.shape != local_idx.shape or node_type.dim() != 1:
+        raise TypeError("group_input: node_type and local_idx must be int64 vectors of one length")
+    from .optim import row_state
+    states = tuple(row_state(t) for t in tensors)
+    return _GroupInput.apply(node_type.contiguous(), local_idx.contiguous(), int(D), oob, keys, states, *tensors)

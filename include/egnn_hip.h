@@ -741,6 +741,58 @@ size_t egnn_rbf_cka_ws_bytes(int64_t N);
 int egnn_rbf_cka_f32(const float* xs, int64_t ld_s, int64_t Ps, const float* xt, int64_t ld_t, int64_t Pt, int64_t N,
                      const double* sigma2_dev, double* out3, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * MAG embedding tables (the reference's mag_pyg/gnn.py:100-108,117-127,424): the one-launch group_input gather and a row-lazy Adam
+ * that gives dense torch.optim.Adam's parameters while touching only the rows of the batch; csrc/adam_rows.hip.
+ *
+ * egnn_group_input_f32   h[i, :] = tables[node_type[i]][local_idx[i], :], i < n, in ONE launch (no mask, no nonzero, no host read).
+ *     tables / table_rows are HOST arrays of n_types <= 8 entries (device pointers of contiguous [table_rows[k], D] fp32 matrices and
+ *     their row counts), copied into the kernel arguments.  A NULL table writes zeros for its type (the mask form of :117-127 leaves
+ *     such rows zero too); a type outside [0, n_types) or an index outside its table writes zeros and adds 1 to *oob (device int32
+ *     the caller zeroes and reads when it reads anything else).  D % 4 == 0; h and every table 16-byte aligned, ldh % 4 == 0
+ *     (else EGNN_EALIGN).
+ *
+ * Row-lazy Adam.  Per table: p, m, v [n_rows, ld] and last [n_rows] int32, the step each row is current for; -1 = the row never had
+ * a gradient (m = v = 0: dense Adam does not move it).  One step of one element, in torch.optim.Adam's single-tensor order:
+ *     m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;  p -= step_size[tau] (m / (sqrtf(v) / bc2_sqrt[tau] + eps))
+ * A row outside the batch of step tau takes that step with g = 0 -- later, in registers, when it is next read or stepped (the same
+ * device function: deferring a zero-gradient step changes no bit).  step_size[tau % MAX_LAG] = lr_tau / (1 - beta1^tau) and
+ * bc2_sqrt[tau % MAX_LAG] = sqrt(1 - beta2^tau) are formed by the host in double, as are 1 - beta1 and 1 - beta2: the rings hold the
+ * last EGNN_ADAM_MAX_LAG steps, so no row may lag further behind than that: the caller flushes in time and states in `flushed` the
+ * last step every touched row was brought up to; step - flushed > EGNN_ADAM_MAX_LAG is EGNN_EINVAL (nothing enqueued).
+ * The descriptor is read only while a call runs (it is copied into the kernel arguments).
+ *   egnn_adam_rows_catchup_f32  for every batch row i < n with node_type[i] == type_id (all i when node_type == NULL), table row
+ *       r = local_idx[i]: replay tau = last[r] + 1 .. step with g = 0, then last[r] = step.  Rows with last[r] == -1 or == step cost
+ *       one 4-byte read.  A table row named more than once is served once (claimed by compare-and-swap on last[r]); ids outside
+ *       [0, n_rows) are skipped.
+ *   egnn_adam_rows_flush_f32    the same over all n_rows.
+ *   egnn_adam_rows_step_f32     step >= 1; claims r with a compare-and-swap step - 1 -> step on last[r] (-1 -> step for a row's first
+ *       gradient) and applies the step above with g = g[i, :] ([n, ldg], 16-byte aligned, ldg % 4 == 0).  The row must be current for
+ *       step - 1 (catch-up first).  A batch row that loses the claim -- a table row named twice in one batch, a row that is not
+ *       current, an id outside the table -- adds 1 to *dup_count and writes nothing; the other rows are unaffected.
+ * D % 4 == 0, ld % 4 == 0 and p, m, v 16-byte aligned (else EGNN_EALIGN).  No float atomics: results are bit-stable.
+ * ---------------------------------------------------------------------------------------------- */
+#define EGNN_ADAM_MAX_LAG 64
+typedef struct egnn_adam_rows {
+  float* p; float* m; float* v;                          /* [n_rows, ld] fp32, one ld */
+  int32_t* last;                                         /* [n_rows] step the row is current for; -1 = never had a gradient */
+  int64_t n_rows; int64_t D; int64_t ld;
+  float beta1; float beta2; float eps;
+  float one_minus_beta1; float one_minus_beta2;          /* formed on the host in double, like the rings */
+  int32_t step;                                          /* t of the step being applied (step) / the step to reach (catch-up, flush) */
+  int32_t flushed;                                       /* the last step every touched row is known to have reached (0: none yet) */
+  float step_size[EGNN_ADAM_MAX_LAG];                    /* ring, index tau % MAX_LAG: lr_tau / (1 - beta1^tau) */
+  float bc2_sqrt[EGNN_ADAM_MAX_LAG];                     /* ring: sqrt(1 - beta2^tau) */
+  int32_t* dup_count;                                    /* device counter of batch rows whose step was not applied */
+} egnn_adam_rows_t;
+int egnn_group_input_f32(const float* const* tables, const int64_t* table_rows, int n_types, const int64_t* node_type,
+                         const int64_t* local_idx, int64_t n, int64_t D, float* h, int64_t ldh, int32_t* oob, void* stream);
+int egnn_adam_rows_catchup_f32(const egnn_adam_rows_t* a, int type_id, const int64_t* node_type, const int64_t* local_idx, int64_t n,
+                               void* stream);
+int egnn_adam_rows_flush_f32(const egnn_adam_rows_t* a, void* stream);
+int egnn_adam_rows_step_f32(const egnn_adam_rows_t* a, int type_id, const int64_t* node_type, const int64_t* local_idx, int64_t n,
+                            const float* g, int64_t ldg, void* stream);
+
 /* DIAGNOSTIC (measurement only; bench.py's roofline.gather_ceiling_GBs): replays the gather stream of one aggregation call and
  * nothing else -- for every stored entry e, the 128-byte slice s of row col[e] of X [n_src, K] is read by an 8-lane sub-group,
  * slice s by the workgroups with blockIdx % (K / 32) == s (the aggregation kernel's slice <-> XCD binding,
