@@ -12,25 +12,13 @@
 //      dXs = g * (Ws Xs - rowsum(Ws) o Xs) ,  dXt = g * (Wt Xt - rowsum(Wt) o Xt)
 // (the rowsum term only for the distance kernels): one MFMA GEMM each (egnn_gemm_f32) plus the
 // row kernels below.  All reductions have a fixed order.
-#include "gemm_core.h"
+#include "pair_tile.h"
 
-using namespace egnn_gemm;
+using namespace egnn_pair;
 
 namespace {
 
-constexpr int GB = 128;
 enum { K_COSINE = 0, K_POLY = 1, K_L2 = 2, K_RBF = 3 };
-
-__global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* __restrict__ x, int64_t ld, int64_t n, int64_t D,
-                                                         float* __restrict__ out) {
-  const int lane = egnn_lane();
-  const int64_t row = blockIdx.x * 4LL + egnn_wave_id();
-  if (row >= n) return;
-  float s = 0.f;
-  for (int64_t d = lane; d < D; d += 64) { const float v = x[row * ld + d]; s = fmaf(v, v, s); }
-  s = egnn_wave_sum(s);
-  if (lane == 0) out[row] = s;
-}
 
 // similarity value and d(sim)/d(gram-like argument) pieces for one pair
 struct PairK {
@@ -56,17 +44,12 @@ __global__ __launch_bounds__(256) void gsp_fwd_kernel(const float* __restrict__ 
                                                       int kernel, const float* __restrict__ ns, const float* __restrict__ nt,
                                                       float coef, float* __restrict__ Ws, float* __restrict__ Wt,
                                                       float* __restrict__ partials) {
-  using TS = TileShape<GB, GB>;
   __shared__ __attribute__((aligned(16))) float smem[TS::SMEM_FLOATS];
   const int64_t tiles = (S + GB - 1) / GB;
   const int64_t i0 = (blockIdx.x / tiles) * GB;
   const int64_t j0 = (blockIdx.x % tiles) * GB;
-  IdentityXf id;
   f32x16 as[TS::TM][TS::TN], at[TS::TM][TS::TN];
-  zero_acc(as);
-  zero_acc(at);
-  mainloop<GB, GB, KMAJOR, KMAJOR, VEC4>(as, xs, lds_, i0, S, xs, lds_, j0, S, 0, Ps, id, id, smem);
-  mainloop<GB, GB, KMAJOR, KMAJOR, VEC4>(at, xt, ldt, i0, S, xt, ldt, j0, S, 0, Pt, id, id, smem);
+  gram_pair<VEC4>(as, at, xs, lds_, Ps, xt, ldt, Pt, i0, j0, S, smem);
   const int lane = egnn_lane();
   const int wave = egnn_wave_id();
   const int wm = wave >> 1, wn = wave & 1;
@@ -202,8 +185,8 @@ extern "C" int egnn_gsp_fwd_f32(const float* xs, int64_t ld_s, int64_t Ps, const
   float* nt = ws + S;
   float* partials = ws + 2 * S;
   if (kernel >= K_L2) {
-    hipLaunchKernelGGL(row_sqnorm_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, xs, ld_s, S, Ps, ns);
-    hipLaunchKernelGGL(row_sqnorm_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, xt, ld_t, S, Pt, nt);
+    row_sqnorm(xs, ld_s, Ps, S, ns, st);
+    row_sqnorm(xt, ld_t, Pt, S, nt, st);
   }
   const int64_t tiles = (S + GB - 1) / GB;
   const int64_t nblocks = tiles * tiles;
@@ -211,8 +194,9 @@ extern "C" int egnn_gsp_fwd_f32(const float* xs, int64_t ld_s, int64_t Ps, const
   // dL/dk = 2 D / S^2; each unordered pair enters twice (k_ij and k_ji) => 4 / S^2
   const float coef = 4.f / ((float)S * (float)S);
   const bool vec4 = (ld_s % 4 == 0) && (ld_t % 4 == 0) && egnn_aligned16(xs) && egnn_aligned16(xt);
-  if (vec4) hipLaunchKernelGGL(gsp_fwd_kernel<true>, dim3((unsigned)nblocks), dim3(256), 0, st, xs, ld_s, Ps, xt, ld_t, Pt, S, kernel, ns, nt, coef, Ws, Wt, partials);
-  else hipLaunchKernelGGL(gsp_fwd_kernel<false>, dim3((unsigned)nblocks), dim3(256), 0, st, xs, ld_s, Ps, xt, ld_t, Pt, S, kernel, ns, nt, coef, Ws, Wt, partials);
+  dispatch_vec4(vec4, [&](auto v4) {
+    hipLaunchKernelGGL(gsp_fwd_kernel<v4.value>, dim3((unsigned)nblocks), dim3(256), 0, st, xs, ld_s, Ps, xt, ld_t, Pt, S, kernel, ns, nt, coef, Ws, Wt, partials);
+  });
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(1024), 0, st, partials, nblocks, 1.f / ((float)S * (float)S), loss);
   return egnn_launch_status();
 }

@@ -8,8 +8,8 @@
 // twice), so the SIMILARITIES a = <xs_i, xs_j>, b = <xt_i, xt_j> are accumulated instead of the distances, and r needs only
 //      out6 = (n, sum a, sum b, sum a^2, sum b^2, sum ab)      over the pairs i < j.
 // No N x N object exists: one workgroup per 128 x 128 tile of the upper triangle (tj >= ti; T(T+1)/2 of the T^2 tiles) runs the
-// fp32-MFMA mainloop twice (student Gram tile, teacher Gram tile -- as gsp_fwd_kernel of pairwise.hip does) and reduces both
-// accumulator sets in registers.
+// fp32-MFMA mainloop twice (student Gram tile, teacher Gram tile -- gram_pair of pair_tile.h, which also holds the pair predicate
+// and the walk over the accumulators) and reduces both accumulator sets in registers.
 // Precision split: a lane sums its <= 64 accumulator entries in fp32; from the wave reduction onwards everything is float64 and in
 // a fixed order (wave butterfly, 4 waves in order, per-tile partials in the workspace, one finalising launch).  No atomics: two calls
 // give bit-equal results.
@@ -19,98 +19,39 @@
 // cancellation left for fp32 to lose), and the tile's raw moments are restored in float64,
 //      sum a = S_a + n c_a,   sum a^2 = S_aa + 2 c_a S_a + n c_a^2,   sum ab = S_ab + c_a S_b + c_b S_a + n c_a c_b,
 // so that the float64 cancellation downstream sees inputs good to fp32 RELATIVE TO THE SPREAD, not to the mean.
-#include "gemm_core.h"
+#include "pair_tile.h"
 
-using namespace egnn_gemm;
+using namespace egnn_pair;
 
 namespace {
 
-constexpr int GB = 128;
 constexpr int kMoments = 6;         // n, sum a, sum b, sum a^2, sum b^2, sum ab
 constexpr int kVecBlocks = 1024;    // upper bound of the vector kernel's grid
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// first block index of tile row ti in the row-major walk of the upper triangle (row ti holds the T - ti tiles tj = ti .. T-1)
-__host__ __device__ __forceinline__ int64_t tri_row_start(int64_t ti, int64_t T) { return ti * T - ti * (ti - 1) / 2; }
-
-// block index -> (ti, tj), tj >= ti: a float64 estimate of the inverse of tri_row_start, then an exact integer correction
-__device__ __forceinline__ void tri_tile(int64_t b, int64_t T, int64_t& ti_out, int64_t& tj_out) {
-  const double tt = 2.0 * (double)T + 1.0;
-  int64_t ti = (int64_t)((tt - sqrt(fmax(tt * tt - 8.0 * (double)b, 0.0))) * 0.5);
-  ti = ti < 0 ? 0 : (ti > T - 1 ? T - 1 : ti);
-  while (ti > 0 && tri_row_start(ti, T) > b) --ti;
-  while (ti + 1 < T && tri_row_start(ti + 1, T) <= b) ++ti;
-  ti_out = ti;
-  tj_out = ti + (b - tri_row_start(ti, T));
-}
-
-// sum over the 256 threads of K values each, in a fixed order (wave butterfly, then the 4 waves in order); every thread gets the
-// totals.  `red` holds 4 * K doubles and is free again when the call returns.
-template <int K>
-__device__ __forceinline__ void block_sum_f64(double (&m)[K], double* red) {
-  const int lane = egnn_lane();
-  const int wave = egnn_wave_id();
-#pragma unroll
-  for (int q = 0; q < K; ++q) m[q] = wave_sum_f64(m[q]);
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < K; ++q) red[wave * K + q] = m[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < K; ++q) m[q] = ((red[q] + red[K + q]) + red[2 * K + q]) + red[3 * K + q];
-  __syncthreads();
-}
 
 template <bool VEC4>
 __global__ __launch_bounds__(256) void pair_moments_kernel(const float* __restrict__ xs, int64_t lds_, int64_t Ps,
                                                            const float* __restrict__ xt, int64_t ldt, int64_t Pt, int64_t N,
                                                            int64_t T, double* __restrict__ partials) {
-  using TS = TileShape<GB, GB>;
   __shared__ __attribute__((aligned(16))) float smem[TS::SMEM_FLOATS];
   const int64_t b = blockIdx.x;
   int64_t ti, tj;
   tri_tile(b, T, ti, tj);
   const int64_t i0 = ti * GB, j0 = tj * GB;
 
-  IdentityXf id;
   f32x16 as[TS::TM][TS::TN], at[TS::TM][TS::TN];
-  zero_acc(as);
-  zero_acc(at);
-  mainloop<GB, GB, KMAJOR, KMAJOR, VEC4>(as, xs, lds_, i0, N, xs, lds_, j0, N, 0, Ps, id, id, smem);
-  mainloop<GB, GB, KMAJOR, KMAJOR, VEC4>(at, xt, ldt, i0, N, xt, ldt, j0, N, 0, Pt, id, id, smem);
-  // the mainloop's last barrier has passed: its LDS is free
+  gram_pair<VEC4>(as, at, xs, lds_, Ps, xt, ldt, Pt, i0, j0, N, smem);
   double* red = reinterpret_cast<double*>(smem);
 
-  const int lane = egnn_lane();
-  const int wave = egnn_wave_id();
-  const int wm = wave >> 1, wn = wave & 1;
-  // pass 1: pairs of this tile and their means.  row < col keeps the strict upper triangle of a diagonal tile (always true off the
-  // diagonal); col < N cuts the ragged edge.  Tile-local 32-bit form: row - i0 < col - i0 = lc + dj, lc < ncols
-  const int dj = (int)(j0 - i0);
-  const int ncols = (int)(N - j0 < GB ? N - j0 : GB);
+  // pass 1: pairs of this tile and their means
+  const PairGeom g(i0, j0, N);
   float cnt = 0.f, sa = 0.f, sb = 0.f;
-#pragma unroll
-  for (int tn = 0; tn < TS::TN; ++tn) {
-    const int lc = acc_col<GB, GB>(wn, tn, lane);
-#pragma unroll
-    for (int tm = 0; tm < TS::TM; ++tm) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int lr = acc_row<GB, GB>(wm, tm, r, lane);
-        if (lr < lc + dj && lc < ncols) {
-          cnt += 1.f;
-          sa += as[tm][tn][r];
-          sb += at[tm][tn][r];
-        }
-      }
+  for_each_entry([&](int tm, int tn, int r, int lr, int lc) {
+    if (g.above(lr, lc)) {
+      cnt += 1.f;
+      sa += as[tm][tn][r];
+      sb += at[tm][tn][r];
     }
-  }
+  });
   double m1[3] = {(double)cnt, (double)sa, (double)sb};
   block_sum_f64(m1, red);
   const double n = m1[0];
@@ -118,25 +59,16 @@ __global__ __launch_bounds__(256) void pair_moments_kernel(const float* __restri
   const float cb = n > 0.0 ? (float)(m1[2] / n) : 0.f;
   // pass 2: moments about (ca, cb)
   float da = 0.f, db = 0.f, daa = 0.f, dbb = 0.f, dab = 0.f;
-#pragma unroll
-  for (int tn = 0; tn < TS::TN; ++tn) {
-    const int lc = acc_col<GB, GB>(wn, tn, lane);
-#pragma unroll
-    for (int tm = 0; tm < TS::TM; ++tm) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int lr = acc_row<GB, GB>(wm, tm, r, lane);
-        if (lr < lc + dj && lc < ncols) {
-          const float a = as[tm][tn][r] - ca, bb = at[tm][tn][r] - cb;
-          da += a;
-          db += bb;
-          daa = fmaf(a, a, daa);
-          dbb = fmaf(bb, bb, dbb);
-          dab = fmaf(a, bb, dab);
-        }
-      }
+  for_each_entry([&](int tm, int tn, int r, int lr, int lc) {
+    if (g.above(lr, lc)) {
+      const float a = as[tm][tn][r] - ca, bb = at[tm][tn][r] - cb;
+      da += a;
+      db += bb;
+      daa = fmaf(a, a, daa);
+      dbb = fmaf(bb, bb, dbb);
+      dab = fmaf(a, bb, dab);
     }
-  }
+  });
   double m2[5] = {(double)da, (double)db, (double)daa, (double)dbb, (double)dab};
   block_sum_f64(m2, red);
   if (threadIdx.x == 0) {
@@ -196,11 +128,6 @@ __global__ __launch_bounds__(1024) void moments_finalize_kernel(const double* __
   if (threadIdx.x < K) out[threadIdx.x] = red[threadIdx.x][0];
 }
 
-inline int64_t pair_tiles(int64_t N) {
-  const int64_t T = (N + GB - 1) / GB;
-  return T * (T + 1) / 2;
-}
-
 inline int64_t vec_blocks(int64_t n) {
   const int64_t want = (n + 255) / 256;
   return want < kVecBlocks ? want : kVecBlocks;
@@ -238,20 +165,6 @@ __device__ __forceinline__ float sqdist(float ni, float nj, float g) {
   return v > 0.f ? v : 0.f;            // max(v, +0): -0 and NaN become +0, so the bit pattern is a valid bin index
 }
 
-// |x_i|^2 in fp32, one wave per row
-__global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* __restrict__ x, int64_t ld, int64_t P, int64_t N,
-                                                         float* __restrict__ out) {
-  const int lane = egnn_lane();
-  const int64_t row = (int64_t)blockIdx.x * 4 + egnn_wave_id();
-  if (row >= N) return;
-  const float* xr = x + row * ld;
-  float s = 0.f;
-  for (int64_t k = lane; k < P; k += 64) s = fmaf(xr[k], xr[k], s);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if (lane == 0) out[row] = s;
-}
-
 // ++h[bin] for the active lanes.  Unit rows put almost every d into a dozen bins of the first pass, and tied distances put a whole
 // wave on one bin in any pass: the lanes that share the first active lane's bin are counted with a ballot and added once, for up to
 // kAggRounds distinct bins; what is left goes through one LDS atomic per lane.  Called by all 64 lanes together.
@@ -276,7 +189,6 @@ template <int PASS, bool VEC4>
 __global__ __launch_bounds__(256) void sqdist_hist_kernel(const float* __restrict__ x, int64_t ld, int64_t P, int64_t N, int64_t T,
                                                           const float* __restrict__ norms, const SelState* __restrict__ st,
                                                           unsigned long long* __restrict__ ghist) {
-  using TS = TileShape<GB, GB>;
   static_assert(TS::SMEM_FLOATS >= 2 * kHistBins + 2 * GB, "the histograms and the norms live in the mainloop's LDS");
   __shared__ __attribute__((aligned(16))) float smem[TS::SMEM_FLOATS];
   const int64_t b = blockIdx.x;
@@ -309,32 +221,19 @@ __global__ __launch_bounds__(256) void sqdist_hist_kernel(const float* __restric
   constexpr int kTopShift = PASS == 1 ? 20 : 9;
 
   const int lane = egnn_lane();
-  const int wave = egnn_wave_id();
-  const int wm = wave >> 1, wn = wave & 1;
-  const int dj = (int)(j0 - i0);
-  const int ncols = (int)(N - j0 < GB ? N - j0 : GB);
-#pragma unroll
-  for (int tn = 0; tn < TS::TN; ++tn) {
-    const int lc = acc_col<GB, GB>(wn, tn, lane);
-    const float nj = ncol[lc];
-#pragma unroll
-    for (int tm = 0; tm < TS::TM; ++tm) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int lr = acc_row<GB, GB>(wm, tm, r, lane);
-        const bool valid = lr < lc + dj && lc < ncols;
-        const unsigned bits = __float_as_uint(sqdist(nrow[lr], nj, acc[tm][tn][r]));
-        const unsigned bin = (bits >> kBinShift) & kBinMask;
-        if (PASS == 0) {
-          wave_hist_add(lh, bin, valid, lane);
-        } else {
-          const unsigned top = bits >> kTopShift;
-          wave_hist_add(lh, bin, valid && top == p0, lane);
-          if (two) wave_hist_add(lh + kHistBins, bin, valid && top == p1, lane);
-        }
-      }
+  const PairGeom g(i0, j0, N);
+  for_each_entry([&](int lc) { return ncol[lc]; }, [&](int tm, int tn, int r, int lr, int lc, float nj) {
+    const bool valid = g.above(lr, lc);
+    const unsigned bits = __float_as_uint(sqdist(nrow[lr], nj, acc[tm][tn][r]));
+    const unsigned bin = (bits >> kBinShift) & kBinMask;
+    if (PASS == 0) {
+      wave_hist_add(lh, bin, valid, lane);
+    } else {
+      const unsigned top = bits >> kTopShift;
+      wave_hist_add(lh, bin, valid && top == p0, lane);
+      if (two) wave_hist_add(lh + kHistBins, bin, valid && top == p1, lane);
     }
-  }
+  });
   __syncthreads();
   for (int i = tid; i < 2 * kHistBins; i += 256) {
     const unsigned c = lh[i];
@@ -409,7 +308,6 @@ __global__ __launch_bounds__(256) void rbf_rowsum_kernel(const float* __restrict
                                                          const float* __restrict__ xt, int64_t ldt, int64_t Pt, int64_t N, int64_t T,
                                                          int C, const float* __restrict__ norms, const double* __restrict__ sigma2,
                                                          double* __restrict__ rowpart) {
-  using TS = TileShape<GB, GB>;
   __shared__ __attribute__((aligned(16))) float smem[TS::SMEM_FLOATS];
   __shared__ double racc[2][2][GB];      // [wn][q][row]: each entry is owned by one lane of one wave
   __shared__ float nrow[2][GB], ncol[2][GB];
@@ -427,7 +325,6 @@ __global__ __launch_bounds__(256) void rbf_rowsum_kernel(const float* __restrict
     racc[1][q][lr] = 0.0;
   }
   const double scale_s = rbf_scale(sigma2[0]), scale_t = rbf_scale(sigma2[1]);
-  IdentityXf id;
 #pragma unroll 1
   for (int64_t tj = c; tj < T; tj += C) {
     const int64_t j0 = tj * GB;
@@ -436,12 +333,8 @@ __global__ __launch_bounds__(256) void rbf_rowsum_kernel(const float* __restrict
       ncol[q][lc] = j0 + lc < N ? norms[q * N + j0 + lc] : 0.f;
     }
     f32x16 as[TS::TM][TS::TN], at[TS::TM][TS::TN];
-    zero_acc(as);
-    zero_acc(at);
-    mainloop<GB, GB, KMAJOR, KMAJOR, VEC4>(as, xs, lds_, i0, N, xs, lds_, j0, N, 0, Ps, id, id, smem);
-    mainloop<GB, GB, KMAJOR, KMAJOR, VEC4>(at, xt, ldt, i0, N, xt, ldt, j0, N, 0, Pt, id, id, smem);
-    const int dj = (int)(j0 - i0);         // the diagonal entry of row lr is column lr - dj of this tile
-    const int ncols = (int)(N - j0 < GB ? N - j0 : GB);
+    gram_pair<VEC4>(as, at, xs, lds_, Ps, xt, ldt, Pt, i0, j0, N, smem);
+    const PairGeom g(i0, j0, N);           // any tile of the row: the diagonal entry of row lr is column lr - dj of this tile
 #pragma unroll
     for (int tm = 0; tm < TS::TM; ++tm) {
 #pragma unroll
@@ -451,8 +344,8 @@ __global__ __launch_bounds__(256) void rbf_rowsum_kernel(const float* __restrict
 #pragma unroll
         for (int tn = 0; tn < TS::TN; ++tn) {
           const int lc = acc_col<GB, GB>(wn, tn, lane);
-          if (lc < ncols) {
-            const bool diag = lr == lc + dj;
+          if (g.in_cols(lc)) {
+            const bool diag = g.diag(lr, lc);
             ss += diag ? 1.f : rbf_value(sqdist(nrow[0][lr], ncol[0][lc], as[tm][tn][r]), scale_s);
             st += diag ? 1.f : rbf_value(sqdist(nrow[1][lr], ncol[1][lc], at[tm][tn][r]), scale_t);
           }
@@ -508,7 +401,6 @@ __global__ __launch_bounds__(256) void rbf_hsic_kernel(const float* __restrict__
                                                        const float* __restrict__ norms, const double* __restrict__ sigma2,
                                                        const double* __restrict__ mean, const double* __restrict__ msum,
                                                        double* __restrict__ partials) {
-  using TS = TileShape<GB, GB>;
   __shared__ __attribute__((aligned(16))) float smem[TS::SMEM_FLOATS];
   __shared__ float nrow[2][GB], ncol[2][GB], arow[2][GB], acol[2][GB];
   const int64_t b = blockIdx.x;
@@ -527,19 +419,14 @@ __global__ __launch_bounds__(256) void rbf_hsic_kernel(const float* __restrict__
   }
   const double scale_s = rbf_scale(sigma2[0]), scale_t = rbf_scale(sigma2[1]);
 
-  IdentityXf id;
   f32x16 as[TS::TM][TS::TN], at[TS::TM][TS::TN];
-  zero_acc(as);
-  zero_acc(at);
-  mainloop<GB, GB, KMAJOR, KMAJOR, VEC4>(as, xs, lds_, i0, N, xs, lds_, j0, N, 0, Ps, id, id, smem);
-  mainloop<GB, GB, KMAJOR, KMAJOR, VEC4>(at, xt, ldt, i0, N, xt, ldt, j0, N, 0, Pt, id, id, smem);
+  gram_pair<VEC4>(as, at, xs, lds_, Ps, xt, ldt, Pt, i0, j0, N, smem);
   double* red = reinterpret_cast<double*>(smem);
 
   const int lane = egnn_lane();
   const int wave = egnn_wave_id();
   const int wm = wave >> 1, wn = wave & 1;
-  const int dj = (int)(j0 - i0);
-  const int ncols = (int)(N - j0 < GB ? N - j0 : GB);
+  const PairGeom g(i0, j0, N);
   float ukl = 0.f, ukk = 0.f, ull_ = 0.f, dkl = 0.f, dkk = 0.f, dll = 0.f;   // strictly above the diagonal / on it
 #pragma unroll
   for (int tn = 0; tn < TS::TN; ++tn) {
@@ -550,8 +437,8 @@ __global__ __launch_bounds__(256) void rbf_hsic_kernel(const float* __restrict__
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int lr = acc_row<GB, GB>(wm, tm, r, lane);
-        if (lr <= lc + dj && lc < ncols) {
-          const bool diag = lr == lc + dj;
+        if (g.on_or_above(lr, lc)) {
+          const bool diag = g.diag(lr, lc);
           const float k = diag ? 1.f : rbf_value(sqdist(nrow[0][lr], njs, as[tm][tn][r]), scale_s);
           const float l = diag ? 1.f : rbf_value(sqdist(nrow[1][lr], njt, at[tm][tn][r]), scale_t);
           const float kc = (k - arow[0][lr]) - ajs, lcn = (l - arow[1][lr]) - ajt;
@@ -619,8 +506,9 @@ extern "C" int egnn_pair_moments_f32(const float* xs, int64_t ld_s, int64_t Ps, 
   hipStream_t st = (hipStream_t)stream;
   double* partials = static_cast<double*>(ws);
   const bool vec4 = (ld_s % 4 == 0) && (ld_t % 4 == 0) && egnn_aligned16(xs) && egnn_aligned16(xt);
-  if (vec4) hipLaunchKernelGGL(pair_moments_kernel<true>, dim3((unsigned)nblocks), dim3(256), 0, st, xs, ld_s, Ps, xt, ld_t, Pt, N, T, partials);
-  else hipLaunchKernelGGL(pair_moments_kernel<false>, dim3((unsigned)nblocks), dim3(256), 0, st, xs, ld_s, Ps, xt, ld_t, Pt, N, T, partials);
+  dispatch_vec4(vec4, [&](auto v4) {
+    hipLaunchKernelGGL(pair_moments_kernel<v4.value>, dim3((unsigned)nblocks), dim3(256), 0, st, xs, ld_s, Ps, xt, ld_t, Pt, N, T, partials);
+  });
   hipLaunchKernelGGL(moments_finalize_kernel<kMoments>, dim3(1), dim3(1024), 0, st, partials, nblocks, out6);
   return egnn_launch_status();
 }
@@ -663,21 +551,17 @@ extern "C" int egnn_sqdist_median_f32(const float* x, int64_t ld, int64_t P, int
   float* norms = reinterpret_cast<float*>(static_cast<char*>(ws) + hist_bytes() + round8(sizeof(SelState)));
   const unsigned long long m = (unsigned long long)N * (unsigned long long)(N - 1) / 2ull;
   if (hipMemsetAsync(ws, 0, hist_bytes() + round8(sizeof(SelState)), st) != hipSuccess) return egnn_launch_status();
-  hipLaunchKernelGGL(row_sqnorm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, x, ld, P, N, norms);
+  row_sqnorm(x, ld, P, N, norms, st);
   const bool vec4 = (ld % 4 == 0) && egnn_aligned16(x);
-  const dim3 grid((unsigned)nblocks), block(256);
-  unsigned long long* h0 = hist;
-  unsigned long long* h1 = hist + 2 * kHistBins;
-  unsigned long long* h2 = hist + 4 * kHistBins;
-  if (vec4) hipLaunchKernelGGL((sqdist_hist_kernel<0, true>), grid, block, 0, st, x, ld, P, N, T, norms, sel, h0);
-  else hipLaunchKernelGGL((sqdist_hist_kernel<0, false>), grid, block, 0, st, x, ld, P, N, T, norms, sel, h0);
-  hipLaunchKernelGGL(select_scan_kernel<0>, dim3(1), dim3(1024), 0, st, h0, sel, m, out2);
-  if (vec4) hipLaunchKernelGGL((sqdist_hist_kernel<1, true>), grid, block, 0, st, x, ld, P, N, T, norms, sel, h1);
-  else hipLaunchKernelGGL((sqdist_hist_kernel<1, false>), grid, block, 0, st, x, ld, P, N, T, norms, sel, h1);
-  hipLaunchKernelGGL(select_scan_kernel<1>, dim3(1), dim3(1024), 0, st, h1, sel, m, out2);
-  if (vec4) hipLaunchKernelGGL((sqdist_hist_kernel<2, true>), grid, block, 0, st, x, ld, P, N, T, norms, sel, h2);
-  else hipLaunchKernelGGL((sqdist_hist_kernel<2, false>), grid, block, 0, st, x, ld, P, N, T, norms, sel, h2);
-  hipLaunchKernelGGL(select_scan_kernel<2>, dim3(1), dim3(1024), 0, st, h2, sel, m, out2);
+  dispatch_vec4(vec4, [&](auto v4) {
+    auto pass = [&](auto p, unsigned long long* h) {   // h: this pass's [2][kHistBins]
+      hipLaunchKernelGGL((sqdist_hist_kernel<p.value, decltype(v4)::value>), dim3((unsigned)nblocks), dim3(256), 0, st, x, ld, P, N, T, norms, sel, h);
+      hipLaunchKernelGGL(select_scan_kernel<p.value>, dim3(1), dim3(1024), 0, st, h, sel, m, out2);
+    };
+    pass(std::integral_constant<int, 0>{}, hist);
+    pass(std::integral_constant<int, 1>{}, hist + 2 * kHistBins);
+    pass(std::integral_constant<int, 2>{}, hist + 4 * kHistBins);
+  });
   return egnn_launch_status();
 }
 
@@ -702,17 +586,16 @@ extern "C" int egnn_rbf_cka_f32(const float* xs, int64_t ld_s, int64_t Ps, const
   float* norms = reinterpret_cast<float*>(w + lay.norms);
   const int C = row_chunks(N);
   const int64_t nb = (N + 255) / 256;
-  hipLaunchKernelGGL(row_sqnorm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, xs, ld_s, Ps, N, norms);
-  hipLaunchKernelGGL(row_sqnorm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, xt, ld_t, Pt, N, norms + N);
+  row_sqnorm(xs, ld_s, Ps, N, norms, st);
+  row_sqnorm(xt, ld_t, Pt, N, norms + N, st);
   const bool vec4 = (ld_s % 4 == 0) && (ld_t % 4 == 0) && egnn_aligned16(xs) && egnn_aligned16(xt);
-  const dim3 rgrid((unsigned)(T * C)), block(256);
-  if (vec4) hipLaunchKernelGGL(rbf_rowsum_kernel<true>, rgrid, block, 0, st, xs, ld_s, Ps, xt, ld_t, Pt, N, T, C, norms, sigma2_dev, w + lay.rowpart);
-  else hipLaunchKernelGGL(rbf_rowsum_kernel<false>, rgrid, block, 0, st, xs, ld_s, Ps, xt, ld_t, Pt, N, T, C, norms, sigma2_dev, w + lay.rowpart);
-  hipLaunchKernelGGL(rbf_rowmean_kernel, dim3((unsigned)nb), dim3(256), 0, st, w + lay.rowpart, C, N, w + lay.mean, w + lay.blockpart);
-  hipLaunchKernelGGL(moments_finalize_kernel<2>, dim3(1), dim3(1024), 0, st, w + lay.blockpart, nb, w + lay.msum);
-  const dim3 hgrid((unsigned)nblocks);
-  if (vec4) hipLaunchKernelGGL(rbf_hsic_kernel<true>, hgrid, block, 0, st, xs, ld_s, Ps, xt, ld_t, Pt, N, T, norms, sigma2_dev, w + lay.mean, w + lay.msum, w + lay.tilepart);
-  else hipLaunchKernelGGL(rbf_hsic_kernel<false>, hgrid, block, 0, st, xs, ld_s, Ps, xt, ld_t, Pt, N, T, norms, sigma2_dev, w + lay.mean, w + lay.msum, w + lay.tilepart);
+  const dim3 rgrid((unsigned)(T * C)), hgrid((unsigned)nblocks), block(256);
+  dispatch_vec4(vec4, [&](auto v4) {
+    hipLaunchKernelGGL(rbf_rowsum_kernel<v4.value>, rgrid, block, 0, st, xs, ld_s, Ps, xt, ld_t, Pt, N, T, C, norms, sigma2_dev, w + lay.rowpart);
+    hipLaunchKernelGGL(rbf_rowmean_kernel, dim3((unsigned)nb), dim3(256), 0, st, w + lay.rowpart, C, N, w + lay.mean, w + lay.blockpart);
+    hipLaunchKernelGGL(moments_finalize_kernel<2>, dim3(1), dim3(1024), 0, st, w + lay.blockpart, nb, w + lay.msum);
+    hipLaunchKernelGGL(rbf_hsic_kernel<v4.value>, hgrid, block, 0, st, xs, ld_s, Ps, xt, ld_t, Pt, N, T, norms, sigma2_dev, w + lay.mean, w + lay.msum, w + lay.tilepart);
+  });
   hipLaunchKernelGGL(moments_finalize_kernel<3>, dim3(1), dim3(1024), 0, st, w + lay.tilepart, nblocks, out3);
   return egnn_launch_status();
 }
