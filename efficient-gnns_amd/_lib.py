@@ -165,6 +165,9 @@ SIGNATURES = {
     "egnn_fitnet_bwd_f32": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _i64, _p, _i64, _p]),
     "egnn_at_fwd_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _sz, _p]),
     "egnn_at_bwd_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _i64, _p, _i64, _p]),
+    "egnn_at_energy_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _p, _sz, _p]),
+    "egnn_at_partial_f32": (_i32, [_p, _p, _i64, _p, _f32, _p, _p, _p, _sz, _p]),
+    "egnn_at_bwd_rows_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _f32, _p, _p, _i64, _p, _i64, _p]),
     "egnn_saint_induced_geometry": (_i64, [_i32]),
     "egnn_saint_random_walk_i64": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _u64, _p, _p, _p, _p]),
     "egnn_saint_scan_ws_bytes": (_sz, [_i64]),

@@ -157,6 +157,71 @@ __global__ __launch_bounds__(256) void at_bwd_kernel(const float* __restrict__ f
   if (dt) for (int64_t k = lane; k < Dt; k += 64) dt[row * lddt + k] = 2.f * get * t[row * ldt + k];
 }
 
+// ---- attention transfer on node-range shards: the same three steps cut where the ranks' sums meet ---------------------------------
+// The host all-reduces sumsq (2 floats) between energy and partial and sums (3 floats) between partial and the backward; nothing else
+// crosses ranks.  d_i stays in the direct form e_s[i]/ns - e_t[i]/nt: one all-reduce of the moments {sum e_s^2, sum e_t^2, sum e_s e_t}
+// would do, but that closed form cancels (tens of per cent off at e_s ~ k e_t in fp32, the direct form below 1e-5).
+constexpr int kAtPartBlocks = 512;   // 3 partial arrays of the second step fit the 2 kFlBlocks floats the first one uses
+
+__global__ __launch_bounds__(256) void fl_sumq_kernel(const float* __restrict__ partials, int stride, int nb, float* __restrict__ out) {
+  __shared__ float red[256];   // block q: out[q] = sum of partials[q * stride .. + nb), fixed order
+  const float* p = partials + (int64_t)blockIdx.x * stride;
+  float v = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) v += p[i];
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+}
+
+// this rank's partials of sum d^2, sum d e_s, sum d e_t under the GLOBAL norms; scal = {ns, nt, raw |e_s|, raw |e_t|}
+__global__ __launch_bounds__(256) void at_partial_kernel(const float* __restrict__ es, const float* __restrict__ et, int64_t n,
+                                                         const float* __restrict__ sumsq_global, float eps, float* __restrict__ scal,
+                                                         float* __restrict__ partials) {
+  __shared__ float red[3][256];
+  const float raw_s = sqrtf(sumsq_global[0]), raw_t = sqrtf(sumsq_global[1]);
+  const float ns = fmaxf(raw_s, eps), nt = fmaxf(raw_t, eps);
+  float d2 = 0.f, ds = 0.f, dt_ = 0.f;
+  for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float d = es[i] / ns - et[i] / nt;
+    d2 = fmaf(d, d, d2); ds = fmaf(d, es[i], ds); dt_ = fmaf(d, et[i], dt_);
+  }
+  red[0][threadIdx.x] = d2; red[1][threadIdx.x] = ds; red[2][threadIdx.x] = dt_;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o)
+      for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    for (int q = 0; q < 3; ++q) partials[q * kAtPartBlocks + blockIdx.x] = red[q][0];
+    if (blockIdx.x == 0) { scal[0] = ns; scal[1] = nt; scal[2] = raw_s; scal[3] = raw_t; }
+  }
+}
+
+// at_bwd_kernel for a row block of a larger problem: c = 2 g / n_global, the dot products sums = {sum d^2, sum d e_s, sum d e_t} over ALL
+// ranks' rows, the projection term dropped where the GLOBAL raw norm is <= eps
+__global__ __launch_bounds__(256) void at_bwd_rows_kernel(const float* __restrict__ f, int64_t ldf, int64_t Df, const float* __restrict__ t,
+                                                          int64_t ldt, int64_t Dt, int64_t n, int64_t n_global, const float* __restrict__ es,
+                                                          const float* __restrict__ et, const float* __restrict__ scal,
+                                                          const float* __restrict__ sums, float eps, const float* __restrict__ g,
+                                                          float* __restrict__ df, int64_t lddf, float* __restrict__ dt, int64_t lddt) {
+  const int lane = egnn_lane();
+  const int64_t row = blockIdx.x * 4LL + egnn_wave_id();
+  if (row >= n) return;
+  const float ns = scal[0], nt = scal[1];
+  const float d = es[row] / ns - et[row] / nt;
+  const float ps = scal[2] > eps ? es[row] * sums[1] / (ns * ns * ns) : 0.f;
+  const float pt = scal[3] > eps ? et[row] * sums[2] / (nt * nt * nt) : 0.f;
+  const float c = 2.f * g[0] / (float)n_global;
+  const float ges = c * (d / ns - ps), get = -c * (d / nt - pt);
+  if (df) for (int64_t k = lane; k < Df; k += 64) df[row * lddf + k] = 2.f * ges * f[row * ldf + k];
+  if (dt) for (int64_t k = lane; k < Dt; k += 64) dt[row * lddt + k] = 2.f * get * t[row * ldt + k];
+}
+
 }  // namespace
 
 extern "C" size_t egnn_feature_loss_ws_floats(int64_t n) { return 2 * (size_t)kFlBlocks + 2 * (size_t)(n > 0 ? n : 0) + 8; }
@@ -205,5 +270,41 @@ extern "C" int egnn_at_bwd_f32(const float* f, int64_t ldf, int64_t Df, const fl
   const float* scal = et + n;
   hipLaunchKernelGGL(at_bwd_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, f, ldf, Df, t, ldt, Dt, n, es, et, scal, eps, g,
                      df, lddf, dt, lddt);
+  return egnn_launch_status();
+}
+
+// ---- the split form (node-range shards).  ws of the two forward steps: egnn_feature_loss_ws_floats(n) floats, partials only (free after the call)
+extern "C" int egnn_at_energy_f32(const float* f, int64_t ldf, int64_t Df, const float* t, int64_t ldt, int64_t Dt, int64_t n, float* es,
+                                  float* et, float* sumsq, float* ws, size_t ws_floats, void* stream) {
+  EGNN_CHECK_ARG(n > 0 && Df > 0 && Dt > 0 && f && t && es && et && sumsq && ws && ldf >= Df && ldt >= Dt);
+  if (ws_floats < egnn_feature_loss_ws_floats(n)) return EGNN_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t want = (n + 3) / 4;
+  const int nb = (int)(want < kFlBlocks ? want : kFlBlocks);
+  hipLaunchKernelGGL(at_energy_kernel, dim3(nb), dim3(256), 0, st, f, ldf, Df, t, ldt, Dt, n, es, et, ws);
+  hipLaunchKernelGGL(fl_sumq_kernel, dim3(2), dim3(256), 0, st, ws, kFlBlocks, nb, sumsq);
+  return egnn_launch_status();
+}
+
+extern "C" int egnn_at_partial_f32(const float* es, const float* et, int64_t n, const float* sumsq_global, float eps, float* scal, float* sums,
+                                   float* ws, size_t ws_floats, void* stream) {
+  EGNN_CHECK_ARG(n > 0 && es && et && sumsq_global && scal && sums && ws && eps > 0.f);
+  static_assert(3 * kAtPartBlocks <= 2 * kFlBlocks, "the partials of at_partial_kernel must fit egnn_feature_loss_ws_floats");
+  if (ws_floats < egnn_feature_loss_ws_floats(n)) return EGNN_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t want = (n + 255) / 256;
+  const int nb = (int)(want < kAtPartBlocks ? want : kAtPartBlocks);
+  hipLaunchKernelGGL(at_partial_kernel, dim3(nb), dim3(256), 0, st, es, et, n, sumsq_global, eps, scal, ws);
+  hipLaunchKernelGGL(fl_sumq_kernel, dim3(3), dim3(256), 0, st, ws, kAtPartBlocks, nb, sums);
+  return egnn_launch_status();
+}
+
+extern "C" int egnn_at_bwd_rows_f32(const float* f, int64_t ldf, int64_t Df, const float* t, int64_t ldt, int64_t Dt, int64_t n, int64_t n_global,
+                                    const float* es, const float* et, const float* scal, const float* sums_global, float eps, const float* g,
+                                    float* df, int64_t lddf, float* dt, int64_t lddt, void* stream) {
+  EGNN_CHECK_ARG(n > 0 && n_global >= n && Df > 0 && Dt > 0 && f && t && es && et && scal && sums_global && g && ldf >= Df && ldt >= Dt &&
+                 (df == nullptr || lddf >= Df) && (dt == nullptr || lddt >= Dt));
+  hipLaunchKernelGGL(at_bwd_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, f, ldf, Df, t, ldt, Dt, n, n_global,
+                     es, et, scal, sums_global, eps, g, df, lddf, dt, lddt);
   return egnn_launch_status();
 }

@@ -859,6 +859,33 @@ class _DistNCE(torch.autograd.Function):
         return df, dt_all[off:off + Sr].contiguous(), None, None, None, None
 
 
+class _DistAT(torch.autograd.Function):
+    """Attention transfer (criterion.py:39-54) over the train rows of ALL ranks from this rank's rows f [n, Ds] / t [n, Dt]; returns the
+    GLOBAL loss (identical on every rank).  The per-node energies are normalised ACROSS nodes, so the forward meets the peers twice:
+    all-reduce of {sum es^2, sum et^2} (the norms), then of {sum d^2, sum d es, sum d et} for d = es / ns - et / nt (the loss and the two
+    dot products of the backward's projection terms); the backward needs no collective.  ONE all-reduce of the moments
+    {sum es^2, sum et^2, sum es et} would give the same numbers on paper, but that closed form cancels where the student's energies
+    approach a multiple of the teacher's (tens of per cent off in fp32 where the direct form stays below 1e-5).  A rank without rows
+    takes part in both all-reduces with zeros and launches nothing."""
+
+    @staticmethod
+    def forward(ctx, f, t, n_global, eps, group):
+        es, et, sumsq = ops.at_energy(f, t)
+        dist.all_reduce(sumsq, group=group)
+        scal, sums = ops.at_partial(es, et, sumsq, eps)
+        dist.all_reduce(sums, group=group)
+        ctx.save_for_backward(f, t, es, et, scal, sums)
+        ctx.meta = (int(n_global), float(eps))
+        return sums[0] / n_global
+
+    @staticmethod
+    def backward(ctx, g):
+        f, t, es, et, scal, sums = ctx.saved_tensors
+        n_global, eps = ctx.meta
+        df, dt = ops.at_rows_bwd(f, t, n_global, es, et, scal, sums, g, eps, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return df, dt, None, None, None
+
+
 class _GatherSampledRows(torch.autograd.Function):
     """This rank's sampled rows -> the [S, P] matrix of ALL ranks' sampled rows (rank blocks in order).  The consumer (GSP)
     evaluates the full all-pairs loss on every rank -- S <= 4096 rows: milliseconds, no row-block kernel needed -- so every
@@ -1122,6 +1149,8 @@ class ShardedProblem:
         self.static_sample = None        # StaticSample: the sampled criteria run in draw-independent shapes
         self._forced_pick = None
         self._zero = None
+        self._teacher_train_rows = None  # at: the teacher's features at this rank's train rows (constant, gathered at the first step)
+        self._gcd_teacher_agg = None     # gcd: A^ T for the constant teacher features T (one halo exchange per run)
         self.x = data.x[lo:hi].to(device)
         self.adj.register_static(self.x)          # input features never change: halo copy fetched once
         self.y = data.y[lo:hi].to(device)
@@ -1229,6 +1258,26 @@ def _flat_grads_of(optimizer) -> FlatGrads:
     return fg
 
 
+def _gcd_head(proj, x, prob: ShardedProblem, pick_rows: Tensor) -> Tensor:
+    """The rows ``pick_rows`` (unique local row ids, may be empty) of ``models.ProjectionGCD`` on this shard's full rows:
+    relu(bn(lin(x) + conv(x, A^))) with the BatchNorm statistics over every row of every rank (``swap_batchnorm``).  ``x`` = None: the
+    teacher head on ``prob.teacher_out_feat`` T.  T never changes and A^ (T W) = (A^ T) W, so A^ T is formed at the first step and kept
+    (GCNConv's re-association for a constant input, nn.py): the teacher head then needs no halo exchange and no backward aggregation."""
+    if x is None:
+        x = prob.teacher_out_feat
+        if prob._gcd_teacher_agg is None:
+            with torch.no_grad():
+                ax = prob.adj.gcn_normalized().aggregate(x.contiguous(), "sum")
+            prob._gcd_teacher_agg = ops.pad_pitch(ax) if ax.is_cuda else ax
+        conv = ops.matmul(prob._gcd_teacher_agg, proj.conv.weight, proj.conv.bias)
+    else:
+        conv = proj.conv(x, prob.adj)
+    z = ops.linear_add(x, proj.lin.weight, proj.lin.bias, conv)
+    if hasattr(proj.bn, "fused_act"):
+        return proj.bn.fused_act(z, True, 0.0, proj.training, pick=pick_rows)
+    return torch.relu(proj.bn(z))[pick_rows]
+
+
 def _sampled_rows(prob: ShardedProblem, S: int, dev):
     """criterion.py:62-65,134-137 on shards: ONE np.random.choice over the GLOBAL train list (the same draw on every rank), then
     (local positions of the rows this rank owns, as a device tensor; rows per rank).  ``prob.sample_hook`` (ShardedGraphedEpoch)
@@ -1248,12 +1297,12 @@ def _sampled_rows(prob: ShardedProblem, S: int, dev):
 
 def finish_losses(vals, mode: str, hp: dict):
     """(loss, loss_cls, loss_aux) of the GLOBAL problem from the three reduced numbers of ``sharded_train_step_tensors``."""
-    aux_is_global = mode in ("nce", "gpw")
+    aux_is_global = mode in ("nce", "gpw", "at", "gcd")
     loss_cls_g = vals[0]
     loss_aux_g = vals[2] if aux_is_global else vals[1]
     if mode == "kd":
         loss_g = loss_aux_g * (hp["alpha"] * hp["kd_T"] ** 2) + loss_cls_g * (1 - hp["alpha"])
-    elif mode in ("nce", "gpw", "lpw"):
+    elif mode in ("nce", "gpw", "lpw", "fitnet", "at", "gcd"):
         loss_g = loss_cls_g + hp["beta"] * loss_aux_g
     else:
         loss_g = loss_cls_g
@@ -1268,8 +1317,11 @@ def sharded_train_step(model, prob: ShardedProblem, optimizer, mode: str, hp: di
 
 def sharded_train_step_tensors(model, prob: ShardedProblem, optimizer, mode: str, hp: dict, student_proj=None, teacher_proj=None):
     """The step without its host read: forward, loss, backward, gradient all-reduce, Adam, and the all-reduce of the loss terms;
-    returns the device tensor [loss_cls, loss_aux (sum over ranks), loss_aux (already global for nce / gpw)]."""
+    returns the device tensor [loss_cls, loss_aux (sum over ranks), loss_aux (already global for nce / gpw / at / gcd)]."""
     from . import criterion as C
+    if mode == "gcd" and prob.adj._gcn is None:       # (refused before anything runs: no half-made step on some ranks)
+        raise ValueError("sharded 'gcd' needs the normalised adjacency for its projection heads (also under a SAGE student): "
+                         "build the ShardedProblem with need_gcn=True")
     model.train()
     for p in (student_proj, teacher_proj):
         if p is not None:
@@ -1297,6 +1349,18 @@ def sharded_train_step_tensors(model, prob: ShardedProblem, optimizer, mode: str
             return (student_proj.forward_rows(model.out_feat, rows, pick=pick), teacher_proj.forward_rows(prob.teacher_out_feat, rows, pick=pick, const_input=True))
         f, t = student_proj(take(model.out_feat, rows)), teacher_proj(take(prob.teacher_out_feat, rows))
         return (f, t) if pick is None else (f[pick], t[pick])
+
+    def sampled_nce(heads_fn):
+        """G-CRD on the step's global sample (criterion.py:129-149) from ``heads_fn(pick)`` = the two heads' rows at the local train
+        positions ``pick``: static shapes when the draw fits them, the dynamic row blocks otherwise."""
+        if _static_sample_ready(prob):
+            ss = prob.static_sample
+            f, t = heads_fn(ss.idx_dev[:ss.m])
+            fhat_all, t_all = _static_sampled_pair(prob, f, t, normalize=True, reduce_grad=True)
+            return _BalancedNCE.apply(fhat_all, t_all, hp["nce_T"], prob.rank, prob.world, group)
+        idx, counts = _sampled_rows(prob, hp["max_samples"], dev)
+        f, t = heads_fn(idx)
+        return _DistNCE.apply(ops.gather_normalize(f, None), ops.gather_normalize(t, None), hp["nce_T"], counts, prob.rank, group)
     if mode == "supervised":
         loss_cls = ce() if n_tr else attached_zero
         loss_aux = zero
@@ -1310,17 +1374,7 @@ def sharded_train_step_tensors(model, prob: ShardedProblem, optimizer, mode: str
         loss = loss_aux * (hp["alpha"] * hp["kd_T"] ** 2) + loss_cls * (1 - hp["alpha"])
     elif mode == "nce":
         loss_cls = ce() if n_tr else attached_zero
-        if _static_sample_ready(prob):
-            ss = prob.static_sample
-            f, t = heads(ss.idx_dev[:ss.m])
-            fhat_all, t_all = _static_sampled_pair(prob, f, t, normalize=True, reduce_grad=True)
-            loss_aux = _BalancedNCE.apply(fhat_all, t_all, hp["nce_T"], prob.rank, prob.world, group)
-        else:
-            idx, counts = _sampled_rows(prob, hp["max_samples"], dev)
-            f, t = heads(idx)
-            fhat = ops.gather_normalize(f, None)
-            that = ops.gather_normalize(t, None)
-            loss_aux = _DistNCE.apply(fhat, that, hp["nce_T"], counts, prob.rank, group)
+        loss_aux = sampled_nce(heads)
         # loss_aux is already the global value on every rank: scale its gradient contribution once (1/world per rank
         # would double count the all-reduce of parameter grads), so only the local row block's graph carries grad
         loss = loss_cls + hp["beta"] * loss_aux
@@ -1357,6 +1411,32 @@ def sharded_train_step_tensors(model, prob: ShardedProblem, optimizer, mode: str
             # [n_ext, C] is the operator class _audit.CaptureAudit refuses inside a captured step (on this rank only: the ranks diverge)
             loss_aux = f_ext[:1].sum() * 0.0
         loss = loss_cls + hp["beta"] * loss_aux
+    elif mode == "fitnet":
+        # FitNet (criterion.py:24-36) is a mean over rows of one width: the ranks' means, weighted by their share of the train rows, add up
+        loss_cls = ce() if n_tr else attached_zero
+        f, t = heads(None)
+        if n_tr:
+            loss_aux = ops.fitnet_loss(f, t) * frac
+        else:   # no row here: both heads' SyncBN backward collectives stay in the graph (a zero from the empty blocks, no reduction)
+            loss_aux = (f[:1].sum() + t[:1].sum()) * 0.0
+        loss = loss_cls + hp["beta"] * loss_aux
+    elif mode == "at":
+        # attention transfer (criterion.py:39-54): the energies are normalised across ALL train nodes -- see _DistAT
+        loss_cls = ce() if n_tr else attached_zero
+        if prob._teacher_train_rows is None:      # constant: gathered once per run
+            prob._teacher_train_rows = prob.teacher_out_feat.index_select(0, rows)
+            if prob._teacher_train_rows.is_cuda:
+                prob._teacher_train_rows = ops.pad_pitch(prob._teacher_train_rows)
+        loss_aux = _DistAT.apply(take(model.out_feat, rows), prob._teacher_train_rows, prob.n_train_global, 1e-12, group)   # global already
+        loss = loss_cls + hp["beta"] * loss_aux
+    elif mode == "gcd":
+        # G-CRD behind ProjectionGCD (gnn.py:88-99,181-187): both heads run on the shard's FULL rows (all-rank BatchNorm statistics; the
+        # student's aggregation exchanges its halo every step, the teacher's is kept, see _gcd_head); only the sampled train rows are
+        # normalised and stored, and from there on the step is the nce one
+        loss_cls = ce() if n_tr else attached_zero
+        loss_aux = sampled_nce(lambda pick: (_gcd_head(student_proj, model.out_feat, prob, rows.index_select(0, pick)),
+                                             _gcd_head(teacher_proj, None, prob, rows.index_select(0, pick))))
+        loss = loss_cls + hp["beta"] * loss_aux
     else:
         raise NotImplementedError(f"sharded training mode '{mode}'")
     fg = _flat_grads_of(optimizer)
@@ -1364,9 +1444,9 @@ def sharded_train_step_tensors(model, prob: ShardedProblem, optimizer, mode: str
     loss.backward()
     fg.all_reduce(group)
     optimizer.step()
-    aux_is_global = mode in ("nce", "gpw")
+    aux_is_global = mode in ("nce", "gpw", "at", "gcd")
     rep = torch.stack([loss_cls.detach(), loss_aux.detach() if not aux_is_global else zero, loss_aux.detach()])
-    dist.all_reduce(rep[:2], group=group)                     # loss_aux of nce / gpw is already global: not reduced
+    dist.all_reduce(rep[:2], group=group)                     # loss_aux of nce / gpw / at / gcd is already global: not reduced
     return rep
 
 

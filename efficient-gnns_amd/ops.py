@@ -968,6 +968,62 @@ def at_loss(feat: Tensor, teacher_feat: Tensor, eps: float = 1e-12) -> Tensor:
     return _FeatureLoss.apply(feat, teacher_feat, "at", eps)
 
 
+# The same loss on node-range shards (dist._DistAT): three steps with the ranks' two all-reduces in between.  No autograd here -- the
+# caller's Function owns the graph.  A rank without rows launches nothing: empty energies, zero sums.
+def at_energy(f: Tensor, t: Tensor):
+    """(es [n], et [n], sumsq [2]): the row energies sum_d f^2 / sum_d t^2 of this rank's rows and {sum es^2, sum et^2} over them."""
+    _lib.require_gpu(f, t)
+    f, t = _rowmajor(f), _rowmajor(t)
+    if f.dim() != 2 or t.dim() != 2 or f.shape[0] != t.shape[0]:
+        raise ValueError(f"at: student features {tuple(f.shape)} and teacher features {tuple(t.shape)} do not match")
+    n, dev = f.shape[0], f.device
+    if n == 0:
+        return f.new_empty(0), f.new_empty(0), torch.zeros(2, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    es, et = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+    sumsq = torch.empty(2, dtype=torch.float32, device=dev)
+    nws = lib.egnn_feature_loss_ws_floats(n)
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    _lib.check(lib.egnn_at_energy_f32(_lib.ptr(f), f.stride(0), f.shape[1], _lib.ptr(t), t.stride(0), t.shape[1], n, _lib.ptr(es), _lib.ptr(et),
+                                      _lib.ptr(sumsq), _lib.ptr(ws), nws, _lib.stream()), "egnn_at_energy_f32")
+    return es, et, sumsq
+
+
+def at_partial(es: Tensor, et: Tensor, sumsq_global: Tensor, eps: float = 1e-12):
+    """(scal [4] = {ns, nt, raw |e_s|, raw |e_t|}, sums [3] = {sum d^2, sum d es, sum d et} over this rank's rows) for
+    d = es / ns - et / nt under the all-rank norms ns = max(sqrt(sumsq_global[0]), eps), nt likewise."""
+    _lib.require_gpu(es, et, sumsq_global)
+    n, dev = es.shape[0], sumsq_global.device
+    sums = torch.empty(3, dtype=torch.float32, device=dev)
+    scal = torch.empty(4, dtype=torch.float32, device=dev)
+    if n == 0:                         # nothing reads scal on a rank without rows
+        return scal, sums.zero_()
+    lib = _lib.load()
+    nws = lib.egnn_feature_loss_ws_floats(n)
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    _lib.check(lib.egnn_at_partial_f32(_lib.ptr(es), _lib.ptr(et), n, _lib.ptr(sumsq_global), float(eps), _lib.ptr(scal), _lib.ptr(sums),
+                                       _lib.ptr(ws), nws, _lib.stream()), "egnn_at_partial_f32")
+    return scal, sums
+
+
+def at_rows_bwd(f: Tensor, t: Tensor, n_global: int, es: Tensor, et: Tensor, scal: Tensor, sums_global: Tensor, g: Tensor,
+                eps: float = 1e-12, need_df: bool = True, need_dt: bool = True):
+    """(df, dt) of this rank's rows for loss = sums_global[0] / n_global and the upstream gradient ``g``; None where not needed."""
+    _lib.require_gpu(f, t)
+    f, t = _rowmajor(f), _rowmajor(t)
+    n = f.shape[0]
+    df = torch.empty_like(f) if need_df else None
+    dt = torch.empty_like(t) if need_dt else None
+    if n == 0:
+        return df, dt
+    g = g.contiguous().to(torch.float32).reshape(1)
+    _lib.check(_lib.load().egnn_at_bwd_rows_f32(_lib.ptr(f), f.stride(0), f.shape[1], _lib.ptr(t), t.stride(0), t.shape[1], n, int(n_global),
+                                                _lib.ptr(es), _lib.ptr(et), _lib.ptr(scal), _lib.ptr(sums_global), float(eps), _lib.ptr(g),
+                                                _lib.ptr(df), 0 if df is None else df.stride(0), _lib.ptr(dt),
+                                                0 if dt is None else dt.stride(0), _lib.stream()), "egnn_at_bwd_rows_f32")
+    return df, dt
+
+
 # ------------------------------------------------------------------------------------------------
 # G-CRD / InfoNCE on unit rows
 # ------------------------------------------------------------------------------------------------

@@ -605,6 +605,21 @@ int egnn_at_fwd_f32(const float* f, int64_t ldf, int64_t Df, const float* t, int
 int egnn_at_bwd_f32(const float* f, int64_t ldf, int64_t Df, const float* t, int64_t ldt, int64_t Dt, int64_t n, float eps, const float* ws,
                     const float* g, float* df, int64_t lddf, float* dt, int64_t lddt, void* stream);
 
+/* Attention transfer on node-range shards: the same loss cut where the ranks' sums meet.  Each rank holds n of the n_global rows; the
+ * host sums two device arrays over the ranks in between (nothing passes through host memory):
+ *   energy  : es[i] = sum_d f^2, et[i] = sum_d t^2 for the rank's rows; sumsq = {sum es^2, sum et^2} of the rank          -> all-reduce sumsq
+ *   partial : ns = max(sqrt(sumsq_global[0]), eps), nt likewise; d_i = es[i]/ns - et[i]/nt;
+ *             sums = {sum d^2, sum d es, sum d et} of the rank; scal = {ns, nt, raw |e_s|, raw |e_t|} (4 floats)        -> all-reduce sums
+ *   bwd_rows: df / dt (nullable) of the rank's rows for loss = sums_global[0] / n_global, upstream gradient g[0].
+ * ws (energy, partial): egnn_feature_loss_ws_floats(n) floats, free again after the call.  Fixed-order sums, no atomics. */
+int egnn_at_energy_f32(const float* f, int64_t ldf, int64_t Df, const float* t, int64_t ldt, int64_t Dt, int64_t n, float* es, float* et,
+                       float* sumsq, float* ws, size_t ws_floats, void* stream);
+int egnn_at_partial_f32(const float* es, const float* et, int64_t n, const float* sumsq_global, float eps, float* scal, float* sums,
+                        float* ws, size_t ws_floats, void* stream);
+int egnn_at_bwd_rows_f32(const float* f, int64_t ldf, int64_t Df, const float* t, int64_t ldt, int64_t Dt, int64_t n, int64_t n_global,
+                         const float* es, const float* et, const float* scal, const float* sums_global, float eps, const float* g,
+                         float* df, int64_t lddf, float* dt, int64_t lddt, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * GraphSAINT random-walk mini-batches formed on the device (csrc/saint.hip).
  *

@@ -76,6 +76,19 @@ def full_size_cases():
                                                 hidden=256, seed=0, agg="sliced")}
 
 
+def feature_mode_cases():
+    """Reached through --cases only (tests/test_gpu_feature_modes.py): FitNet, attention transfer and G-CRD behind ProjectionGCD on shards,
+    at the weights of record (scripts/run_gcn.sh: fitnet beta = 1000, at beta = 100 000; gnn.py:181-187 for gcd) so that the auxiliary
+    gradient drives steps 2 and 3 -- each under a GCN and a SAGE student, and once with the last rank(s) owning no train row."""
+    cases = {}
+    for mode, sig in (("fitnet", None), ("at", None), ("gcd", 6.0)):
+        cases[f"gcn-{mode}-natural-ov1"] = dict(gnn="gcn", mode=mode, sigmas=sig, order="natural", overlap=1)
+        cases[f"sage-{mode}-natural-ov0"] = dict(gnn="sage", mode=mode, sigmas=sig, order="natural", overlap=0)
+        cases[f"gcn-{mode}-notrain-tail-ov1"] = dict(gnn="gcn", mode=mode, sigmas=sig, order="natural", overlap=1, train_below=0.4)
+    cases["gcn-gcd-overflow-natural-ov1"] = dict(gnn="gcn", mode="gcd", sigmas=-50.0, order="natural", overlap=1)   # the dynamic row blocks
+    return cases
+
+
 def _problem(case, world, dev):
     import efficient_gnns_amd.data as D
     import efficient_gnns_amd.dist as DD
@@ -103,8 +116,9 @@ def _build(case, d, dev):
     model = (PM.GCN if case["gnn"] == "gcn" else PM.SAGE)(d.num_features, hidden, d.num_classes, 3, 0.0).to(dev)
     sp = tp = None
     groups = [{"params": model.parameters(), "lr": 0.01}]
-    if case["mode"] in ("nce", "gpw"):
-        sp, tp = PM.make_projection(hidden, proj).to(dev), PM.make_projection(d.teacher_out_feat.shape[1], proj).to(dev)
+    if case["mode"] in ("nce", "gpw", "fitnet", "gcd"):
+        make = PM.ProjectionGCD if case["mode"] == "gcd" else PM.make_projection
+        sp, tp = make(hidden, proj).to(dev), make(d.teacher_out_feat.shape[1], proj).to(dev)
         groups += [{"params": sp.parameters(), "lr": 0.01}, {"params": tp.parameters(), "lr": 0.01}]
     return model, sp, tp, groups
 
@@ -113,6 +127,8 @@ def _hp(case):
     hp = dict(alpha=0.9, kd_T=4.0, beta=0.1, nce_T=0.075, max_samples=case.get("max_samples", 256), kernel="rbf")
     if case["mode"] in ("gpw", "lpw"):
         hp.update(kernel="cosine", beta=100.0)
+    elif case["mode"] in ("fitnet", "at"):      # scripts/run_gcn.sh
+        hp.update(beta=1000.0 if case["mode"] == "fitnet" else 1e5)
     return hp
 
 
@@ -150,7 +166,7 @@ def _sharded(case, d, world, rank, dev, steps):
         if m is not None:
             DD.swap_batchnorm(m)
     opt = torch.optim.Adam(groups)
-    prob = DD.ShardedProblem(d, world, rank, dev, None, need_gcn=(case["gnn"] == "gcn"))
+    prob = DD.ShardedProblem(d, world, rank, dev, None, need_gcn=(case["gnn"] == "gcn" or case["mode"] == "gcd"))   # gcd: the heads' GCNConv
     if case["sigmas"] is not None:
         prob.static_sample = DD.StaticSample(prob, hp["max_samples"], sigmas=case["sigmas"])
     with DD.CommTrace() as trace:
@@ -179,7 +195,7 @@ def _worker(rank, world, port, names, out_path, steps):
         from efficient_gnns_amd import _lib, hostcomm
         assert not hasattr(_lib, "HOST_STANDINS")      # (round 6: the product has no stand-in switch any more)
         hostcomm.install()
-        cases = dict(all_cases(), **full_size_cases())
+        cases = dict(all_cases(), **full_size_cases(), **feature_mode_cases())
         report = {}
         for name in names:
             case = cases[name]
