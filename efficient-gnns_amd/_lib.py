@@ -86,6 +86,8 @@ SIGNATURES = {
     "egnn_bn_stats_merge_f32": (_i32, [_p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _sz, _p]),
     "egnn_spmm_combine_f32": (_i32, [_p, _p, _p, _i64, _p, _i64, _p]),
     "egnn_spmm_csr_max_bwd_f32": (_i32, [_i64, _i64, _p, _i32, _p, _p, _p, _i64, _p, _i64, _p]),
+    "egnn_spmm_csr_max_piece_f32": (_i32, [_p, _p, _i32, _p, _p]),
+    "egnn_spmm_csr_max_bwd_rows_f32": (_i32, [_i64, _i64, _i64, _p, _p, _i32, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p]),
     "egnn_spmm_algorithmic_bytes": (_i64, [_i64, _i64, _i64, _i64, _i32, _i32]),
     "egnn_csr_from_coo_ws_bytes": (_sz, [_i64, _i64, _i32]),
     "egnn_csr_from_coo_i64": (_i32, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _sz, _p]),

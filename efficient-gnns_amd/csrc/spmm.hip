@@ -52,29 +52,35 @@ constexpr int kUnroll = 4;
 
 // Accumulate entries [start, end) of one row into acc (and arg for max).  All 64 lanes take part in
 // the broadcasts; lanes whose column is out of range (colok == false) only skip the loads.
-template <typename IdxT, int VEC, bool IS_MAX>
+// PIECE (max over one piece of a row set, egnn_spmm_csr_max_piece_f32): the id recorded for entry e is entry_id[e] (e itself when
+// entry_id is null), read with the same coalesced load as the column and broadcast with it.
+template <typename IdxT, int VEC, bool IS_MAX, bool PIECE = false>
 __device__ __forceinline__ void accumulate_range(const SpmmArgs<IdxT>& a, int64_t start, int64_t end, int64_t col0,
                                                  bool colok, int lane, int sub, float (&acc)[VEC],
-                                                 int64_t (&arg)[VEC]) {
+                                                 int64_t (&arg)[VEC], const int64_t* entry_id = nullptr) {
   const int npw = 64 >> a.logG;
   for (int64_t base = start; base < end; base += 64) {
     const int64_t rem = end - base;
     const int n = rem < 64 ? (int)rem : 64;
     long long c_l = 0;
+    long long id_l = 0;
     float v_l = 1.f;
     if (lane < n) {
       c_l = (long long)a.col[base + lane];
+      if constexpr (PIECE) id_l = entry_id ? (long long)entry_id[base + lane] : (long long)(base + lane);
       if (a.val) v_l = a.val[base + lane];
       if (a.src_scale) v_l *= a.src_scale[c_l];
     }
     for (int j0 = 0; j0 < n; j0 += npw * kUnroll) {
       float xv[kUnroll][VEC];
       float vv[kUnroll];
+      long long ee[PIECE ? kUnroll : 1];
       bool ok[kUnroll];
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         ok[u] = false;
         vv[u] = 0.f;
+        if constexpr (PIECE) ee[u] = 0;
 #pragma unroll
         for (int q = 0; q < VEC; ++q) xv[u][q] = 0.f;
         if (j0 + u * npw < n) {  // wave-uniform
@@ -83,6 +89,7 @@ __device__ __forceinline__ void accumulate_range(const SpmmArgs<IdxT>& a, int64_
           const int jj = ok[u] ? j : n - 1;  // clamp: same cache line as a live lane, never out of bounds
           const long long c = __shfl(c_l, jj);
           vv[u] = __shfl(v_l, jj);
+          if constexpr (PIECE) ee[u] = __shfl(id_l, jj);
           if (colok) {
             const float* xp = a.X + c * a.ldx + col0;
             if constexpr (VEC == 4) {
@@ -98,7 +105,8 @@ __device__ __forceinline__ void accumulate_range(const SpmmArgs<IdxT>& a, int64_
       for (int u = 0; u < kUnroll; ++u) {
         if (j0 + u * npw < n) {
           if constexpr (IS_MAX) {
-            const int64_t e = base + j0 + u * npw + sub;
+            int64_t e = base + j0 + u * npw + sub;
+            if constexpr (PIECE) e = (int64_t)ee[u];
 #pragma unroll
             for (int q = 0; q < VEC; ++q) {
               const float cand = vv[u] * xv[u][q];
@@ -160,13 +168,9 @@ __device__ __forceinline__ void store_row(const SpmmArgs<IdxT>& a, int64_t row, 
   }
 }
 
-// ---- wave-per-(row, slice) kernel ---------------------------------------------------------------
-template <typename IdxT, int VEC, bool IS_MAX>
-__global__ __launch_bounds__(256) void spmm_rows_kernel(const SpmmArgs<IdxT> a) {
-  const int lane = egnn_lane();
-  const int wave = egnn_wave_id();
-  const int64_t b = blockIdx.x;
-  int64_t slice, rg;
+// block b of a wave-per-(row, slice) launch -> (column slice, group of four rows): the slice <-> XCD binding of the header comment
+template <typename IdxT>
+__device__ __forceinline__ void block_slice_and_row_group(const SpmmArgs<IdxT>& a, int64_t b, int64_t& slice, int64_t& rg) {
   if (a.map_mode == 1) {  // NS in {1,2,4,8}: XCD x = b % 8 owns slice x % NS
     const int x = (int)(b & 7);
     const int r = 8 / a.NS;
@@ -182,6 +186,16 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(const SpmmArgs<IdxT> a) 
     slice = b % a.NS;
     rg = b / a.NS;
   }
+}
+
+// ---- wave-per-(row, slice) kernel ---------------------------------------------------------------
+template <typename IdxT, int VEC, bool IS_MAX>
+__global__ __launch_bounds__(256) void spmm_rows_kernel(const SpmmArgs<IdxT> a) {
+  const int lane = egnn_lane();
+  const int wave = egnn_wave_id();
+  const int64_t b = blockIdx.x;
+  int64_t slice, rg;
+  block_slice_and_row_group(a, b, slice, rg);
   const int64_t ridx = rg * 4 + wave;
   if (ridx >= a.n_list) return;
   const int64_t row = a.rows ? a.rows[ridx] : ridx;
@@ -204,6 +218,49 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(const SpmmArgs<IdxT> a) 
     const int64_t cnt = end - start;
     const float inv = a.mean ? 1.f / (float)(cnt > 0 ? cnt : 1) : 1.f;
     store_row<IdxT, VEC, IS_MAX>(a, row, col0, inv, acc, arg);
+  }
+}
+
+// ---- max over one PIECE of a row set: wave-per-(row, slice), merging into the state earlier pieces left -----------------------
+// The geometry of spmm_rows_kernel over rows 0..n_rows-1.  merge == 0: (Y, argmax) are written from scratch.  merge != 0: the stored
+// pair of the row competes with this piece's winner under max_merge unless it is empty (argmax < 0: its Y value is not compared).
+// The wave owns its row's state: one read and one write of each element, no atomics.
+template <typename IdxT, int VEC>
+__global__ __launch_bounds__(256) void spmm_max_piece_kernel(const SpmmArgs<IdxT> a, const int64_t* __restrict__ entry_id, int merge) {
+  const int lane = egnn_lane();
+  const int wave = egnn_wave_id();
+  const int64_t b = blockIdx.x;
+  int64_t slice, rg;
+  block_slice_and_row_group(a, b, slice, rg);
+  const int64_t row = rg * 4 + wave;
+  if (row >= a.n_rows) return;
+  const int64_t start = (int64_t)a.rowptr[row];
+  const int64_t end = (int64_t)a.rowptr[row + 1];
+
+  const int G = 1 << a.logG;
+  const int sub = lane >> a.logG;
+  const int li = lane & (G - 1);
+  const int64_t col0 = (slice * G + li) * VEC;
+  const bool colok = col0 < a.K;
+
+  float acc[VEC];
+  int64_t arg[VEC];
+#pragma unroll
+  for (int q = 0; q < VEC; ++q) { acc[q] = 0.f; arg[q] = -1; }
+  accumulate_range<IdxT, VEC, true, true>(a, start, end, col0, colok, lane, sub, acc, arg, entry_id);
+  cross_sub_reduce<VEC, true>(a.logG, acc, arg);
+  if (sub == 0 && colok) {
+    if (merge) {
+      const float* yp = a.Y + row * a.ldy + col0;
+      const int64_t* ap = a.argmax + row * a.K + col0;
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) {
+        const float ov = yp[q];
+        const int64_t oe = ap[q];
+        max_merge(acc[q], arg[q], ov, oe);   // an empty stored state (oe < 0) never wins: its value stays out of the comparison
+      }
+    }
+    store_row<IdxT, VEC, true>(a, row, col0, 1.f, acc, arg);
   }
 }
 
@@ -447,25 +504,10 @@ struct RowPlan {
   const int64_t* long_rows; int64_t n_long;
 };
 
-template <typename IdxT, int VEC, bool IS_MAX>
-void launch_wave_per_row(SpmmArgs<IdxT> a, const int64_t* rows, int64_t n_list, hipStream_t st) {
-  if (n_list <= 0) return;
-  a.rows = rows;
-  a.n_list = n_list;
-  const int64_t rgroups = (n_list + 3) / 4;
-  int64_t grid;
-  if (a.map_mode == 1) {
-    const int r = 8 / a.NS;
-    grid = ((rgroups + r - 1) / r) * 8;
-  } else {
-    grid = rgroups * a.NS;
-  }
-  hipLaunchKernelGGL((spmm_rows_kernel<IdxT, VEC, IS_MAX>), dim3((unsigned)grid), dim3(256), 0, st, a);
-}
-
-template <typename IdxT, int VEC, bool IS_MAX>
-int launch(SpmmArgs<IdxT> a, const RowPlan& plan, hipStream_t st) {
-  // slice geometry: 128-byte slices (G = 8 float4 lanes) whenever K allows, else one slice per <=64 lanes
+// slice geometry of the wave-per-(row, slice) kernels: 128-byte slices (G = 8 float4 lanes) whenever K allows, else one slice per
+// <=64 lanes; false when a launch over all n_rows would not fit a grid
+template <typename IdxT, int VEC>
+bool slice_geometry(SpmmArgs<IdxT>& a) {
   const int64_t kv = (a.K + VEC - 1) / VEC;  // columns in VEC units
   if (VEC == 4 && kv % 8 == 0) {
     a.logG = 3;
@@ -475,7 +517,32 @@ int launch(SpmmArgs<IdxT> a, const RowPlan& plan, hipStream_t st) {
     a.NS = (int)((kv + (1 << a.logG) - 1) >> a.logG);
   }
   a.map_mode = (a.NS <= 8 && 8 % a.NS == 0) ? 1 : (a.NS % 8 == 0 ? 2 : 0);
-  if ((a.n_rows + 3) / 4 * (int64_t)a.NS > 0x7fffffffLL) return EGNN_EINVAL;
+  return (a.n_rows + 3) / 4 * (int64_t)a.NS <= 0x7fffffffLL;
+}
+
+// blocks of a wave-per-(row, slice) launch over n_list rows
+template <typename IdxT>
+int64_t rows_grid(const SpmmArgs<IdxT>& a, int64_t n_list) {
+  const int64_t rgroups = (n_list + 3) / 4;
+  if (a.map_mode == 1) {
+    const int r = 8 / a.NS;
+    return ((rgroups + r - 1) / r) * 8;
+  }
+  return rgroups * a.NS;
+}
+
+template <typename IdxT, int VEC, bool IS_MAX>
+void launch_wave_per_row(SpmmArgs<IdxT> a, const int64_t* rows, int64_t n_list, hipStream_t st) {
+  if (n_list <= 0) return;
+  a.rows = rows;
+  a.n_list = n_list;
+  const int64_t grid = rows_grid(a, n_list);
+  hipLaunchKernelGGL((spmm_rows_kernel<IdxT, VEC, IS_MAX>), dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+template <typename IdxT, int VEC, bool IS_MAX>
+int launch(SpmmArgs<IdxT> a, const RowPlan& plan, hipStream_t st) {
+  if (!slice_geometry<IdxT, VEC>(a)) return EGNN_EINVAL;
   const bool planned = plan.short_rows || plan.mid_rows || plan.long_rows;
   if (!planned) {
     launch_wave_per_row<IdxT, VEC, IS_MAX>(a, nullptr, a.n_rows, st);
@@ -605,7 +672,154 @@ __global__ void spmm_max_bwd_kernel(int64_t total, int64_t K, const IdxT* col, c
   }
 }
 
+template <typename IdxT, int VEC>
+int launch_max_piece(SpmmArgs<IdxT> a, const int64_t* entry_id, int merge, hipStream_t st) {
+  if (!slice_geometry<IdxT, VEC>(a)) return EGNN_EINVAL;
+  const int64_t grid = rows_grid(a, a.n_rows);
+  hipLaunchKernelGGL((spmm_max_piece_kernel<IdxT, VEC>), dim3((unsigned)grid), dim3(256), 0, st, a, entry_id, merge);
+  return egnn_launch_status();
+}
+
+template <typename IdxT>
+int dispatch_max_piece(const egnn_spmm_t& op, const int64_t* entry_id, int merge, int64_t* argmax, hipStream_t st) {
+  SpmmArgs<IdxT> a = spmm_args<IdxT>(op, kSpmmGather);
+  a.argmax = argmax;
+  const bool vec4 = (a.K % 4 == 0) && (a.ldx % 4 == 0) && (a.ldy % 4 == 0) && egnn_aligned16(a.X) && egnn_aligned16(a.Y);
+  return vec4 ? launch_max_piece<IdxT, 4>(a, entry_id, merge, st) : launch_max_piece<IdxT, 1>(a, entry_id, merge, st);
+}
+
+// ---- backward of max as a GATHER over the transposed piece: wave per source row, lanes over the columns --------------------------
+// dX[j,k] = addend[j,k] + sum over the transposed entries p of row j, in t_rowptr order, of (argmax[t_row[p],k] == t_eid[p] ?
+// val[t_eid[p]] * dY[t_row[p],k] : 0).  The wave reads up to 64 (target row, forward id, value) triples with one coalesced load and
+// broadcasts them lane to lane; four targets' argmax / dY rows are in flight per step.  Every row of dX is written (no zero-fill by
+// the caller), nothing is shared between waves (no atomics) and the order of the sum is the entry order (bit-stable).
+template <typename IdxT, int VEC>
+__global__ __launch_bounds__(256) void spmm_max_bwd_rows_kernel(int64_t n_src, int64_t K, const IdxT* __restrict__ t_rowptr,
+                                                                const IdxT* __restrict__ t_row, const int64_t* __restrict__ t_eid,
+                                                                const float* __restrict__ val, const int64_t* __restrict__ argmax,
+                                                                const float* __restrict__ dY, int64_t ldy,
+                                                                const float* __restrict__ addend, int64_t ld_add,
+                                                                float* __restrict__ dX, int64_t ldx) {
+  const int lane = egnn_lane();
+  const int64_t j = (int64_t)blockIdx.x * 4 + egnn_wave_id();
+  if (j >= n_src) return;
+  const int64_t start = (int64_t)t_rowptr[j];
+  const int64_t end = (int64_t)t_rowptr[j + 1];
+  for (int64_t cb = 0; cb < K; cb += 64 * VEC) {   // wave-uniform: every lane takes part in the broadcasts
+    const int64_t col0 = cb + (int64_t)lane * VEC;
+    const bool colok = col0 < K;
+    float acc[VEC];
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) acc[q] = 0.f;
+    if (addend && colok) {
+      const float* ap = addend + j * ld_add + col0;
+      if constexpr (VEC == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(ap);
+        acc[0] = t.x; acc[1] = t.y; acc[2] = t.z; acc[3] = t.w;
+      } else {
+        acc[0] = *ap;
+      }
+    }
+    for (int64_t base = start; base < end; base += 64) {
+      const int64_t rem = end - base;
+      const int n = rem < 64 ? (int)rem : 64;
+      long long r_l = 0, id_l = 0;
+      float v_l = 1.f;
+      if (lane < n) {
+        r_l = (long long)t_row[base + lane];
+        id_l = (long long)t_eid[base + lane];
+        if (val) v_l = val[id_l];
+      }
+      for (int j0 = 0; j0 < n; j0 += kUnroll) {
+        long long am[kUnroll][VEC];
+        float g[kUnroll][VEC];
+        long long id[kUnroll];
+        float v[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+          id[u] = 0;
+          v[u] = 0.f;
+#pragma unroll
+          for (int q = 0; q < VEC; ++q) { am[u][q] = -1; g[u][q] = 0.f; }   // -1 equals no forward id
+          if (j0 + u < n) {  // wave-uniform
+            const long long r = __shfl(r_l, j0 + u);
+            id[u] = __shfl(id_l, j0 + u);
+            v[u] = __shfl(v_l, j0 + u);
+            if (colok) {
+              const int64_t* mp = argmax + r * K + col0;
+              const float* gp = dY + r * ldy + col0;
+              if constexpr (VEC == 4) {
+                const longlong2 m0 = *reinterpret_cast<const longlong2*>(mp);
+                const longlong2 m1 = *reinterpret_cast<const longlong2*>(mp + 2);
+                const float4 t = *reinterpret_cast<const float4*>(gp);
+                am[u][0] = m0.x; am[u][1] = m0.y; am[u][2] = m1.x; am[u][3] = m1.y;
+                g[u][0] = t.x; g[u][1] = t.y; g[u][2] = t.z; g[u][3] = t.w;
+              } else {
+                am[u][0] = (long long)*mp;
+                g[u][0] = *gp;
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+          if (j0 + u < n) {
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) acc[q] = (am[u][q] == id[u]) ? fmaf(v[u], g[u][q], acc[q]) : acc[q];
+          }
+        }
+      }
+    }
+    if (colok) {
+      float* xp = dX + j * ldx + col0;
+      if constexpr (VEC == 4) *reinterpret_cast<float4*>(xp) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+      else xp[0] = acc[0];
+    }
+  }
+}
+
+template <typename IdxT>
+int launch_max_bwd_rows(int64_t n_src, int64_t K, const void* t_rowptr, const void* t_row, const int64_t* t_eid, const float* val,
+                        const int64_t* argmax, const float* dY, int64_t ldy, const float* addend, int64_t ld_add, float* dX,
+                        int64_t ldx, hipStream_t st) {
+  const int64_t grid = (n_src + 3) / 4;
+  if (grid > 0x7fffffffLL) return EGNN_EINVAL;
+  const bool vec4 = (K % 4 == 0) && (ldy % 4 == 0) && (ldx % 4 == 0) && egnn_aligned16(dY) && egnn_aligned16(dX) && egnn_aligned16(argmax) &&
+                    (!addend || (ld_add % 4 == 0 && egnn_aligned16(addend)));
+  if (vec4)
+    hipLaunchKernelGGL((spmm_max_bwd_rows_kernel<IdxT, 4>), dim3((unsigned)grid), dim3(256), 0, st, n_src, K, (const IdxT*)t_rowptr,
+                       (const IdxT*)t_row, t_eid, val, argmax, dY, ldy, addend, ld_add, dX, ldx);
+  else
+    hipLaunchKernelGGL((spmm_max_bwd_rows_kernel<IdxT, 1>), dim3((unsigned)grid), dim3(256), 0, st, n_src, K, (const IdxT*)t_rowptr,
+                       (const IdxT*)t_row, t_eid, val, argmax, dY, ldy, addend, ld_add, dX, ldx);
+  return egnn_launch_status();
+}
+
 }  // namespace
+
+extern "C" int egnn_spmm_csr_max_piece_f32(const egnn_spmm_t* op, const int64_t* entry_id, int merge, int64_t* argmax, void* stream) {
+  const int rc = spmm_check(op, kSpmmGather, /*max_ok=*/true);   // addend / stat_part / ReLU: EGNN_EINVAL (no epilogue here)
+  if (rc != EGNN_OK) return rc;
+  EGNN_CHECK_ARG(op->reduce == EGNN_MAX && op->bias == nullptr && (merge == 0 || merge == 1));
+  if (op->n_rows == 0 || op->K == 0) return EGNN_OK;
+  EGNN_CHECK_ARG(op->rowptr && op->col && op->X && op->Y && argmax);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return op->index_bits == 32 ? dispatch_max_piece<int32_t>(*op, entry_id, merge, argmax, st)
+                              : dispatch_max_piece<int64_t>(*op, entry_id, merge, argmax, st);
+}
+
+extern "C" int egnn_spmm_csr_max_bwd_rows_f32(int64_t n_src, int64_t n_rows, int64_t K, const void* t_rowptr, const void* t_row,
+                                              int index_bits, const int64_t* t_eid, const float* val, const int64_t* argmax,
+                                              const float* dY, int64_t ldy, const float* addend, int64_t ld_addend, float* dX,
+                                              int64_t ldx, void* stream) {
+  EGNN_CHECK_ARG(n_src >= 0 && n_rows >= 0 && K >= 0 && (index_bits == 32 || index_bits == 64));
+  if (n_src == 0 || K == 0) return EGNN_OK;
+  EGNN_CHECK_ARG(t_rowptr && t_row && t_eid && argmax && dY && dX && ldy >= K && ldx >= K && (!addend || ld_addend >= K));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return index_bits == 32
+             ? launch_max_bwd_rows<int32_t>(n_src, K, t_rowptr, t_row, t_eid, val, argmax, dY, ldy, addend, ld_addend, dX, ldx, st)
+             : launch_max_bwd_rows<int64_t>(n_src, K, t_rowptr, t_row, t_eid, val, argmax, dY, ldy, addend, ld_addend, dX, ldx, st);
+}
 
 extern "C" int egnn_spmm_csr_f32(const egnn_spmm_t* op, int64_t* argmax, const int64_t* short_rows, int64_t n_short,
                                  const int64_t* mid_rows, int64_t n_mid, const int64_t* long_rows, int64_t n_long, void* stream) {

@@ -447,6 +447,74 @@ class _SlicedAggregate(torch.autograd.Function):
         return g_x, None, None, g_b, None
 
 
+class _MaxPlan:
+    """What max-aggregation on a shard needs besides the two pieces of ``ShardedAdj._split``: the id of every piece entry in the entry
+    numbering of ``plan.local_adj()`` (``eid_own`` / ``eid_halo``: ``split_adj`` keeps the entry order, so both are ascending and strictly
+    increasing within a row) and, for the gather-form backward, the transposed pieces with the forward id of every transposed entry.
+    ``val``: the values of ``local_adj()`` (indexed by forward id), None for the value-less form."""
+
+    def __init__(self, plan: ShardPlan, own: SparseTensor, halo: SparseTensor, val: Tensor | None, device):
+        remote = plan.remote_mask
+        self.own, self.halo = own, halo
+        self.eid_own = torch.nonzero(~remote).view(-1).to(device).contiguous()
+        self.eid_halo = torch.nonzero(remote).view(-1).to(device).contiguous()
+        self.val = None if val is None else val.to(device).contiguous()
+        # transposed piece: rowptr = t_rowptr [n_src + 1], col = t_row (stable sort by column: target rows ascending per source)
+        self.own_t, self.halo_t = own.t(), halo.t()
+        self.t_eid_own = self.eid_own[own._transpose_meta()[1]].contiguous()
+        self.t_eid_halo = self.eid_halo[halo._transpose_meta()[1]].contiguous()
+
+
+class _MaxAggregate(torch.autograd.Function):
+    """``ShardedAdj.aggregate(x, "max")``: y = max over the row's entries of [own | halo] columns, as ONE running (value, argmax) state
+    -- the own-column piece is reduced from scratch while the halo rows travel, the halo-column piece then merges into it (ties: the
+    first maximal entry of the whole row in CSR order, as on one GPU; argmax in ``local_adj()`` numbering).  Backward: the gather-form
+    kernel on the transposed pieces (no atomics, fixed order) -- the halo piece's gradient rows go back through the reverse exchange
+    under the own piece's, and are folded into their owners by ``sadj.scatter``.  ``_OVERLAP`` off: the same kernels after a blocking
+    exchange."""
+
+    @staticmethod
+    def forward(ctx, x_local, sadj, mp, static_halo):
+        plan, group = sadj.plan, sadj.group
+        x_local = x_local.contiguous()
+        K = x_local.shape[1]
+        work = None
+        if static_halo is not None:
+            x_halo = static_halo
+        else:      # EVERY rank takes part in the exchange, whatever its own pieces hold
+            send_buf = x_local.index_select(0, sadj.send_idx_dev).contiguous()
+            x_halo = torch.empty(plan.n_halo, K, dtype=x_local.dtype, device=x_local.device)
+            work = dist.all_to_all_single(x_halo, send_buf, plan.recv_counts, plan.send_counts, group=group, async_op=_OVERLAP)
+        y, arg = ops.spmm_max_piece(mp.own, x_local, mp.eid_own, False)        # (n_local == 0: nothing is launched)
+        if work is not None and _OVERLAP:
+            work.wait()
+        if plan.n_halo:
+            y, arg = ops.spmm_max_piece(mp.halo, x_halo, mp.eid_halo, True, y, arg)
+        ctx.sadj, ctx.mp = sadj, mp
+        ctx.save_for_backward(arg)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        sadj, mp = ctx.sadj, ctx.mp
+        (arg,) = ctx.saved_tensors
+        plan, group = sadj.plan, sadj.group
+        g_y = g_y.contiguous()
+        K = g_y.shape[1]
+        back = torch.empty(plan.send_idx.numel(), K, dtype=g_y.dtype, device=g_y.device)
+        if plan.n_halo:
+            g_halo = ops.spmm_max_bwd_rows(mp.halo_t, mp.t_eid_halo, mp.val, arg, g_y)
+        else:
+            g_halo = torch.zeros(0, K, dtype=g_y.dtype, device=g_y.device)
+        work = dist.all_to_all_single(back, g_halo, plan.send_counts, plan.recv_counts, group=group, async_op=_OVERLAP)
+        g_x = ops.spmm_max_bwd_rows(mp.own_t, mp.t_eid_own, mp.val, arg, g_y)  # runs while the halo gradients travel back
+        if _OVERLAP:
+            work.wait()
+        if back.shape[0]:
+            g_x = _agg(sadj.scatter, back, addend=g_x)                         # fixed-order accumulation into the owners' rows
+        return g_x, None, None, None
+
+
 class _ShardedSageLayer(torch.autograd.Function):
     """``ops._SageLayer`` on a node-range shard: SAGEConv (``lin_l(aggr_j x_j) + lin_r(x_i)``, gnn.py:79-84) as ONE autograd node whose
     aggregation is the overlapped halo-exchange form above -- ``lin_r(x)`` is the addend of the GEMM / aggregation store, the input
@@ -536,6 +604,7 @@ class ShardedAdj:
         self.raw = self.plan.local_adj(dev)
         self.scatter = self.plan.scatter_adj(dev)
         self._pieces = {}
+        self._max_plans = {}
         self._static = None
         self._full = {}
         plan = self.plan
@@ -664,13 +733,28 @@ class ShardedAdj:
             self._pieces[key] = (own, halo)
         return self._pieces[key]
 
+    def _max_plan(self, valueless: bool) -> _MaxPlan:
+        """The cached ``_MaxPlan`` of this adjacency, per (valueless,)."""
+        key = (bool(valueless),)
+        if key not in self._max_plans:
+            own, halo = self._split(False, valueless)
+            val = None if valueless else self.plan.value_local
+            self._max_plans[key] = _MaxPlan(self.plan, own, halo, val, self.device)
+        return self._max_plans[key]
+
     def aggregate(self, x_local: Tensor, reduce: str, valueless: bool = False, bias: Tensor | None = None, relu: bool = False) -> Tensor:
         """``bias`` [K]: added to every row in the aggregation's store (GCNConv's bias: no separate pass over [n, K]); ``relu``
-        (inference only): clamp in the same store (the eval-mode BatchNorm fold of GCNConv)."""
-        if reduce not in ("sum", "add", "mean"):
-            raise NotImplementedError(f"sharded aggregation supports sum / mean, not '{reduce}'")
+        (inference only): clamp in the same store (the eval-mode BatchNorm fold of GCNConv).  ``max`` takes neither (ValueError) and
+        always runs in halo form (``_MaxAggregate``): ``sliced_pays`` / EGNN_DIST_AGG=sliced do not apply to it."""
+        if reduce not in ("sum", "add", "mean", "max"):
+            raise NotImplementedError(f"sharded aggregation supports sum / mean / max, not '{reduce}'")
         st = self._static
         static = st is not None and st[0] is x_local and not x_local.requires_grad and x_local._version == st[2]   # version AT registration
+        if reduce == "max":
+            # max does not decompose over column slices or into a sum of pieces: always the halo form, as one merged (value, argmax) state
+            if bias is not None or relu:
+                raise ValueError("sharded max aggregation has no bias / ReLU epilogue (the max kernels have none)")
+            return _MaxAggregate.apply(x_local, self, self._max_plan(valueless), st[1][self.plan.n_local:] if static else None)
         if not static and self.sliced_pays(x_local.shape[1]):      # (a registered static input travels once per run: nothing to save)
             return _SlicedAggregate.apply(x_local, self, self.full_adj(reduce == "mean", valueless), bias, relu)
         if _OVERLAP:
@@ -1490,6 +1574,9 @@ class ShardedGraphedEpoch(ReplayedEpoch):
 
     def __init__(self, model, prob: ShardedProblem, optimizer, mode: str, hp: dict, student_proj=None, teacher_proj=None, warmup: int = 3,
                  static_sample: bool | None = None):
+        if any(type(m).__name__ == "SAGEConv" and getattr(m, "aggr", None) == "max" for m in model.modules()):
+            raise ValueError("ShardedGraphedEpoch does not capture a model with a max-aggregation SAGEConv: sharded max aggregation "
+                             "(dist._MaxAggregate) runs with eager launches only")
         if not prob.x.is_cuda:
             raise ValueError("ShardedGraphedEpoch needs GPU tensors")
         if not self.capturable(prob.world, mode):

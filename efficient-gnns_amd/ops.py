@@ -321,6 +321,71 @@ def spmm(adj, x: Tensor, reduce: str = "sum", bias: Tensor | None = None, bn_sta
     return y
 
 
+def spmm_max_piece(adj, x: Tensor, entry_id: Tensor | None = None, merge: bool = False, y: Tensor | None = None,
+                   argmax: Tensor | None = None, src_scale: Tensor | None = None):
+    """max-aggregation over ONE PIECE of a row set (egnn_spmm_csr_max_piece_f32): ``adj`` holds some of the rows' entries, ``entry_id``
+    [nnz] int64 the id ``argmax`` records for each of them (None: the entry's own position; strictly increasing within a row).
+    ``merge=False`` writes (Y, argmax) from scratch; ``merge=True`` merges the piece into the state ``y`` / ``argmax`` hold, in place
+    (larger value wins, equal values: smaller id; a state with argmax < 0 is empty).  Returns (Y, argmax).  No autograd: the
+    sharded run's ``dist._MaxAggregate`` drives it."""
+    _lib.require_gpu(x, adj._col)
+    x = _rowmajor(x)
+    n_rows, n_src = adj.sparse_sizes()
+    if x.shape[0] != n_src:
+        raise ValueError(f"spmm_max_piece: adjacency has {n_src} columns, x has {x.shape[0]} rows")
+    K = x.shape[1]
+    if merge:
+        if (y is None or argmax is None or tuple(y.shape) != (n_rows, K) or tuple(argmax.shape) != (n_rows, K) or y.dtype != torch.float32
+                or argmax.dtype != torch.int64 or y.stride(1) != 1 or not argmax.is_contiguous()):
+            raise ValueError("spmm_max_piece(merge=True) needs the float32 [n_rows, K] / contiguous int64 [n_rows, K] state of the earlier pieces")
+    else:
+        y = torch.empty(n_rows, K, dtype=torch.float32, device=x.device)
+        argmax = torch.empty(n_rows, K, dtype=torch.int64, device=x.device)
+    if n_rows == 0 or K == 0:
+        return y, argmax
+    if adj.nnz() == 0:   # a piece without entries changes no state; from scratch every row is empty
+        if not merge:
+            y.zero_()
+            argmax.fill_(-1)
+        return y, argmax
+    if entry_id is not None and (entry_id.dtype != torch.int64 or entry_id.numel() != adj.nnz() or not entry_id.is_contiguous()):
+        raise ValueError("spmm_max_piece: `entry_id` is a contiguous int64 [nnz] vector")
+    rowptr, col, bits = adj._index_arrays()
+    op = _spmm_desc(adj, rowptr, col, bits, x, y, _REDUCE["max"], src_scale, None)
+    rc = _lib.load().egnn_spmm_csr_max_piece_f32(ctypes.byref(op), _lib.ptr(entry_id), int(bool(merge)), _lib.ptr(argmax), _lib.stream())
+    _lib.check(rc, "egnn_spmm_csr_max_piece_f32")
+    return y, argmax
+
+
+def spmm_max_bwd_rows(t_adj, t_eid: Tensor, val: Tensor | None, argmax: Tensor, gy: Tensor, addend: Tensor | None = None) -> Tensor:
+    """Backward of a max piece as a gather (egnn_spmm_csr_max_bwd_rows_f32): ``t_adj`` is the TRANSPOSED piece ([n_src, n_rows]: its
+    rowptr / col are t_rowptr / t_row), ``t_eid`` [nnz] int64 the forward id of every transposed entry, ``val`` the values indexed by
+    forward id (None = 1).  Returns dX [n_src, K] with every row written: ``addend`` + the picked gradients, added in entry order."""
+    _lib.require_gpu(gy, t_adj._col)
+    gy = _rowmajor(gy)
+    n_src, n_rows = t_adj.sparse_sizes()
+    K = gy.shape[1]
+    if gy.shape[0] != n_rows or tuple(argmax.shape) != (n_rows, K) or argmax.dtype != torch.int64 or not argmax.is_contiguous():
+        raise ValueError("spmm_max_bwd_rows: dY is [n_rows, K] and argmax a contiguous int64 [n_rows, K]")
+    if addend is not None:
+        if tuple(addend.shape) != (n_src, K):
+            raise ValueError("spmm_max_bwd_rows: `addend` is a float32 [n_src, K] matrix")
+        addend = _rowmajor(addend)
+    gx = torch.empty(n_src, K, dtype=torch.float32, device=gy.device)
+    if n_src == 0 or K == 0:
+        return gx
+    if t_adj.nnz() == 0:   # nobody picked anything
+        return gx.zero_() if addend is None else gx.copy_(addend)
+    if t_eid.dtype != torch.int64 or t_eid.numel() != t_adj.nnz() or not t_eid.is_contiguous():
+        raise ValueError("spmm_max_bwd_rows: `t_eid` is a contiguous int64 [nnz] vector")
+    rowptr, col, bits = t_adj._index_arrays()
+    rc = _lib.load().egnn_spmm_csr_max_bwd_rows_f32(n_src, n_rows, K, _lib.ptr(rowptr), _lib.ptr(col), bits, _lib.ptr(t_eid), _lib.ptr(val),
+                                                    _lib.ptr(argmax), _lib.ptr(gy), gy.stride(0), _lib.ptr(addend),
+                                                    0 if addend is None else addend.stride(0), _lib.ptr(gx), gx.stride(0), _lib.stream())
+    _lib.check(rc, "egnn_spmm_csr_max_bwd_rows_f32")
+    return gx
+
+
 class _TakeRows(torch.autograd.Function):
     """x[idx] for UNIQUE row ids: the backward is a plain scatter (ATen's index backward sorts the ids every step)."""
 

@@ -61,7 +61,7 @@ int egnn_build_info(char* buf, size_t buf_bytes);
  *   src_scale  [n_src] nullable; per-source-row factor, used for the backward of mean (dX = A^T (dY / cnt)) without
  *                      materialising a per-entry value array
  *   bias       [K]     nullable; added to every written row (GCNConv `out += bias`, gnn.py:47); not with EGNN_MAX
- *   reduce             EGNN_SUM, EGNN_MEAN (sum / max(stored entries of the row, 1)), EGNN_MAX (egnn_spmm_csr_f32 only)
+ *   reduce             EGNN_SUM, EGNN_MEAN (sum / max(stored entries of the row, 1)), EGNN_MAX (egnn_spmm_csr_f32 and egnn_spmm_csr_max_piece_f32 only)
  * The epilogue is read by egnn_spmm_csr_blk_f32 and egnn_spmm_combine_f32 only.  The other two schedules have none: there addend,
  * stat_part or flags bit 3 set is EGNN_EINVAL (a fused add or ReLU is never silently dropped); the store hints are ignored.
  *   addend     nullable [n_rows, ld_addend] fp32: added to every stored row (Y = A X + addend): the sharded run aggregates
@@ -161,6 +161,36 @@ int egnn_spmm_combine_f32(const egnn_spmm_t* op, const int64_t* comb_rows, const
 int egnn_spmm_csr_max_bwd_f32(int64_t n_rows, int64_t K, const void* col, int index_bits, const float* val,
                               const int64_t* argmax, const float* dY, int64_t ldy, float* dX, int64_t ldx,
                               void* stream);
+
+/* EGNN_MAX over one PIECE of a row set -- the sharded run aggregates a shard's own columns while the halo rows travel and then
+ * merges the halo columns' piece into the same (Y, argmax) state.  Descriptor as for egnn_spmm_csr_f32 with reduce == EGNN_MAX (val,
+ * src_scale as there; bias, addend, stat_part or flags bit 3 set is EGNN_EINVAL: there is no epilogue); every row of [0, n_rows) takes the
+ * one-wavefront path (64-entry chunks, float4 lanes where K % 4 == 0 and the rows are 16-byte aligned, else scalar lanes).
+ *   entry_id   nullable [nnz] int64: the id recorded in argmax for entry e of this piece (NULL: e itself).  Must be strictly increasing
+ *              within a row.  The sharded run passes the entry's position in the unsplit [own | halo] matrix, so that the merged argmax
+ *              is the one a single egnn_spmm_csr_f32(EGNN_MAX) call over that matrix writes, bit for bit.
+ *   merge      0: Y / argmax are written from scratch (an empty row: 0.0 and -1; with entry_id == NULL the result of egnn_spmm_csr_f32
+ *              with its three row lists NULL).  1: Y / argmax hold the state earlier pieces over the same rows left.  A state with
+ *              argmax < 0 is EMPTY and its Y value is not compared; otherwise the stored pair competes with this piece's candidates:
+ *              the larger value wins, on equal values the smaller id.  A row that stays empty keeps 0.0 and -1.
+ *   argmax     [n_rows, K] int64, required
+ * No atomics: each wavefront owns its row's state.  The result does not depend on the order the pieces are applied in.
+ * (op is the descriptor above, named by its struct tag.) */
+int egnn_spmm_csr_max_piece_f32(const struct egnn_spmm* op, const int64_t* entry_id, int merge, int64_t* argmax, void* stream);
+
+/* Backward of EGNN_MAX as a GATHER over the TRANSPOSED piece (deterministic; the form the sharded run uses):
+ *   dX[j,k] = addend[j,k] + sum_p (argmax[t_row[p],k] == t_eid[p] ? val[t_eid[p]] * dY[t_row[p],k] : 0),  p in [t_rowptr[j], t_rowptr[j+1])
+ * added in p order.  EVERY row j of dX [n_src, K] is written -- no zero-fill by the caller; rows no target picked receive the addend,
+ * or an exact 0 -- no atomics, fixed summation order (run-to-run bit-stable).
+ *   t_rowptr   [n_src + 1], t_row [nnz]: the transposed structure (target row of transposed entry p), index_bits wide
+ *   t_eid      [nnz] int64: the forward id of transposed entry p, in the numbering argmax is expressed in
+ *   val        nullable, indexed by FORWARD id (= 1.0)
+ *   argmax     [n_rows, K] int64 (leading dimension K), dY [n_rows, ldy]
+ *   addend     nullable [n_src, ld_addend]
+ * Reads nnz * K argmax words against the n_rows * K of the scatter form above. */
+int egnn_spmm_csr_max_bwd_rows_f32(int64_t n_src, int64_t n_rows, int64_t K, const void* t_rowptr, const void* t_row, int index_bits,
+                                   const int64_t* t_eid, const float* val, const int64_t* argmax, const float* dY, int64_t ldy,
+                                   const float* addend, int64_t ld_addend, float* dX, int64_t ldx, void* stream);
 
 /* Algorithmic (compulsory) HBM bytes of one egnn_spmm_csr_f32 call, SURVEY.md 8(d):
  * 4*n_src*K (read X) + 4*n_rows*K (write Y) + nnz*(index bytes + value bytes) + rowptr. */

@@ -89,6 +89,18 @@ def feature_mode_cases():
     return cases
 
 
+def max_aggregation_cases():
+    """Reached through --cases only (tests/test_gpu_sharded_max_multirank.py): a SAGE student with max aggregation on shards
+    (dist._MaxAggregate: own piece, merged halo piece, gather-form backward) in both exchange orders, with the last rank(s) owning no train
+    row, and with the column-sliced form forced -- which max never takes: that case too must move its rows through the halo exchange."""
+    base = dict(gnn="sage", aggr="max", sigmas=None, scale=0.02)
+    return {"sage-max-supervised-natural-ov1": dict(base, mode="supervised", order="natural", overlap=1),
+            "sage-max-kd-natural-ov0": dict(base, mode="kd", order="natural", overlap=0),
+            "sage-max-lpw-community-ov1": dict(base, mode="lpw", order="community", overlap=1),
+            "sage-max-kd-notrain-tail-ov1": dict(base, mode="kd", order="natural", overlap=1, train_below=0.4),
+            "sage-max-kd-sliced-natural-ov1": dict(base, mode="kd", order="natural", overlap=1, agg="sliced")}
+
+
 def _problem(case, world, dev):
     import efficient_gnns_amd.data as D
     import efficient_gnns_amd.dist as DD
@@ -113,7 +125,10 @@ def _build(case, d, dev):
     hidden, proj = case.get("hidden", 64), case.get("proj", 32)
     torch.manual_seed(0)
     np.random.seed(0)
-    model = (PM.GCN if case["gnn"] == "gcn" else PM.SAGE)(d.num_features, hidden, d.num_classes, 3, 0.0).to(dev)
+    if case["gnn"] == "gcn":
+        model = PM.GCN(d.num_features, hidden, d.num_classes, 3, 0.0).to(dev)
+    else:
+        model = PM.SAGE(d.num_features, hidden, d.num_classes, 3, 0.0, aggr=case.get("aggr", "mean")).to(dev)
     sp = tp = None
     groups = [{"params": model.parameters(), "lr": 0.01}]
     if case["mode"] in ("nce", "gpw", "fitnet", "gcd"):
@@ -195,7 +210,7 @@ def _worker(rank, world, port, names, out_path, steps):
         from efficient_gnns_amd import _lib, hostcomm
         assert not hasattr(_lib, "HOST_STANDINS")      # (round 6: the product has no stand-in switch any more)
         hostcomm.install()
-        cases = dict(all_cases(), **full_size_cases(), **feature_mode_cases())
+        cases = dict(all_cases(), **full_size_cases(), **feature_mode_cases(), **max_aggregation_cases())
         report = {}
         for name in names:
             case = cases[name]
@@ -225,7 +240,9 @@ def _worker(rank, world, port, names, out_path, steps):
                          per_rank=infos, note=note, seconds=round(time.perf_counter() - t0, 2), host_staged=hostcomm.stats())
             entry["ok"] = bool(logit_err <= 1.0 and loss_err <= 1.0 and acc_err <= 1.5 / min_split and bad is None
                                and all(i["n_halo"] > 0 for i in infos)
-                               and (all(i["comm"]["halo_all_to_all_bytes_sent"] > 0 for i in infos) if case.get("agg") != "sliced"
+                               # (max aggregation has no column-sliced form: its rows travel in the halo exchange also where "sliced" is forced)
+                               and (all(i["comm"]["halo_all_to_all_bytes_sent"] > 0 for i in infos)
+                                    if case.get("agg") != "sliced" or case.get("aggr") == "max"
                                     else all(i["comm"].get("sliced_exchanges", 0) > 0 for i in infos)))
             report[name] = entry
             with open(out_path, "w") as f:      # after every case: a crash in a later one keeps what has been compared
