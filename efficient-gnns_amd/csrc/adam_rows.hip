@@ -12,6 +12,14 @@
 // hands the verdict to its G - 1 neighbours through a width-G shuffle, so the replay trip count is uniform per row.  A row is claimed
 // with a compare-and-swap on `last[r]`, so a table row named twice in one batch is served once (catch-up) or counted (step) and never
 // read while another group writes it.  All stores are ordinary vector stores; no float atomics: results are bit-stable.
+//
+// The summing step (egnn_adam_rows_step_sum_f32) takes a list that may name a table row several times (several batches of one optimiser
+// step, or the batches of several ranks).  The selected entries get 64-bit keys (row << shift) | entry, the keys are radix-sorted over
+// the bits they use, and the lane group at the first key of a row's run walks the run forward: the row's gradient rows are added in
+// registers in ascending entry order, scaled once, and the row takes ONE step through the same device functions.  Only the head's
+// group touches the row, so runs that cross a workgroup boundary need no hand-over.
+#include <hipcub/hipcub.hpp>
+
 #include "common.h"
 
 namespace {
@@ -42,15 +50,24 @@ __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g,
   p -= step_size * (m / (sqrtf(v) / bc2_sqrt + eps));
 }
 
-// steps tau = from .. to of table row r with the gradient row g (nullptr: zero) over the columns of sub-lane `sub`
+// the four gradient columns c .. c + 3 of one gradient row (nullptr: zero)
+struct RowGrad {
+  const float* __restrict__ g_row;
+  __device__ __forceinline__ float4 operator()(int64_t c) const {
+    return g_row ? *reinterpret_cast<const float4*>(g_row + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+};
+
+// steps tau = from .. to of table row r with the gradient columns grad(c) over the columns of sub-lane `sub`
+template <class GradAt>
 __device__ __forceinline__ void row_steps(const egnn_adam_rows_t& a, const float* s_ss, const float* s_bc, int64_t r, int sub, int G,
-                                          int from, int to, const float* __restrict__ g_row) {
+                                          int from, int to, GradAt grad) {
   for (int64_t c = (int64_t)sub * 4; c < a.D; c += (int64_t)G * 4) {
     const int64_t o = r * a.ld + c;
     float4 p4 = *reinterpret_cast<const float4*>(a.p + o);
     float4 m4 = *reinterpret_cast<const float4*>(a.m + o);
     float4 v4 = *reinterpret_cast<const float4*>(a.v + o);
-    const float4 g4 = g_row ? *reinterpret_cast<const float4*>(g_row + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 g4 = grad(c);
     float p[4] = {p4.x, p4.y, p4.z, p4.w}, m[4] = {m4.x, m4.y, m4.z, m4.w}, v[4] = {v4.x, v4.y, v4.z, v4.w};
     const float g[4] = {g4.x, g4.y, g4.z, g4.w};
     for (int tau = from; tau <= to; ++tau) {
@@ -96,7 +113,7 @@ __global__ __launch_bounds__(THREADS) void adam_rows_catchup_kernel(egnn_adam_ro
     if (l != -1 && l < a.step && atomicCAS(a.last + r, l, a.step) == l) from = l + 1;
   }
   from = __shfl(from, 0, 1 << lg);
-  if (from <= a.step) row_steps(a, s_ss, s_bc, r, sub, 1 << lg, from, a.step, nullptr);
+  if (from <= a.step) row_steps(a, s_ss, s_bc, r, sub, 1 << lg, from, a.step, RowGrad{nullptr});
 }
 
 // the step: claim step - 1 -> step (or -1 -> step for a row's first gradient); a loser is counted in dup_count and writes nothing
@@ -121,7 +138,87 @@ __global__ __launch_bounds__(THREADS) void adam_rows_step_kernel(egnn_adam_rows_
     if (!win) atomicAdd(a.dup_count, 1);
   }
   win = __shfl(win, 0, 1 << lg);
-  if (win) row_steps(a, s_ss, s_bc, r, sub, 1 << lg, a.step, a.step, g + i * ldg);
+  if (win) row_steps(a, s_ss, s_bc, r, sub, 1 << lg, a.step, a.step, RowGrad{g + i * ldg});
+}
+
+// ---- the summing step --------------------------------------------------------------------------------------------------------------
+constexpr size_t kAlign = 256;
+constexpr uint64_t NO_KEY = ~uint64_t(0);              // an entry of another type or outside the table: sorts behind every row
+inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
+
+static int bits_for(uint64_t v) {  // number of bits needed to represent values in [0, v]
+  int b = 1;
+  while (b < 64 && (v >> b) != 0) ++b;
+  return b;
+}
+
+// hipCUB sizes the sort's temporary storage from the current device's configuration: false when that query fails (no device)
+static bool sort_keys_temp(int64_t n, int end_bit, size_t* bytes) {
+  *bytes = 0;
+  return hipcub::DeviceRadixSort::SortKeys(nullptr, *bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n, 0, end_bit) == hipSuccess;
+}
+
+// keys[i] = (local_idx[i] << shift) | i for a selected entry inside the table; a selected entry outside it is counted here (keys ==
+// nullptr: an empty table, count only)
+__global__ __launch_bounds__(THREADS) void adam_rows_keys_kernel(int64_t n_rows, int32_t* __restrict__ dup_count, int type_id,
+                                                                 const int64_t* __restrict__ node_type,
+                                                                 const int64_t* __restrict__ local_idx, int64_t n, int shift,
+                                                                 uint64_t* __restrict__ keys) {
+  const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (i >= n) return;
+  uint64_t key = NO_KEY;
+  if (!node_type || node_type[i] == (int64_t)type_id) {
+    const int64_t r = local_idx[i];
+    if (r >= 0 && r < n_rows) key = ((uint64_t)r << shift) | (uint64_t)i;
+    else atomicAdd(dup_count, 1);
+  }
+  if (keys) keys[i] = key;
+}
+
+// scale * (((g[i1] + g[i2]) + ...) + g[ik]) over the run of sorted keys that starts at j (all of table row r, ascending entry)
+struct RunGrad {
+  const uint64_t* __restrict__ sorted;
+  int64_t j, n;
+  uint64_t r;
+  int shift;
+  const float* __restrict__ g;
+  int64_t ldg;
+  float scale;
+  __device__ __forceinline__ float4 operator()(int64_t c) const {
+    const uint64_t entry_mask = (uint64_t(1) << shift) - 1;
+    float4 s = *reinterpret_cast<const float4*>(g + (int64_t)(sorted[j] & entry_mask) * ldg + c);
+    for (int64_t q = j + 1; q < n; ++q) {
+      const uint64_t k = sorted[q];
+      if ((k >> shift) != r) break;
+      const float4 x = *reinterpret_cast<const float4*>(g + (int64_t)(k & entry_mask) * ldg + c);
+      s.x += x.x; s.y += x.y; s.z += x.z; s.w += x.w;
+    }
+    return make_float4(scale * s.x, scale * s.y, scale * s.z, scale * s.w);
+  }
+};
+
+// one lane group per sorted key; the group at the head of a row's run claims the row like adam_rows_step_kernel and steps it once
+__global__ __launch_bounds__(THREADS) void adam_rows_step_sum_kernel(egnn_adam_rows_t a, const uint64_t* __restrict__ sorted, int64_t n,
+                                                                     int shift, const float* __restrict__ g, int64_t ldg, float scale,
+                                                                     int lg) {
+  __shared__ float s_ss[RING], s_bc[RING];
+  stage_ring(a, s_ss, s_bc);
+  const int64_t j = (int64_t)blockIdx.x * (THREADS >> lg) + (threadIdx.x >> lg);
+  const int sub = threadIdx.x & ((1 << lg) - 1);
+  if (j >= n) return;
+  const uint64_t key = sorted[j];
+  if (key == NO_KEY) return;
+  const uint64_t r = key >> shift;
+  if (j > 0 && (sorted[j - 1] >> shift) == r) return;          // not the head of its run
+  int win = 0;
+  if (sub == 0) {
+    int old = atomicCAS(a.last + r, a.step - 1, a.step);
+    win = old == a.step - 1;
+    if (!win && old == -1) win = atomicCAS(a.last + r, -1, a.step) == -1;
+    if (!win) atomicAdd(a.dup_count, 1);
+  }
+  win = __shfl(win, 0, 1 << lg);
+  if (win) row_steps(a, s_ss, s_bc, (int64_t)r, sub, 1 << lg, a.step, a.step, RunGrad{sorted, j, n, r, shift, g, ldg, scale});
 }
 
 struct Tables {
@@ -215,5 +312,46 @@ extern "C" int egnn_adam_rows_step_f32(const egnn_adam_rows_t* a, int type_id, c
   const int lg = lanes_lg(a->D);
   hipLaunchKernelGGL(adam_rows_step_kernel, dim3((unsigned)blocks_for(n, lg)), dim3(THREADS), 0, (hipStream_t)stream, *a, type_id, node_type,
                      local_idx, n, g, ldg, lg);
+  return egnn_launch_status();
+}
+
+extern "C" size_t egnn_adam_rows_step_sum_ws_bytes(int64_t n, int64_t n_rows) {
+  if (n <= 0 || n >= 0x7fffffffLL || n_rows <= 0 || n_rows >= 0x7fffffffLL) return kAlign;
+  const int end_bit = bits_for((uint64_t)n - 1) + bits_for((uint64_t)n_rows);
+  size_t temp = 0;
+  if (!sort_keys_temp(n, end_bit, &temp)) temp = 0;      // no device to ask: the key arrays alone (the step itself then refuses)
+  return 2 * align_up((size_t)n * 8) + align_up(temp) + kAlign;
+}
+
+extern "C" int egnn_adam_rows_step_sum_f32(const egnn_adam_rows_t* a, int type_id, const int64_t* node_type, const int64_t* local_idx,
+                                           int64_t n, const float* g, int64_t ldg, float scale, void* ws, size_t ws_bytes,
+                                           void* stream) {
+  const int rc = check_rows(a, 1);
+  if (rc != EGNN_OK) return rc;
+  EGNN_CHECK_ARG(local_idx && g && n >= 0 && ldg >= a->D);
+  EGNN_CHECK_ARG(n < 0x7fffffffLL && a->n_rows < 0x7fffffffLL);     // hipCUB item counts are int; row and entry share one 64-bit key
+  if (ldg % 4 != 0 || !egnn_aligned16(g)) return EGNN_EALIGN;
+  if (n == 0) return EGNN_OK;
+  if (!ws || ws_bytes < egnn_adam_rows_step_sum_ws_bytes(n, a->n_rows)) return EGNN_EWORKSPACE;
+  if (!egnn_aligned16(ws)) return EGNN_EALIGN;
+  size_t temp = 0;
+  if (a->n_rows > 0 && !sort_keys_temp(n, bits_for((uint64_t)n - 1) + bits_for((uint64_t)a->n_rows), &temp)) return EGNN_ELAUNCH;
+  if (a->n_rows == 0) {                                              // every selected entry is outside the table: counted, nothing sorted
+    hipLaunchKernelGGL(adam_rows_keys_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream,
+                       a->n_rows, a->dup_count, type_id, node_type, local_idx, n, 1, (uint64_t*)nullptr);
+    return egnn_launch_status();
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int shift = bits_for((uint64_t)n - 1), end_bit = shift + bits_for((uint64_t)a->n_rows);
+  char* p = (char*)ws;
+  uint64_t* keys = (uint64_t*)p;   p += align_up((size_t)n * 8);
+  uint64_t* sorted = (uint64_t*)p; p += align_up((size_t)n * 8);
+  size_t tb = ws_bytes - (size_t)(p - (char*)ws);
+  hipLaunchKernelGGL(adam_rows_keys_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, a->n_rows, a->dup_count,
+                     type_id, node_type, local_idx, n, shift, keys);
+  if (hipcub::DeviceRadixSort::SortKeys(p, tb, keys, sorted, (int)n, 0, end_bit, st) != hipSuccess) return EGNN_ELAUNCH;
+  const int lg = lanes_lg(a->D);
+  hipLaunchKernelGGL(adam_rows_step_sum_kernel, dim3((unsigned)blocks_for(n, lg)), dim3(THREADS), 0, st, *a, sorted, n, shift, g, ldg, scale,
+                     lg);
   return egnn_launch_status();
 }

@@ -16,6 +16,9 @@ tests).  Collectives on the data path, all with autograd:
   * parameters               -- one flat ``all_reduce`` of all gradients per step (~0.5 MB: latency-bound).
 
 Everything else (local aggregation, GEMMs, losses) is the single-GPU kernel path on the local shard.
+
+The MAG mini-batch workload is not sharded by node range but run data-parallel (``mag_dp_train_epoch``): every rank samples its own
+GraphSAINT batches, the dense gradients travel in one flat all-reduce and the embedding tables exchange only their batch rows.
 """
 from __future__ import annotations
 
@@ -1672,6 +1675,126 @@ class ShardedGraphedEpoch(ReplayedEpoch):
         vals = host_vals.tolist()
         accs = tuple(vals[3 + i] / max(1, self.prob.split_sizes[k]) for i, k in enumerate(("train", "valid", "test")))
         return finish_losses(vals[:3], self.mode, self.hp), accs
+
+
+# ------------------------------------------------------------------------------------------------
+# data-parallel MAG mini-batch epoch: every rank its own batches, only the batch rows of the tables travel
+# ------------------------------------------------------------------------------------------------
+LAST_DP_STATS: dict = {}     # what the last ``mag_dp_train_epoch`` of this process moved, per round (identical on every rank)
+
+
+def _dp_local_rows(tables, D: int, dev):
+    """This rank's table-gradient rows of one round as ONE list: ``(g [n, D], idx [n, 2] = (node_type, local_idx))`` in which table ``k``
+    owns the entries of node type ``k``.  The usual case -- one ``ops.group_input`` backward left the same three arrays with every table,
+    each under its own type id -- passes them on as they are.  Anything else (several deposits for a table, different arrays per
+    table, a deposit without a type vector or under another id) is merged in table order, then deposit order: every deposit's rows,
+    typed ``k`` where the deposit selects them and -1 elsewhere, so no gradient row is lost."""
+    deps = [(k, d) for k, st in tables for d in st.deposits]
+    if not deps:
+        return torch.zeros(0, D, dtype=torch.float32, device=dev), torch.zeros(0, 2, dtype=torch.int64, device=dev)
+    g0, nt0, li0, _ = deps[0][1]
+    shared = nt0 is not None and all(len(st.deposits) <= 1 for _, st in tables) and \
+        all(d[0] is g0 and d[1] is nt0 and d[2] is li0 and d[3] == k for k, d in deps)
+    if shared:
+        return g0, torch.stack([nt0, li0], dim=1)
+    gs, idx = [], []
+    for k, (g, nt, li, tid) in deps:
+        own = torch.ones_like(li, dtype=torch.bool) if nt is None else nt == tid
+        gs.append(g)
+        idx.append(torch.stack([torch.where(own, torch.full_like(li, k), torch.full_like(li, -1)), li], dim=1))
+    return torch.cat(gs), torch.cat(idx)
+
+
+def mag_dp_train_epoch(model, loader, x_dict, optimizer, mode, hp, teacher_model=None, student_proj=None, teacher_proj=None, group=None,
+                       seed=None):
+    """One data-parallel MAG epoch over replicas that stay equal: ``loader`` is this rank's slice of ONE batch stream
+    (``saint.GraphSAINTRandomWalkSampler(..., rank=r, world=W)``); a round is one batch per rank (none for a rank whose share has run
+    out) and ends in one optimisation step whose gradient is the mean of the round's batch-loss gradients -- what
+    ``models.mag_accumulate_epoch(accumulate=W, seed=seed)`` computes on one device over the same stream.
+
+    Per round: the dense gradients travel in one flat all-reduce (``FlatGrads``), scaled by 1 / (batches of the round).  The embedding
+    tables (``optim.LazyRowAdam(duplicates="sum")``, i.e. ``mag_optimizer(model, lr, duplicates="sum")``) never form a dense gradient:
+    the ranks exchange their batch sizes, then all-gather in rank order the deposit of their batch -- gradient rows [n_r, D] and
+    (node_type, local_idx) [n_r, 2] -- and every rank applies the same concatenated list with the same scale in one summing row step
+    per table (a table row named by several ranks is stepped once with the sum).  A rank without a batch contributes zero rows and zero
+    dense gradients and still steps.  A dense optimiser is accepted too and gets plain all-reduced table gradients (the comparison
+    form).  ``seed``: ``torch.manual_seed(seed + b)`` before the forward of global batch ``b``.  Eager launches only.
+
+    The projection heads' BatchNorm (``fitnet`` / ``nce``) normalises every batch with its own statistics, exactly as ``accumulate``
+    does; the heads' running-statistics buffers are NOT synchronised across ranks (they feed no training computation).
+
+    One difference from ``mag_accumulate_epoch``: a dense parameter that no batch of a round reaches (a relation absent from every
+    batch) has ``.grad = None`` there and is skipped by the optimiser, while here it receives the all-reduced ZERO gradient and takes
+    a zero-gradient Adam step (``m`` and ``v`` decay, ``p`` moves while ``m != 0``), as under ``DistributedDataParallel``: whether a
+    parameter was reached is not known across ranks without another collective.
+
+    Returns the epoch means of (loss, loss_cls, loss_aux) weighted by train rows, all-reduced once at the end.  ``LAST_DP_STATS``
+    then holds per round the rows each rank contributed and the table-gradient payload sum(n_r) * (4 D + 16) bytes."""
+    from .models import MAG_MODES, mag_batch_loss, train_mode
+    from .optim import LazyRowAdam
+    if mode not in MAG_MODES:
+        raise NotImplementedError(mode)
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    lazy = isinstance(optimizer, LazyRowAdam)
+    if lazy and optimizer.duplicates != "sum":
+        raise ValueError("mag_dp_train_epoch: the union of the ranks' batches names table rows several times; build the optimiser with "
+                         "mag_optimizer(model, lr, duplicates='sum')")
+    total = getattr(loader, "global_steps", None)
+    if total is None or getattr(loader, "world", world) != world or getattr(loader, "rank", rank) != rank:
+        raise ValueError(f"mag_dp_train_epoch: the loader must be rank {rank} of {world}'s slice of one batch stream "
+                         "(GraphSAINTRandomWalkSampler(..., rank=, world=))")
+    train_mode(model, student_proj, teacher_proj, teacher_model)
+    dev = next(model.parameters()).device
+    rows = optimizer._rows if lazy else {}
+    dense = [p for g in optimizer.param_groups for p in g["params"] if p.requires_grad and p not in rows]
+    fg = getattr(optimizer, "_egnn_dp_flat_grads", None)
+    if fg is None or len(fg.params) != len(dense) or any(a is not b for a, b in zip(fg.params, dense)):
+        fg = optimizer._egnn_dp_flat_grads = FlatGrads(dense)
+    tables = [(int(k), rows[emb]) for k, emb in model.emb_dict.items() if emb in rows]
+    D = model.in_channels
+    tot = torch.zeros(4, dtype=torch.float64, device=dev)
+    stats = dict(world=world, D=D, rows=[], payload_bytes=[])
+    it = iter(loader)
+    for first in range(0, total, world):
+        in_round = min(world, total - first)
+        b = first + rank
+        scale = 1.0 / in_round
+        optimizer.zero_grad()
+        fg.zero()
+        if b < total:
+            batch = next(it).to(dev)
+            if seed is not None:
+                torch.manual_seed(seed + b)
+            loss, loss_cls, loss_aux = mag_batch_loss(model, batch, x_dict, mode, hp, teacher_model, student_proj, teacher_proj)
+            loss.backward()
+            n = batch.train_mask.sum().to(torch.float64)
+            tot += torch.stack([loss.detach().double() * n, loss_cls.detach().double() * n, loss_aux.detach().double() * n, n])
+        fg.all_reduce(group)
+        if in_round > 1:
+            fg.flat.mul_(scale)
+        if not lazy:
+            optimizer.step()
+            continue
+        g, idx = _dp_local_rows(tables, D, dev)
+        sizes = torch.empty(world, dtype=torch.int64, device=dev)
+        dist.all_gather_into_tensor(sizes, torch.tensor([g.shape[0]], dtype=torch.int64, device=dev), group=group)
+        counts = sizes.tolist()
+        G = _all_gather_rows(g, counts, group)
+        IDX = _all_gather_rows(idx, counts, group)
+        node_type, local_idx = IDX[:, 0].contiguous(), IDX[:, 1].contiguous()
+        for k, st in tables:
+            st.deposits = [(G, node_type, local_idx, k)]
+        optimizer.step(grad_scale=scale)
+        stats["rows"].append(counts)
+        stats["payload_bytes"].append(sum(counts) * (4 * D + 16))
+    dist.all_reduce(tot, group=group)
+    flush = getattr(optimizer, "flush", None)
+    if flush is not None:
+        flush()
+    LAST_DP_STATS.clear()
+    LAST_DP_STATS.update(stats)
+    vals = tot.tolist()
+    return tuple(v / max(1.0, vals[3]) for v in vals[:3])
 
 
 # ------------------------------------------------------------------------------------------------

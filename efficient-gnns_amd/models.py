@@ -913,6 +913,67 @@ def mag_batch_loss(model, batch, x_dict, mode, hp, teacher_model=None, student_p
     return C.distill(mode, out, labels, feat, teacher_feat, hp, teacher_logits=teacher_out, rows=rows, edge_index=edge_index)
 
 
+def mag_accumulate_epoch(model, loader, x_dict, optimizer, mode, hp, teacher_model=None, student_proj=None, teacher_proj=None, accumulate=1,
+                         seed=None):
+    """``mag_train_epoch`` with ``accumulate`` consecutive batches per optimisation step, whose gradient is the MEAN of the batch-loss
+    gradients (dense ones summed in ``.grad``, table rows as deposits of ``LazyRowAdam(duplicates="sum")``, both scaled by
+    1 / (batches of the step); the last step of the epoch averages over the batches it has).  Needs an optimiser that takes several
+    deposits per table: ``mag_optimizer(model, lr, duplicates="sum")`` or any dense optimiser; ``LazyRowAdam`` in its default mode
+    raises before the first batch.  ``seed``: ``torch.manual_seed(seed + b)`` runs before the forward of batch number ``b`` of the
+    epoch, so the dropout masks depend on the batch and not on how the batches are grouped.  ``accumulate=1, seed=None`` IS
+    ``mag_train_epoch``.  Returns the epoch means weighted by train rows, like ``mag_train_epoch``."""
+    from .optim import LazyRowAdam
+    if mode not in MAG_MODES:
+        raise NotImplementedError(mode)
+    if int(accumulate) != accumulate or accumulate < 1:
+        raise ValueError("mag_accumulate_epoch: accumulate must be a positive integer")
+    if accumulate == 1 and seed is None:
+        return mag_train_epoch(model, loader, x_dict, optimizer, mode, hp, teacher_model, student_proj, teacher_proj)
+    train_mode(model, student_proj, teacher_proj, teacher_model)
+    lazy_sum = isinstance(optimizer, LazyRowAdam) and optimizer.duplicates == "sum"
+    if accumulate > 1 and isinstance(optimizer, LazyRowAdam) and not lazy_sum:
+        raise ValueError("mag_accumulate_epoch: accumulate > 1 deposits several gradient lists per table and step; build the optimiser with "
+                         "mag_optimizer(model, lr, duplicates='sum')")
+    tot, examples = [0.0, 0.0, 0.0], 0
+    dev = next(model.parameters()).device
+
+    def step(k):
+        scale = 1.0 / k
+        if k > 1:
+            grads = [p.grad for group in optimizer.param_groups for p in group["params"] if p.grad is not None]
+            if grads:
+                torch._foreach_mul_(grads, scale)           # one call for all dense gradients
+        if lazy_sum:
+            optimizer.step(grad_scale=scale)
+        else:
+            optimizer.step()
+
+    pending = 0
+    for b, batch in enumerate(loader):
+        batch = batch.to(dev)
+        if pending == 0:
+            optimizer.zero_grad()
+        if seed is not None:
+            torch.manual_seed(seed + b)
+        loss, loss_cls, loss_aux = mag_batch_loss(model, batch, x_dict, mode, hp, teacher_model, student_proj, teacher_proj)
+        loss.backward()
+        pending += 1
+        if pending == accumulate:
+            step(pending)
+            pending = 0
+        vals = torch.stack([loss.detach(), loss_cls.detach(), loss_aux.detach(), batch.train_mask.sum().to(loss.dtype)]).tolist()
+        n = int(vals[3])
+        for i in range(3):
+            tot[i] += vals[i] * n
+        examples += n
+    if pending:
+        step(pending)                   # the last step of the epoch averages over the batches it has
+    flush = getattr(optimizer, "flush", None)
+    if flush is not None:
+        flush()
+    return tuple(v / max(1, examples) for v in tot)
+
+
 def mag_train_epoch(model, loader, x_dict, optimizer, mode, hp, teacher_model=None, student_proj=None, teacher_proj=None):
     """One MAG epoch (/root/reference/mag_pyg/gnn.py:174-268): one optimisation step per GraphSAINT batch of ``loader``
     (``saint.GraphSAINTRandomWalkSampler`` or any iterable of batches); returns the epoch means of (loss, loss_cls, loss_aux) weighted
@@ -939,13 +1000,14 @@ def mag_train_epoch(model, loader, x_dict, optimizer, mode, hp, teacher_model=No
     return tuple(v / max(1, examples) for v in tot)
 
 
-def mag_optimizer(model, lr):
+def mag_optimizer(model, lr, duplicates="refuse"):
     """The reference's ``torch.optim.Adam(model.parameters(), lr=lr)`` (mag_pyg/gnn.py:424) with the embedding tables stepped row-lazily
     (``optim.LazyRowAdam``): same parameters, but a step moves the ~55 k rows of the batch instead of all 1.2 M, and no dense table
     gradient is formed.  Between flushes ``emb.data`` holds rows that are behind; ``RGCN.forward`` / ``inference`` / ``mag_train_epoch``
-    catch up or flush what they read."""
+    catch up or flush what they read.  ``duplicates="sum"``: a step takes the rows of several batches (``mag_accumulate_epoch``,
+    ``dist.mag_dp_train_epoch``) and sums the gradient rows of a table row named more than once."""
     from .optim import LazyRowAdam
-    return LazyRowAdam(model.parameters(), lr=lr, lazy=list(model.emb_dict.values()))
+    return LazyRowAdam(model.parameters(), lr=lr, lazy=list(model.emb_dict.values()), duplicates=duplicates)
 
 
 @torch.no_grad()

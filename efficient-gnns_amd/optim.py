@@ -15,6 +15,10 @@ Semantics worth knowing:
     further behind than the ring reaches, so every 64th step flushes first (one pass over the rows that ever had a gradient);
   * unique rows: a batch must name a table row at most once (GraphSAINT batches do).  A duplicate is not a fault: one of the two
     gradient rows is applied, the other is counted on the device, and the next ``flush()`` raises ``RuntimeError`` naming the table;
+  * ``duplicates="sum"`` lifts both restrictions: a step takes any number of deposits per table (several ``backward()`` calls, or the
+    gathered batches of several ranks), a table row may be named any number of times, and its gradient is ``grad_scale`` times the sum
+    of its gradient rows in the order they were deposited -- one Adam step per row, no float atomics, no dense gradient
+    (egnn_adam_rows_step_sum_f32).  The default ``"refuse"`` is the unique-rows path above, unchanged;
   * lifetime: the row state hangs on the Parameter (``param._egnn_rows``) and belongs to ONE optimiser.  ``LazyRowAdam.close()`` flushes
     and detaches it; do that before the tables are handed to another optimiser, re-initialised (``reset_parameters``) or moved
     (``model.to``).  A state whose optimiser is gone is flushed and dropped by the next reader (``row_state``), and a new ``LazyRowAdam``
@@ -111,14 +115,55 @@ class RowState:
         """Called by the backward of ``ops.group_input``: the gradient rows of this step, applied by ``LazyRowAdam.step``."""
         self.deposits.append((grad_h, node_type, local_idx, int(type_id)))
 
-    def advance(self) -> None:
+    def _merged_deposits(self, cache: dict):
+        """The deposits of this step as ONE list ``(g, node_type, local_idx, type_id)``, concatenated in the order they were made.
+        ``cache`` is shared by the tables of one optimiser step: they usually hold the same tensors (one ``ops.group_input`` backward
+        deposits its arrays with every table), which are then concatenated once."""
+        deps, self.deposits = self.deposits, []
+        if len(deps) == 1:
+            return deps[0]
+        ids = {d[3] for d in deps}
+        if len(ids) == 1 and all(d[1] is not None for d in deps):
+            key = tuple(id(x) for d in deps for x in d[:3])
+            if key not in cache:
+                cache[key] = (deps, torch.cat([d[0] for d in deps]), torch.cat([d[1] for d in deps]), torch.cat([d[2] for d in deps]))
+            _, g, node_type, local_idx = cache[key]
+            return g, node_type, local_idx, deps[0][3]
+        # deposits under different type ids, or without a type vector: select with a 0 / 1 vector instead
+        sel = [torch.ones_like(d[2]) if d[1] is None else (d[1] == d[3]).to(torch.int64) for d in deps]
+        return torch.cat([d[0] for d in deps]), torch.cat(sel), torch.cat([d[2] for d in deps]), 1
+
+    def _advance_sum(self, grad_scale: float, cache: dict) -> None:
+        """The deposit part of ``advance`` under ``duplicates="sum"``: the named rows are brought to step ``t - 1`` (rows of another
+        rank's batch were not read here; the catch-up serves a row named twice once), then one summing step over the whole list."""
+        g, node_type, local_idx, type_id = self._merged_deposits(cache)
+        n = local_idx.numel()
+        if n == 0:
+            return
+        g = g if g.stride(1) == 1 and g.stride(0) % 4 == 0 and g.data_ptr() % 16 == 0 else g.contiguous().clone()
+        lib = _lib.load()
+        with torch.cuda.device(self.param.device):
+            if self.t - 1 > self.flushed:
+                _lib.check(lib.egnn_adam_rows_catchup_f32(ctypes.byref(self._desc(self.t - 1)), type_id, _lib.ptr(node_type),
+                                                          _lib.ptr(local_idx), n, _lib.stream()), "egnn_adam_rows_catchup_f32")
+            ws_bytes = lib.egnn_adam_rows_step_sum_ws_bytes(n, self.param.shape[0])
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.param.device)
+            _lib.check(lib.egnn_adam_rows_step_sum_f32(ctypes.byref(self._desc(self.t)), type_id, _lib.ptr(node_type),
+                                                       _lib.ptr(local_idx), n, _lib.ptr(g), g.stride(0), float(grad_scale),
+                                                       _lib.ptr(ws), ws_bytes, _lib.stream()), "egnn_adam_rows_step_sum_f32")
+
+    def advance(self, sum_duplicates: bool = False, grad_scale: float = 1.0, cache: "dict | None" = None) -> None:
         """One optimiser step: t += 1, this step's ring entries from the group's current lr, the forced flush, then the deposit
-        (``LazyRowAdam.step`` has checked that there is at most one)."""
+        (``LazyRowAdam.step`` has checked that there is at most one) or, with ``sum_duplicates``, all of them in one summing step."""
         self.t += 1
         self.ring.beta1, self.ring.beta2 = (float(b) for b in self.group["betas"])
         self.ring.fill(self.t, self.group["lr"])
         if self.t - self.flushed >= MAX_LAG:
             self._flush_to(self.t - 1)
+        if sum_duplicates:
+            if self.deposits:
+                self._advance_sum(grad_scale, {} if cache is None else cache)
+            return
         if self.deposits:
             g, node_type, local_idx, type_id = self.deposits.pop()
             g = g if g.stride(1) == 1 and g.stride(0) % 4 == 0 and g.data_ptr() % 16 == 0 else g.contiguous().clone()
@@ -154,10 +199,19 @@ class LazyRowAdam(torch.optim.Optimizer):
     parameter is stepped by an inner ``torch.optim.Adam(..., fused=True)`` with the same options, so with ``lazy=()`` this is that
     optimiser.  ``params`` as for torch.optim.Adam (an iterable or groups).  ``weight_decay = 0`` only, no ``amsgrad`` / ``maximize`` /
     ``capturable`` (NotImplementedError).  ``state_dict()`` flushes first; it and ``load_state_dict()`` use torch Adam's layout (``step``,
-    ``exp_avg``, ``exp_avg_sq`` per parameter in ``params`` order): a dense torch.optim.Adam loads it and the other way round."""
+    ``exp_avg``, ``exp_avg_sq`` per parameter in ``params`` order): a dense torch.optim.Adam loads it and the other way round.
+
+    ``duplicates="refuse"`` (default): one deposit per table and step, unique rows.  ``duplicates="sum"``: any number of deposits, rows
+    named any number of times; a row's gradient is ``grad_scale`` (attribute, or ``step(grad_scale=...)`` for one step; default 1.0)
+    times the sum of its gradient rows.  ``grad_scale`` applies to the lazy tables only: the dense gradients of several ``backward()``
+    calls accumulate in ``.grad`` as under any optimiser, and scaling them is the caller's job."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, lazy=(), weight_decay=0, amsgrad=False, maximize=False,
-                 capturable=False):
+                 capturable=False, duplicates="refuse"):
+        if duplicates not in ("refuse", "sum"):
+            raise ValueError(f"LazyRowAdam: duplicates must be 'refuse' or 'sum', got {duplicates!r}")
+        self.duplicates = duplicates
+        self.grad_scale = 1.0
         for name, val in (("weight_decay", weight_decay), ("amsgrad", amsgrad), ("maximize", maximize), ("capturable", capturable)):
             if val:
                 raise NotImplementedError(f"LazyRowAdam: {name} is not supported")
@@ -216,11 +270,21 @@ class LazyRowAdam(torch.optim.Optimizer):
             ig["lr"], ig["betas"], ig["eps"] = g["lr"], g["betas"], g["eps"]
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, grad_scale=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self.duplicates == "sum":
+            scale, cache = float(self.grad_scale if grad_scale is None else grad_scale), {}
+            for st in self._rows.values():
+                st.advance(True, scale, cache)
+            if self._inner is not None:
+                self._sync_inner()
+                self._inner.step()
+            return loss
+        if grad_scale is not None:
+            raise ValueError("LazyRowAdam: grad_scale needs duplicates='sum'")
         many = [st for st in self._rows.values() if len(st.deposits) > 1]
         if many:                                     # checked for ALL tables before any of them advances: a refused step changes nothing
             msg = ", ".join(f"{st.name}: {len(st.deposits)}" for st in many)

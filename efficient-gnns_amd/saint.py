@@ -75,10 +75,17 @@ class GraphSAINTRandomWalkSampler:
     further keywords of PyG's loader are accepted and ignored; ``sample_coverage > 0`` (the normalisation statistics) is not offered.
     ``seed``: the sampler's own draws are a counter hash of (seed, batch number, walk, step) -- two samplers with the same seed
     yield the same batches.  ``sample(start, rand)`` forms one batch from injected draws instead (test harnesses).
-    ``num_edge_types`` / ``num_node_types``: sizes of ``relations`` (default: largest id + 1)."""
+    ``num_edge_types`` / ``num_node_types``: sizes of ``relations`` (default: largest id + 1).
+    ``rank`` / ``world``: iterating yields the batches ``rank, rank + world, ...`` of the SAME stream of ``num_steps`` batches that
+    ``world=1`` yields (no walk runs for another rank's batch; ``iter()`` takes the epoch's ``num_steps`` stream positions at once, so
+    every rank's next epoch starts at the same position whether or not the iterator was run to its end); ``len()`` is this rank's
+    share and ``global_steps`` the length of the whole stream."""
 
     def __init__(self, data, batch_size, walk_length, num_steps=1, sample_coverage=0, save_dir=None, log=True, seed=0,
-                 device=None, num_edge_types=None, num_node_types=None, **kwargs):
+                 device=None, num_edge_types=None, num_node_types=None, rank=0, world=1, **kwargs):
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError("the sampler needs world >= 1 and 0 <= rank < world")
+        self.rank, self.world = int(rank), int(world)
         if sample_coverage > 0:
             raise NotImplementedError("sample_coverage > 0 (GraphSAINT normalisation) is not offered; the reference passes 0")
         if walk_length < 1 or batch_size < 1:
@@ -96,6 +103,8 @@ class GraphSAINTRandomWalkSampler:
         self.batch_size, self.walk_length, self.num_steps = int(batch_size), int(walk_length), int(num_steps)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self._key_dev = torch.zeros(1, dtype=torch.int64, device=dev)    # batch number << 32, kept on the device
+        self._key_pos = 0          # the batch number ``_key_dev`` holds (host mirror: no device read)
+        self._pos = 0              # stream position of the next batch ``sample()`` draws
         # parent 1: SparseTensor(row, col, value=arange(E)) -- sorted by (row, col), stable, value = original edge id
         row, col = ei[0], ei[1]
         perm = torch.argsort(row * N + col, stable=True)
@@ -136,12 +145,27 @@ class GraphSAINTRandomWalkSampler:
         self._flag = torch.zeros(N, dtype=torch.uint8, device=dev)
         self._ws = {}
 
-    def __len__(self):
+    @property
+    def global_steps(self) -> int:
         return self.num_steps
 
+    def __len__(self):
+        return (self.num_steps - self.rank + self.world - 1) // self.world
+
     def __iter__(self):
-        for _ in range(self.num_steps):
-            yield self.sample()
+        if self.world == 1:
+            return (self.sample() for _ in range(self.num_steps))
+        # a rank's slice: the epoch's ``num_steps`` stream positions are taken HERE, when the iterator is made, and every own batch is
+        # drawn at its absolute position -- so the next epoch starts at the same position on every rank however far (or with how many
+        # ``next()`` calls) this iterator is consumed; another rank's batch costs nothing (the draws are a hash of the batch number)
+        base = self._pos
+        self._pos = base + self.num_steps
+        return (self.sample(_at=base + b) for b in range(self.rank, self.num_steps, self.world))
+
+    def _seek(self, pos: int) -> None:
+        if pos != self._key_pos:
+            self._key_dev.fill_(pos * _BATCH_KEY_STEP)
+            self._key_pos = pos
 
     def _workspace(self, items):
         ws = self._ws.get(items)
@@ -149,8 +173,9 @@ class GraphSAINTRandomWalkSampler:
             ws = self._ws[items] = torch.empty(_lib.load().egnn_saint_scan_ws_bytes(items), dtype=torch.uint8, device=self.device)
         return ws
 
-    def sample(self, start: Tensor | None = None, rand: Tensor | None = None) -> SaintBatch:
-        """One batch.  ``start`` [B] int64 and ``rand`` [B, walk_length] fp32 in [0, 1): the walks' draws (both or neither)."""
+    def sample(self, start: Tensor | None = None, rand: Tensor | None = None, _at: int | None = None) -> SaintBatch:
+        """One batch.  ``start`` [B] int64 and ``rand`` [B, walk_length] fp32 in [0, 1): the walks' draws (both or neither).  (``_at``:
+        the stream position to draw at instead of the next one; the rank-sliced iterator's.)"""
         _lib.require_gpu(self._rowptr)
         if (start is None) != (rand is None):
             raise ValueError("pass both start and rand, or neither")
@@ -161,6 +186,8 @@ class GraphSAINTRandomWalkSampler:
             B = start.numel()
             if B < 1 or tuple(rand.shape) != (B, L) or int(start.min()) < 0 or int(start.max()) >= N:
                 raise ValueError("start must hold B >= 1 node ids and rand must be [B, walk_length]")
+        if start is None:
+            self._seek(self._pos if _at is None else _at)
         cap = min(N, B * (L + 1))                                 # n_sub can never exceed it: sizes everything before the host knows n_sub
         flag = self._flag.zero_()
         walks = torch.empty((B, L + 1), dtype=torch.int64, device=dev)
@@ -169,6 +196,9 @@ class GraphSAINTRandomWalkSampler:
                    "egnn_saint_random_walk_i64")
         if start is None:
             self._key_dev += _BATCH_KEY_STEP
+            self._key_pos += 1
+            if _at is None:
+                self._pos += 1
         relabel = torch.empty(N + 1, dtype=torch.int64, device=dev)
         node_buf = torch.empty(cap, dtype=torch.int64, device=dev)
         ws_n = self._workspace(N)

@@ -837,6 +837,23 @@ int egnn_adam_rows_catchup_f32(const egnn_adam_rows_t* a, int type_id, const int
 int egnn_adam_rows_flush_f32(const egnn_adam_rows_t* a, void* stream);
 int egnn_adam_rows_step_f32(const egnn_adam_rows_t* a, int type_id, const int64_t* node_type, const int64_t* local_idx, int64_t n,
                             const float* g, int64_t ldg, void* stream);
+/* egnn_adam_rows_step_sum_f32  the step over a list that may name a table row SEVERAL times (the batches of one accumulated step, or
+ *     of several data-parallel ranks).  Entry i is selected when node_type[i] == type_id (every entry when node_type == NULL); a
+ *     selected entry with local_idx[i] outside [0, n_rows) is not applied and adds 1 to *dup_count.  For a table row r named by the
+ *     selected entries i1 < i2 < ... < ik the gradient is  G_r = scale * (((g[i1] + g[i2]) + ...) + g[ik])  -- plain fp32 adds in
+ *     ascending entry order, one multiply -- and r takes exactly ONE step `step` with G_r, claimed like egnn_adam_rows_step_f32 (a row
+ *     that is not current for step - 1 is not stepped and adds 1 to *dup_count).  With no row named twice and scale == 1.0f the
+ *     result equals egnn_adam_rows_step_f32's bit for bit.  The entries get 64-bit keys (row, entry), radix-sorted over the bits they
+ *     use; the lane group at the head of a row's run adds the run in registers.  No float atomics, no dense gradient: the result
+ *     does not depend on the launch geometry.  n and n_rows < 2^31 - 1.  ws: egnn_adam_rows_step_sum_ws_bytes(n, n_rows) bytes,
+ *     16-byte aligned (two key arrays of 8 n bytes and the sort's temporary storage: O(n), independent of n_rows x D); else
+ *     EGNN_EWORKSPACE.  Checks as egnn_adam_rows_step_f32, all before any launch; n == 0 enqueues nothing (ws may be NULL).
+ *     The sort's temporary size is asked of hipCUB, which reads the current device's configuration: in a process without a
+ *     device egnn_adam_rows_step_sum_ws_bytes counts the two key arrays only, and the step returns EGNN_ELAUNCH (before any
+ *     launch) if that query fails.  Size the workspace in the process, and on the device, that runs the step. */
+size_t egnn_adam_rows_step_sum_ws_bytes(int64_t n, int64_t n_rows);
+int egnn_adam_rows_step_sum_f32(const egnn_adam_rows_t* a, int type_id, const int64_t* node_type, const int64_t* local_idx, int64_t n,
+                                const float* g, int64_t ldg, float scale, void* ws, size_t ws_bytes, void* stream);
 
 /* DIAGNOSTIC (measurement only; bench.py's roofline.gather_ceiling_GBs): replays the gather stream of one aggregation call and
  * nothing else -- for every stored entry e, the 128-byte slice s of row col[e] of X [n_src, K] is read by an 8-lane sub-group,
