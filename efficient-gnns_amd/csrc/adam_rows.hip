@@ -18,23 +18,24 @@
 // the bits they use, and the lane group at the first key of a row's run walks the run forward: the row's gradient rows are added in
 // registers in ascending entry order, scaled once, and the row takes ONE step through the same device functions.  Only the head's
 // group touches the row, so runs that cross a workgroup boundary need no hand-over.
-#include <hipcub/hipcub.hpp>
-
-#include "common.h"
+#include "rows_keys.h"
 
 namespace {
+
+using egnn_rows::NO_KEY;               // an entry of another type or outside the table: sorts behind every row
+using egnn_rows::align_up;
+using egnn_rows::bits_for;
+using egnn_rows::kAlign;
+using egnn_rows::make_key;
+using egnn_rows::sort_keys;
+using egnn_rows::sort_keys_temp;
 
 constexpr int THREADS = 256;
 constexpr int MAX_TABLES = 8;
 constexpr int RING = EGNN_ADAM_MAX_LAG;
 static_assert((RING & (RING - 1)) == 0 && 2 * RING <= THREADS, "the ring is indexed with tau & (RING - 1) and staged by one workgroup pass");
 
-static int lanes_lg(int64_t D) {
-  const int64_t groups = D / 4;
-  int lg = 0;
-  while (lg < 6 && (int64_t(1) << lg) < groups) ++lg;
-  return lg;
-}
+static int lanes_lg(int64_t D) { return egnn_rows::lanes_lg(D / 4); }
 
 static int64_t blocks_for(int64_t n, int lg) {
   const int64_t rows_per_block = THREADS >> lg;
@@ -142,22 +143,6 @@ __global__ __launch_bounds__(THREADS) void adam_rows_step_kernel(egnn_adam_rows_
 }
 
 // ---- the summing step --------------------------------------------------------------------------------------------------------------
-constexpr size_t kAlign = 256;
-constexpr uint64_t NO_KEY = ~uint64_t(0);              // an entry of another type or outside the table: sorts behind every row
-inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
-
-static int bits_for(uint64_t v) {  // number of bits needed to represent values in [0, v]
-  int b = 1;
-  while (b < 64 && (v >> b) != 0) ++b;
-  return b;
-}
-
-// hipCUB sizes the sort's temporary storage from the current device's configuration: false when that query fails (no device)
-static bool sort_keys_temp(int64_t n, int end_bit, size_t* bytes) {
-  *bytes = 0;
-  return hipcub::DeviceRadixSort::SortKeys(nullptr, *bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n, 0, end_bit) == hipSuccess;
-}
-
 // keys[i] = (local_idx[i] << shift) | i for a selected entry inside the table; a selected entry outside it is counted here (keys ==
 // nullptr: an empty table, count only)
 __global__ __launch_bounds__(THREADS) void adam_rows_keys_kernel(int64_t n_rows, int32_t* __restrict__ dup_count, int type_id,
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(THREADS) void adam_rows_keys_kernel(int64_t n_rows,
   uint64_t key = NO_KEY;
   if (!node_type || node_type[i] == (int64_t)type_id) {
     const int64_t r = local_idx[i];
-    if (r >= 0 && r < n_rows) key = ((uint64_t)r << shift) | (uint64_t)i;
+    if (r >= 0 && r < n_rows) key = make_key(r, shift, i);
     else atomicAdd(dup_count, 1);
   }
   if (keys) keys[i] = key;
@@ -349,7 +334,7 @@ extern "C" int egnn_adam_rows_step_sum_f32(const egnn_adam_rows_t* a, int type_i
   size_t tb = ws_bytes - (size_t)(p - (char*)ws);
   hipLaunchKernelGGL(adam_rows_keys_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, a->n_rows, a->dup_count,
                      type_id, node_type, local_idx, n, shift, keys);
-  if (hipcub::DeviceRadixSort::SortKeys(p, tb, keys, sorted, (int)n, 0, end_bit, st) != hipSuccess) return EGNN_ELAUNCH;
+  if (!sort_keys(p, tb, keys, sorted, n, end_bit, st)) return EGNN_ELAUNCH;
   const int lg = lanes_lg(a->D);
   hipLaunchKernelGGL(adam_rows_step_sum_kernel, dim3((unsigned)blocks_for(n, lg)), dim3(THREADS), 0, st, *a, sorted, n, shift, g, ldg, scale,
                      lg);

@@ -162,7 +162,10 @@ def enable() -> None:
     # copy.  A row gather of a LARGE float32 GPU leaf that takes no part in autograd, by a 1-D int64 GPU index, inside a grad-enabled region
     # (the train step) is deferred (lazy.LazyRows): a following Linear runs the gather-fused GEMM on the tensor's once-cut bf16 planes
     # (ops.linear_rows(..., const_input=True): keyed on identity + version, so an in-place change of the tensor re-cuts them); any other
-    # consumer gets the gathered rows.  Everything else indexes as before.
+    # consumer gets the gathered rows.  Everything else indexes as before.  The index is whatever the script wrote: the deferred gather
+    # follows torch's x[idx] rules (repeated ids sum their gradients, negative ids wrap, an id out of range raises IndexError:
+    # ops.rows_plan), and it records the tensor's version: changing the tensor in place before the rows are formed raises, as autograd
+    # does for a saved tensor, instead of handing out the changed rows.
     getitem = torch.Tensor.__getitem__
     _orig["getitem"] = getitem
 

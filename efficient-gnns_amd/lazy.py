@@ -29,7 +29,7 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import _cache, ops
 
 
 def materialise(x, pick=None):
@@ -228,30 +228,57 @@ class LazyFold(_TensorLike):
         return self._egnn_materialise()[idx]
 
 
-class LazyRows(_TensorLike):
-    """``base[idx]`` (unique 1-D int64 ids) not gathered yet: a ``Linear`` consumes it as ``ops.linear_rows(base, idx, W, b)``."""
+_COMPOSED = _cache.TensorKeyedCache(capacity=16)     # (idx, idx2) -> idx[idx2]: one tensor, hence one ops.rows_plan, per pair and not per step
 
-    def __init__(self, base, idx, const_base=False):
+
+class LazyRows(_TensorLike):
+    """``base[idx]`` (1-D int64 ids of unknown provenance: they may repeat rows, be negative or out of range) not gathered yet: a ``Linear``
+    consumes it as ``ops.linear_rows(base, idx, W, b)``.  Every gather passes ``duplicates="sum"``: torch's ``x[idx]`` rules (ops.rows_plan;
+    unique ids take the same kernels as before).  A ``torch.Tensor`` base is read when the rows are formed, not when they were asked for:
+    its version is recorded, and a base changed in place in between raises instead of handing out the changed rows."""
+
+    def __init__(self, base, idx, const_base=False, base_version=None):
         self._base, self._idx, self._value, self._const = base, idx, None, const_base
+        self._base_version = base_version if base_version is not None else (base._version if isinstance(base, torch.Tensor) else None)
 
     shape = property(lambda self: torch.Size((self._idx.numel(),) + tuple(self._base.shape[1:])))
     device = property(lambda self: self._idx.device)
 
+    def _formed_base(self):
+        base = self._base
+        if self._base_version is not None and base._version != self._base_version:
+            raise RuntimeError(f"one of the variables needed for a deferred row gather has been modified by an inplace operation: the indexed "
+                               f"tensor {list(base.shape)} is at version {base._version}; expected version {self._base_version} instead "
+                               f"(x[idx] under accel is formed by its first consumer: clone x before changing it in place)")
+        return materialise(base)
+
     def _egnn_materialise(self, pick=None):
         if self._value is None:
-            base = materialise(self._base)
+            base = self._formed_base()
             if pick is not None:
-                return ops.take_rows(base, self._idx[pick])
-            self._value = ops.take_rows(base, self._idx)
+                return self._take(base, self._composed(pick))
+            self._value = self._take(base, self._idx)
         return self._value if pick is None else self._value[pick]
 
+    @staticmethod
+    def _take(base, idx):
+        # (accel only defers GPU indices; rows of a CPU tensor are torch's own indexing, which has x[idx]'s rules by definition)
+        return ops.take_rows(base, idx, duplicates="sum") if idx.is_cuda else base[idx]
+
     def linear(self, weight, bias):
-        base = materialise(self._base)
+        base = self._formed_base()
         # ``const_base``: the gathered-from tensor is a leaf outside autograd (accel's deferred constant gather): its rows as once-cut planes
         const = bool(self._const and not base.requires_grad and base.grad_fn is None)
-        return ops.linear_rows(base, self._idx, weight, bias, const_input=const)
+        return ops.linear_rows(base, self._idx, weight, bias, const_input=const, duplicates="sum")
+
+    def _composed(self, idx2):
+        """``idx[idx2]``, memoised on the pair: a script composes it anew every step, its plan is built once."""
+        idx = self._idx
+        if not (isinstance(idx2, torch.Tensor) and idx2.dtype == torch.int64 and idx2.dim() == 1):
+            return idx[idx2]
+        return _COMPOSED.get((idx, idx2), (), lambda: idx[idx2])
 
     def __getitem__(self, idx):
         if isinstance(idx, torch.Tensor) and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_cuda and self._value is None:
-            return LazyRows(self._base, self._idx[idx], self._const)
+            return LazyRows(self._base, self._composed(idx), self._const, self._base_version)
         return self._egnn_materialise()[idx]

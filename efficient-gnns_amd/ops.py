@@ -386,25 +386,110 @@ def spmm_max_bwd_rows(t_adj, t_eid: Tensor, val: Tensor | None, argmax: Tensor, 
     return gx
 
 
+# ------------------------------------------------------------------------------------------------
+# row ids that may repeat: the plan of egnn_rows_plan_build_i64 and the run-sum of the gathers' backward (csrc/rows_sum.hip)
+# ------------------------------------------------------------------------------------------------
+class RowsPlan:
+    """What ``duplicates="sum"`` knows about one index tensor: ``idx`` (the wrapped copy when an entry was negative), the counters, and
+    -- only when a row is named more than once -- the sorted (row, position) keys ``egnn_rows_add_runs_f32`` walks."""
+    __slots__ = ("idx", "n_rows", "S", "dups", "negatives", "longest", "keys", "shift")
+
+    def __init__(self, idx, n_rows, S, dups=0, negatives=0, longest=0, keys=None, shift=1):
+        self.idx, self.n_rows, self.S, self.dups, self.negatives, self.longest, self.keys, self.shift = idx, n_rows, S, dups, negatives, longest, keys, shift
+
+
+_ROWS_PLANS = _cache.TensorKeyedCache(capacity=16, max_bytes=1 << 30)
+
+
+def rows_plan(idx: Tensor, n_rows: int) -> RowsPlan:
+    """The plan of ``idx`` (1-D int64, GPU) over a tensor of ``n_rows`` rows, built once per index tensor (identity + version, like the
+    package's other integer preprocessing) with ONE host read, of the four counters.  An id outside [-n_rows, n_rows) raises
+    ``IndexError``; the build cannot happen inside a graph capture (it reads the counters): a warm-up step builds it."""
+    if not (isinstance(idx, Tensor) and idx.dtype == torch.int64 and idx.dim() == 1):
+        raise TypeError("rows_plan: `idx` must be a 1-D int64 tensor")
+    _lib.require_gpu(idx)
+    n_rows = int(n_rows)
+
+    def build():
+        if torch.cuda.graphs.is_current_stream_capturing():
+            raise RuntimeError("rows_plan: the plan of an index tensor (duplicates='sum') is built with a host read of its counters and cannot "
+                               "be built while a graph is being captured: run one warm-up step with this index tensor before the capture")
+        ids, S = idx.contiguous(), idx.numel()
+        if S == 0:
+            return RowsPlan(ids, n_rows, 0)
+        lib = _lib.load()
+        keys = torch.empty(S, dtype=torch.int64, device=idx.device)      # the bits of the uint64 keys
+        counters = torch.empty(4, dtype=torch.int32, device=idx.device)
+        nws = lib.egnn_rows_plan_ws_bytes(S, n_rows)
+        ws = torch.empty(nws, dtype=torch.uint8, device=idx.device)
+        _lib.check(lib.egnn_rows_plan_build_i64(_lib.ptr(ids), S, n_rows, _lib.ptr(keys), _lib.ptr(counters), _lib.ptr(ws), nws, _lib.stream()),
+                   "egnn_rows_plan_build_i64")
+        oob, dups, neg, longest = counters.tolist()                      # the one host read
+        if oob:
+            raise IndexError(f"index out of range: {oob} of {S} row ids are outside [-{n_rows}, {n_rows})")
+        if neg:
+            ids = torch.where(ids < 0, ids + n_rows, ids)
+        return RowsPlan(ids, n_rows, S, dups, neg, longest, keys if dups else None, max(1, (S - 1).bit_length()))
+    return _ROWS_PLANS.get((idx,), (n_rows,), build)
+
+
+def _check_duplicates(duplicates) -> bool:
+    if duplicates not in ("unique", "sum"):
+        raise ValueError(f"duplicates must be 'unique' or 'sum', got {duplicates!r}")
+    return duplicates == "sum"
+
+
+def _rows_add_runs(dst: Tensor, plan: RowsPlan, rows: Tensor, accumulate: bool) -> None:
+    """dst[r] = (dst[r] if accumulate else 0) + the rows of ``rows`` that ``plan`` assigns to r, in the kernel's documented order."""
+    rows = _rowmajor(rows)
+    lib = _lib.load()
+    S, C = rows.shape
+    nws = lib.egnn_rows_add_runs_ws_bytes(S, C)
+    ws = torch.empty(nws, dtype=torch.uint8, device=rows.device) if nws else None
+    _lib.check(lib.egnn_rows_add_runs_f32(_lib.ptr(dst), dst.stride(0), dst.shape[0], _lib.ptr(plan.keys), S, plan.shift, _lib.ptr(rows),
+                                          rows.stride(0), C, 1 if accumulate else 0, _lib.ptr(ws), nws, _lib.stream()), "egnn_rows_add_runs_f32")
+
+
+def _tap_rows_add(g: Tensor, idx, rows: Tensor) -> None:
+    """One pending piece of a ``_TapBox`` joins the dense gradient ``g``: ``idx`` is the id tensor (unique ids) or a ``RowsPlan``."""
+    rows = _rowmajor(rows)
+    if isinstance(idx, RowsPlan):
+        _rows_add_runs(g, idx, rows, True)
+        return
+    _lib.check(_lib.load().egnn_rows_add_f32(_lib.ptr(g), g.stride(0), _lib.ptr(idx), _lib.ptr(rows), rows.stride(0), rows.shape[0],
+                                             rows.shape[1], _lib.stream()), "egnn_rows_add_f32")
+
+
 class _TakeRows(torch.autograd.Function):
-    """x[idx] for UNIQUE row ids: the backward is a plain scatter (ATen's index backward sorts the ids every step)."""
+    """x[idx]: for UNIQUE row ids the backward is a plain scatter (ATen's index backward sorts the ids every step); with the plan of an
+    index that repeats rows (``plan``), the run-sum of csrc/rows_sum.hip into an uninitialised gradient."""
 
     @staticmethod
-    def forward(ctx, x, idx):
+    def forward(ctx, x, idx, plan=None):
         ctx.save_for_backward(idx)
-        ctx.n = x.shape[0]
+        ctx.n, ctx.plan = x.shape[0], plan
         return x.index_select(0, idx)
 
     @staticmethod
     def backward(ctx, g):
         (idx,) = ctx.saved_tensors
+        if ctx.plan is not None:
+            gx = torch.empty(ctx.n, *g.shape[1:], dtype=g.dtype, device=g.device)
+            _rows_add_runs(gx.view(ctx.n, -1), ctx.plan, g.reshape(g.shape[0], -1), False)
+            return gx, None, None
         gx = torch.zeros(ctx.n, *g.shape[1:], dtype=g.dtype, device=g.device)
         gx.index_copy_(0, idx, g)
-        return gx, None
+        return gx, None, None
 
 
-def take_rows(x: Tensor, idx: Tensor) -> Tensor:
-    return _TakeRows.apply(x, idx)
+def take_rows(x: Tensor, idx: Tensor, duplicates: str = "unique") -> Tensor:
+    """``x[idx]`` for a 1-D int64 ``idx``.  ``duplicates="unique"`` (default): the caller knows the ids to be unique and in range;
+    nothing is checked.  ``"sum"``: torch's rules for any ``idx`` -- negative ids wrap, an id out of range raises ``IndexError``, and
+    the gradients of a row named several times are summed (``rows_plan``; with unique ids the same kernels and bits as "unique")."""
+    if not _check_duplicates(duplicates):
+        return _TakeRows.apply(x, idx)
+    plan = rows_plan(idx, x.shape[0])
+    return _TakeRows.apply(x, plan.idx, plan if plan.dups else None)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -690,10 +775,8 @@ class _GradTap(torch.autograd.Function):
             # (add, a view, identity) or a caller-supplied gradient would be corrupted.  Only a tensor one of this package's
             # backward functions has just allocated FOR THIS tapped tensor (``_fresh`` names the box) is added into directly.
             g = g.clone()
-        for idx, rows in pend:   # unique ids: a plain read-modify-write of those rows, deterministic
-            rows = _rowmajor(rows)
-            _lib.check(_lib.load().egnn_rows_add_f32(_lib.ptr(g), g.stride(0), _lib.ptr(idx), _lib.ptr(rows), rows.stride(0), rows.shape[0],
-                                                     rows.shape[1], _lib.stream()), "egnn_rows_add_f32")
+        for idx, rows in pend:   # unique ids: a plain read-modify-write of those rows; a RowsPlan: its run-sum; both deterministic
+            _tap_rows_add(g, idx, rows)
         return g, None
 
 
@@ -825,10 +908,10 @@ class _LinearRows(torch.autograd.Function):
     them with the tap of a ``grad_tap`` tensor)."""
 
     @staticmethod
-    def forward(ctx, x, idx, weight, bias, box, const_input=False):
+    def forward(ctx, x, idx, weight, bias, box, const_input=False, plan=None):
         w = pad_pitch(weight) if not _pitch_ok(weight) else weight   # 0.8 MB at 256 x 750: rows 16-byte aligned
         ctx.save_for_backward(x, idx, w)
-        ctx.has_bias, ctx.box = bias is not None, box
+        ctx.has_bias, ctx.box, ctx.plan = bias is not None, box, plan   # plan: the ids repeat rows (duplicates="sum"), dx is a run-sum
         # a CONSTANT input (the caller says so: the teacher's features, gnn.py:155): its gathered rows as planes, cut once per (x, idx)
         ctx.const_input = bool(const_input) and not x.requires_grad
         y = _fwd_const_rows(x, idx, w, bias) if ctx.const_input else None
@@ -842,7 +925,10 @@ class _LinearRows(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             rows = gemm_raw(gy, w, False, False)
             if ctx.box is not None:
-                ctx.box.pending.append((idx, rows))
+                ctx.box.pending.append((idx if ctx.plan is None else ctx.plan, rows))
+            elif ctx.plan is not None:
+                gx = torch.empty(x.shape, dtype=gy.dtype, device=gy.device)
+                _rows_add_runs(gx, ctx.plan, rows, False)
             else:
                 gx = torch.zeros(x.shape, dtype=gy.dtype, device=gy.device)
                 gx.index_copy_(0, idx, rows)
@@ -852,17 +938,24 @@ class _LinearRows(torch.autograd.Function):
                 gw = gemm_raw(gy, x, True, False, b_rows=idx)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = colsum(gy)
-        return gx, None, gw, gb, None, None
+        return gx, None, gw, gb, None, None, None
 
 
-def linear_rows(x: Tensor, idx: Tensor, weight: Tensor, bias: Tensor | None = None, const_input: bool = False) -> Tensor:
-    """``F.linear(x[idx], weight, bias)`` with the row gather fused into the GEMM (unique ``idx``).
+def linear_rows(x: Tensor, idx: Tensor, weight: Tensor, bias: Tensor | None = None, const_input: bool = False,
+                duplicates: str = "unique") -> Tensor:
+    """``F.linear(x[idx], weight, bias)`` with the row gather fused into the GEMM (unique ``idx``; ``duplicates="sum"``: any ``idx``,
+    by torch's rules, see ``take_rows`` -- the forward and dW read a row as often as it is named, dx becomes a run-sum).
     ``const_input=True`` (opt-in; the teacher projection head): ``x`` does not change between calls -- its gathered rows are re-laid
     ONCE per (x, idx) identity + version as tile-packed bf16 planes (6 bytes per element, held by a byte-bounded cache) and the forward /
     weight-gradient products run on the planes x planes forms.  Without the flag no plane image is ever built: activations under
     ``no_grad`` (requires_grad False as well) or RGCN's per-node-type calls take the gather-fused GEMM."""
+    summing = _check_duplicates(duplicates)
     _lib.require_gpu(x)
-    return _LinearRows.apply(x, idx, weight, bias, getattr(x, "_egnn_tap", None) if torch.is_grad_enabled() else None, const_input)
+    plan = None
+    if summing:
+        plan = rows_plan(idx, x.shape[0])
+        idx, plan = plan.idx, plan if plan.dups else None
+    return _LinearRows.apply(x, idx, weight, bias, getattr(x, "_egnn_tap", None) if torch.is_grad_enabled() else None, const_input, plan)
 
 
 def linear(x: Tensor, weight: Tensor, bias: Tensor | None = None, out: Tensor | None = None) -> Tensor:
@@ -942,9 +1035,10 @@ def ce_and_kd(logits: Tensor, labels: Tensor, teacher_logits: Tensor, T: float, 
 # ------------------------------------------------------------------------------------------------
 class _GatherNormalize(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, idx, eps):
+    def forward(ctx, x, idx, eps, plan=None):
         _lib.require_gpu(x, idx)
         x = _rowmajor(x)
+        ctx.plan = plan
         n = x.shape[0] if idx is None else idx.numel()
         D = x.shape[1]
         out = torch.empty(n, D, dtype=torch.float32, device=x.device)
@@ -963,16 +1057,25 @@ class _GatherNormalize(torch.autograd.Function):
         idx = saved[2] if len(saved) > 2 else None
         gout = _rowmajor(gout)
         n, D = out.shape
+        if ctx.plan is not None:     # ids that repeat rows: the row-compact gradients (idx == NULL form), then their run-sum into dx
+            idx = None
         dx = torch.zeros(ctx.n_in, D, dtype=torch.float32, device=out.device) if idx is not None else torch.empty_like(out)
         rc = _lib.load().egnn_normalize_rows_bwd_f32(_lib.ptr(out), out.stride(0), _lib.ptr(gout), gout.stride(0), _lib.ptr(inv),
                                                      _lib.ptr(idx), n, D, ctx.eps, _lib.ptr(dx), dx.stride(0), 0, _lib.stream())
         _lib.check(rc, "egnn_normalize_rows_bwd_f32")
-        return dx, None, None
+        if ctx.plan is not None:
+            rows, dx = dx, torch.empty(ctx.n_in, D, dtype=torch.float32, device=out.device)
+            _rows_add_runs(dx, ctx.plan, rows, False)
+        return dx, None, None, None
 
 
-def gather_normalize(x: Tensor, idx: Tensor | None = None, eps: float = 1e-12) -> Tensor:
-    """F.normalize(x[idx], p=2, dim=-1) fused (rows of ``idx`` must be unique, as np.random.choice(replace=False) gives)."""
-    return _GatherNormalize.apply(x, idx, eps)
+def gather_normalize(x: Tensor, idx: Tensor | None = None, eps: float = 1e-12, duplicates: str = "unique") -> Tensor:
+    """F.normalize(x[idx], p=2, dim=-1) fused (rows of ``idx`` must be unique, as np.random.choice(replace=False) gives;
+    ``duplicates="sum"``: any ``idx`` by torch's rules, see ``take_rows``)."""
+    if not _check_duplicates(duplicates) or idx is None:
+        return _GatherNormalize.apply(x, idx, eps)
+    plan = rows_plan(idx, x.shape[0])
+    return _GatherNormalize.apply(x, plan.idx, eps, plan if plan.dups else None)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1433,7 +1536,8 @@ def _tail_backward(ctx, g_h, g_xw, x, gamma, beta, mean, var, h, w, eps, relu, p
     if fused and pend:
         idx, rows = pend[0]
         rows = _rowmajor(rows)
-        fused = rows.stride(0) % 4 == 0 and rows.data_ptr() % 16 == 0 and rows.shape[1] == C
+        # (the fused kernel reads the tap rows through an inverse row map, which exists for unique ids only: a RowsPlan takes the separate passes)
+        fused = rows.stride(0) % 4 == 0 and rows.data_ptr() % 16 == 0 and rows.shape[1] == C and not isinstance(idx, RowsPlan)
         if fused:
             inv = _inverse_rows(idx, n)
 
@@ -1471,9 +1575,7 @@ def _tail_backward(ctx, g_h, g_xw, x, gamma, beta, mean, var, h, w, eps, relu, p
             elif g_h is not None:
                 dh = dh + g_h
             for idx, rows in pend:
-                rows = _rowmajor(rows)
-                _lib.check(lib.egnn_rows_add_f32(_lib.ptr(dh), dh.stride(0), _lib.ptr(idx), _lib.ptr(rows), rows.stride(0), rows.shape[0],
-                                                 rows.shape[1], _lib.stream()), "egnn_rows_add_f32")
+                _tap_rows_add(dh, idx, rows)
             nws = lib.egnn_bn_ws_floats(C)
             ws = torch.empty(nws, dtype=torch.float32, device=dev)
             _lib.check(lib.egnn_bn_act_bwd_reduce_f32(bn, _lib.ptr(dh), dh.stride(0), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws), nws,

@@ -618,6 +618,52 @@ int egnn_split_counts_f32(const float* logits, int64_t ld, int64_t n, int64_t C,
 int egnn_rows_add_f32(float* dst, int64_t ld_dst, const int64_t* idx, const float* src, int64_t ld_src, int64_t n, int64_t C,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Row gathers whose ids may REPEAT (csrc/rows_sum.hip): the backward of x[idx] as torch defines it -- every entry's gradient row is
+ * added into its row -- without float atomics, in a fixed order.  A plan is built once per index tensor; the sum runs per step.
+ *
+ * egnn_rows_plan_build_i64   idx int64 [S].  An entry in [-n_rows, 0) is wrapped (+ n_rows), as torch does; an entry outside
+ *     [-n_rows, n_rows) gets no key (the all-ones key, which sorts last) and is counted.  keys_sorted uint64 [S] (8-byte aligned):
+ *     key = (row << shift) | position with shift = number of bits of S - 1 (at least 1), radix-sorted (hipCUB) over the bits in
+ *     use: a row's positions form one run, ascending.  counters int32 [4], written by the call (the caller zeroes nothing):
+ *       [0] entries out of range, [1] keyed entries that are not the head of their run (0: the ids are unique),
+ *       [2] entries that were negative and wrapped, [3] the longest run.
+ *     S and n_rows < 2^31 - 1 (else EGNN_EINVAL).  S == 0 enqueues nothing and writes nothing (all pointers may be NULL).
+ *     ws: egnn_rows_plan_ws_bytes(S, n_rows) bytes, 16-byte aligned (one key array and the sort's temporary storage; sized by
+ *     hipCUB from the current device, see egnn_adam_rows_step_sum_ws_bytes); missing or short: EGNN_EWORKSPACE, misaligned:
+ *     EGNN_EALIGN.  Every check happens before the first launch.
+ *
+ * egnn_rows_add_runs_f32     dst[r, :] = (accumulate ? dst[r, :] : 0) + sum of src[p, :] over the positions p of row r's run,
+ *     r < n_rows; dst [n_rows, ld_dst], src [S, ld_src], C columns, shift as above (anything else: EGNN_EINVAL).  A row that no key
+ *     names keeps its value when accumulate == 1 and is ZEROED when accumulate == 0 (dst may be uninitialised: no memset needed).
+ *     ORDER OF THE ADDITIONS, a function of (idx, C) only -- never of the launch geometry, so two calls are bit-equal: with
+ *     p1 < p2 < ... < pk the positions of row r and K = EGNN_ROWS_SUM_CHUNK, the run is cut from its head into chunks of K
+ *     positions (the last one may be shorter); chunk j gives  P_j = ((src[p_(jK+1)] + src[p_(jK+2)]) + ...)  in ascending
+ *     position, the row gets  T = ((P_0 + P_1) + ...)  in ascending chunk order, and  dst[r] = accumulate ? dst[r] + T : T.
+ *     k <= K: T = P_0.  With unique ids the result therefore equals egnn_rows_add_f32 into the same dst (accumulate == 1) and
+ *     index_copy_ into zeros (accumulate == 0) bit for bit.  No float atomics.
+ *     One lane group per chunk (min(64, pow2ceil(C / 4)) lanes, 16 bytes per lane) when C % 4 == 0, both pitches % 4 == 0 and
+ *     both matrices are 16-byte aligned; a scalar path in the same entry point otherwise (any C, any pitch).  The chunks of a run
+ *     longer than K are summed by different lane groups and meet in ws: egnn_rows_add_runs_ws_bytes(S, C) bytes, 16-byte aligned
+ *     (0 for S <= K: ws may be NULL); missing or short: EGNN_EWORKSPACE, misaligned: EGNN_EALIGN; all checks before any launch.
+ *     S == 0: EGNN_OK; with accumulate == 0 and a non-NULL dst the n_rows rows are zeroed.
+ *     A position or row that does not fit S / n_rows (keys built for other operands) is skipped, never used as an address.
+ *
+ * EGNN_ROWS_SUM_CHUNK = 128.  A lane group is at most one wave and streams a chunk's rows one after the other (four in flight), so
+ * the chunk length is the longest serial chain of row reads in the kernel: 128 KiB per wave at C = 256.  Edge endpoints name a hub
+ * thousands of times (ogbn-arxiv: a maximum degree of about 13 000) next to a median of a few; uncut, that one wave would still be reading when the
+ * other resident waves (up to 256 CUs x 32) have long finished.  At 128 the hub is spread over ~100 waves, every
+ * run of the common degrees stays in one piece, the partial rows are at most 1/64 of the bytes of src, and the serial second pass
+ * adds ~100 rows for the largest hub.  Chosen by this count, not tuned by measurement.
+ * ---------------------------------------------------------------------------------------------- */
+#define EGNN_ROWS_SUM_CHUNK 128
+size_t egnn_rows_plan_ws_bytes(int64_t S, int64_t n_rows);
+int egnn_rows_plan_build_i64(const int64_t* idx, int64_t S, int64_t n_rows, uint64_t* keys_sorted, int32_t* counters, void* ws,
+                             size_t ws_bytes, void* stream);
+size_t egnn_rows_add_runs_ws_bytes(int64_t S, int64_t C);
+int egnn_rows_add_runs_f32(float* dst, int64_t ld_dst, int64_t n_rows, const uint64_t* keys_sorted, int64_t S, int shift,
+                           const float* src, int64_t ld_src, int64_t C, int accumulate, void* ws, size_t ws_bytes, void* stream);
+
 /* FitNet (/root/reference/arxiv_pyg/criterion.py:24-36, ppi_pyg/criterion.py:21-33): loss[0] = mean over n * D of
  * (F.normalize(f) - F.normalize(t))^2, F.normalize(x) = x / max(||x||_2, eps); one wave per row, fixed-order sums.
  * bwd: df / dt (nullable) = g[0] * dloss/df, dloss/dt.  ws: egnn_feature_loss_ws_floats(n) floats. */
