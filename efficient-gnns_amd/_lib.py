@@ -88,6 +88,7 @@ SIGNATURES = {
     "egnn_spmm_csr_max_bwd_f32": (_i32, [_i64, _i64, _p, _i32, _p, _p, _p, _i64, _p, _i64, _p]),
     "egnn_spmm_csr_max_piece_f32": (_i32, [_p, _p, _i32, _p, _p]),
     "egnn_spmm_csr_max_bwd_rows_f32": (_i32, [_i64, _i64, _i64, _p, _p, _i32, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p]),
+    "egnn_sddmm_csr_f32": (_i32, [_i64, _i64, _i64, _p, _p, _i32, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p]),
     "egnn_spmm_algorithmic_bytes": (_i64, [_i64, _i64, _i64, _i64, _i32, _i32]),
     "egnn_csr_from_coo_ws_bytes": (_sz, [_i64, _i64, _i32]),
     "egnn_csr_from_coo_i64": (_i32, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
@@ -98,6 +99,8 @@ SIGNATURES = {
     "egnn_gcn_norm_count_i64": (_i32, [_p, _p, _i64, _p, _p]),
     "egnn_gcn_norm_fill_i64": (_i32, [_p, _p, _i64, _p, _p, _p, _p]),
     "egnn_gcn_norm_values_i64": (_i32, [_p, _p, _i64, _p, _p, _p]),
+    "egnn_gcn_norm_fill_val_i64": (_i32, [_p, _p, _p, _i64, _p, _p, _p, _p, _p]),
+    "egnn_gcn_norm_scale_i64": (_i32, [_p, _p, _i64, _p, _p, _p, _p, _p]),
     "egnn_gemm_ws_floats": (_sz, [_i32, _i32, _i64, _i64, _i64, _i32]),
     "egnn_gemm_f32": (_i32, [_i32, _i32, _i64, _i64, _i64, _f32, _p, _i64, _p, _i64, _p, _p, _i64, _i32, _p, _sz, _p]),
     "egnn_gemm_ex_f32": (_i32, [_i32, _i32, _i64, _i64, _i64, _f32, _p, _i64, _p, _i64, _p, _p, _i64, _i32, _p, _sz, _i32, _p]),

@@ -25,6 +25,13 @@ __device__ __forceinline__ float egnn_wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+// sum over the aligned group of G consecutive lanes (G a power of two <= 64) the calling lane sits in; every lane of the group gets it
+template <int G>
+__device__ __forceinline__ float egnn_group_sum(float v) {
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 __device__ __forceinline__ float egnn_wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));

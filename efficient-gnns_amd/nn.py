@@ -15,7 +15,7 @@ from . import ops
 import os
 
 from . import _lib, ops_edge
-from .sparse import SparseTensor, _ind2ptr, csr_from_coo, gcn_norm
+from .sparse import SparseTensor, _ind2ptr, csr_from_coo, gcn_norm, gcn_norm_weighted_csr
 
 # opt-in: the headline bench keeps the reference's per-step work (aggregate every layer every step)
 _MEMOISE_AX = os.environ.get("EGNN_GCN_MEMOISE_AX", "0") == "1"
@@ -34,7 +34,9 @@ def _adj_from_edge_index(edge_index: Tensor, n: int, value: Tensor | None = None
 def _gcn_norm_edge_index(edge_index: Tensor, n: int) -> SparseTensor:
     """PyG <=1.7 ``gcn_norm`` on an edge_index (ppi_pyg/gnn.py:125-132): add_remaining_self_loops, then
     D^-1/2 A D^-1/2 with in-degrees by target.  Every loop carries weight 1, so the result equals the
-    SparseTensor branch applied to the target-major CSR with duplicates kept."""
+    SparseTensor branch applied to the target-major CSR with duplicates kept (with unit weights only: given an
+    ``edge_weight`` an existing loop keeps its own weight here, ``_gcn_norm_edge_index_weighted``, while the SparseTensor
+    branch replaces it by 1)."""
     src, dst = edge_index[0], edge_index[1]
     keep = src != dst
     loops = torch.arange(n, dtype=torch.int64, device=edge_index.device)
@@ -45,6 +47,22 @@ def _gcn_norm_edge_index(edge_index: Tensor, n: int) -> SparseTensor:
     dinv.masked_fill_(dinv == float("inf"), 0.0)
     val = dinv[src2] * w * dinv[dst2]
     return _adj_from_edge_index(torch.stack([src2, dst2]), n, val)
+
+
+def _gcn_norm_edge_index_weighted(edge_index: Tensor, edge_weight: Tensor, n: int) -> SparseTensor:
+    """PyG <=1.7 ``gcn_norm`` on (edge_index, edge_weight) (edge-index branch): ``add_remaining_self_loops(edge_index, w, 1.0,
+    n)`` -- an existing loop KEEPS its weight, a node without one gets 1.0 -- then deg = scatter_add(w, target) and
+    norm = dinv[src] * w * dinv[dst], on the target-major CSR.  Differentiable in ``edge_weight`` (the loops' own weights included).
+    Several loops on one node are undefined in PyG (the last write wins) and are not checked for here either."""
+    if edge_weight.dim() != 1 or edge_weight.numel() != edge_index.shape[1] or edge_weight.dtype != torch.float32:
+        raise ValueError("GCNConv: edge_weight is a float32 vector with one weight per edge")
+    src, dst = edge_index[0], edge_index[1]
+    keep = src != dst
+    loops = torch.arange(n, dtype=torch.int64, device=edge_index.device)
+    loop_w = torch.ones(n, dtype=torch.float32, device=edge_index.device).index_put((src[~keep],), edge_weight[~keep])
+    src2, dst2 = torch.cat([src[keep], loops]), torch.cat([dst[keep], loops])
+    w2 = torch.cat([edge_weight[keep], loop_w])
+    return gcn_norm_weighted_csr(_adj_from_edge_index(torch.stack([src2, dst2]), n, w2))
 
 
 from ._cache import TensorKeyedCache as _TensorKeyedCache  # noqa: E402  (LRU, pins entries a captured graph reads: _cache.py)
@@ -88,11 +106,20 @@ class GCNConv(nn.Module):
         in the last kernel's store -- the separate normalisation pass disappears from ``test()``.
         ``xw`` (extension): ``x @ self.weight`` when the caller has it already (``ops.bn_act_linear`` forms it together with x); only
         taken on the transform-first order of a plain SparseTensor adjacency."""
+        sharded = hasattr(edge_index, "gcn_normalized")
         if edge_weight is not None:
-            raise NotImplementedError("GCNConv with edge_weight is not used by the reference")
+            if sharded:
+                raise NotImplementedError("GCNConv: edge_weight on a node-range shard (dist.ShardedAdj) is not offered")
+            if isinstance(edge_index, SparseTensor):
+                raise ValueError("GCNConv: a SparseTensor carries its weights as values (adj_t.set_value(w)); edge_weight goes with an edge_index")
+            edge_weight = _lib.real(edge_weight)
+            _lib.require_gpu(x, edge_index, edge_weight)
+        # learnable weights (edge_weight, or the values of a SparseTensor): A^ changes with every step and carries a graph, so nothing
+        # derived from it is kept -- neither by cached=True nor by the edge-index memo nor by the memoised A^ x
+        weights = edge_weight if edge_weight is not None else (edge_index._value if isinstance(edge_index, SparseTensor) else None)
+        learnable = weights is not None and weights.requires_grad
         agg_first = self.in_channels < self.out_channels
         if eval_bn is not None:
-            sharded = hasattr(edge_index, "gcn_normalized")
             if torch.is_grad_enabled() or eval_bn.training or not (isinstance(edge_index, SparseTensor) or sharded) or not x.is_cuda:
                 raise ValueError("eval_bn: inference only (no_grad, BatchNorm in eval mode, SparseTensor / sharded adjacency on the GPU)")
             if sharded:   # node-range shard: the same fold, bias + ReLU in the store of the aggregation's last piece
@@ -100,10 +127,10 @@ class GCNConv(nn.Module):
                 if agg_first:
                     return ops.gemm_raw(edge_index.gcn_normalized().aggregate(x, "sum"), w, False, False, b, relu=True)
                 return edge_index.gcn_normalized().aggregate(ops.gemm_raw(x, w), "sum", bias=b, relu=True)
-            norm = self._cached_adj_t
+            norm = None if learnable else self._cached_adj_t
             if norm is None:
                 norm = gcn_norm(edge_index)
-                if self.cached:
+                if self.cached and not learnable:
                     self._cached_adj_t = norm
             w, b = ops.bn_fold(self.weight, self.bias, eval_bn)
             if agg_first:
@@ -113,19 +140,26 @@ class GCNConv(nn.Module):
             if agg_first:
                 return ops.matmul(edge_index.gcn_normalized().aggregate(x, "sum"), self.weight, self.bias)
             return edge_index.gcn_normalized().aggregate(ops.matmul(x, self.weight) if xw is None else xw, "sum", bias=self.bias)
-        norm = self._cached_adj_t
+        norm = None if learnable else self._cached_adj_t
         if norm is None:
             if isinstance(edge_index, SparseTensor):
                 norm = gcn_norm(edge_index)
+            elif edge_weight is not None:
+                n_nodes = x.shape[0]
+                if learnable:
+                    norm = _gcn_norm_edge_index_weighted(edge_index, edge_weight, n_nodes)
+                else:   # constant weights: memoised like the value-less edge list, keyed on the weight tensor too (identity + version)
+                    norm = _GCN_NORM_CACHE.get((edge_index, edge_weight), (n_nodes,),
+                                               lambda: _gcn_norm_edge_index_weighted(edge_index, edge_weight, n_nodes))
             else:
                 # ``cached=False`` (PPI: one batch graph per step, ppi_pyg/gnn.py:125) re-normalises on every call in PyG.
                 # The result only depends on the integer edge list, so it is memoised on that tensor's identity: the 20
                 # training graphs come back every epoch, in every layer, and building A^ costs a device->host read.
                 n_nodes = x.shape[0]
                 norm = _GCN_NORM_CACHE.get((edge_index,), (n_nodes,), lambda: _gcn_norm_edge_index(edge_index, n_nodes))
-            if self.cached:
+            if self.cached and not learnable:
                 self._cached_adj_t = norm
-        if (self.cached and _MEMOISE_AX and not x.requires_grad and self.in_channels <= self.out_channels
+        if (self.cached and _MEMOISE_AX and not learnable and not x.requires_grad and self.in_channels <= self.out_channels
                 and isinstance(edge_index, SparseTensor)):
             # constant input (the first layer's node features): A^ (x W) == (A^ x) W, and A^ x does not change between
             # steps, so it is kept next to the cached A^ (same lifetime) and the per-step aggregation disappears from

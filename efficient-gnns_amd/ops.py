@@ -203,18 +203,43 @@ def _spmm_raw(adj, x: Tensor, reduce: str = "sum", src_scale: Tensor | None = No
     return y, arg
 
 
+def _spmm_forward(adj, x, reduce, bias, stat_shift, want_stats):
+    """The forward both aggregation Functions share: (Y, argmax | None, (mean, var) | None)."""
+    b = None if bias is None else bias.detach().contiguous()
+    stats = None
+    if want_stats:
+        try:
+            y, arg, stats = spmm_raw(adj, x, reduce, bias=b, stat_shift=stat_shift, want_stats=True)
+        except HipStatsUnavailable:
+            y, arg = spmm_raw(adj, x, reduce, bias=b)
+    else:
+        y, arg = spmm_raw(adj, x, reduce, bias=b)
+    return y, arg, stats
+
+
+def _spmm_dx(adj, reduce, gy, arg):
+    """dX of Y = REDUCE(adj, X): the transposed aggregation with value[perm] (sum / mean), the scatter through argmax (max)."""
+    if reduce in ("sum", "add"):
+        return spmm_raw(adj.t(), gy, "sum")[0]
+    if reduce == "mean":
+        # dX = A^T (dY / cnt): per-source-row scale of the transposed aggregation
+        return spmm_raw(adj.t(), gy, "sum", src_scale=adj._inv_rowcount())[0]
+    n_rows, n_src = adj.sparse_sizes()
+    K = gy.shape[1]
+    gx = torch.zeros(n_src, K, dtype=torch.float32, device=gy.device)
+    if adj.nnz() == 0:   # no stored entry: nothing receives gradient
+        return gx
+    _, col, bits = adj._index_arrays()
+    rc = _lib.load().egnn_spmm_csr_max_bwd_f32(n_rows, K, _lib.ptr(col), bits, _lib.ptr(adj._value), _lib.ptr(arg),
+                                               _lib.ptr(gy), gy.stride(0), _lib.ptr(gx), gx.stride(0), _lib.stream())
+    _lib.check(rc, "egnn_spmm_csr_max_bwd_f32")
+    return gx
+
+
 class _SpMM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, adj, reduce, bias=None, stat_shift=None, want_stats=False):
-        b = None if bias is None else bias.detach().contiguous()
-        stats = None
-        if want_stats:
-            try:
-                y, arg, stats = spmm_raw(adj, x, reduce, bias=b, stat_shift=stat_shift, want_stats=True)
-            except HipStatsUnavailable:
-                y, arg = spmm_raw(adj, x, reduce, bias=b)
-        else:
-            y, arg = spmm_raw(adj, x, reduce, bias=b)
+        y, arg, stats = _spmm_forward(adj, x, reduce, bias, stat_shift, want_stats)
         ctx.adj, ctx.reduce, ctx.has_bias = adj, reduce, bias is not None
         ctx.tap_box = getattr(x, "_egnn_tap", None)     # x is a tapped tensor (grad_tap): its gradient may be completed in place, see _fresh
         if arg is not None:
@@ -228,24 +253,68 @@ class _SpMM(torch.autograd.Function):
     def backward(ctx, gy, _gm=None, _gv=None):
         adj, reduce = ctx.adj, ctx.reduce
         gy = _rowmajor(gy)
-        if reduce in ("sum", "add"):
-            gx, _ = spmm_raw(adj.t(), gy, "sum")
-        elif reduce == "mean":
-            # dX = A^T (dY / cnt): per-source-row scale of the transposed aggregation
-            gx, _ = spmm_raw(adj.t(), gy, "sum", src_scale=adj._inv_rowcount())
-        else:
-            (arg,) = ctx.saved_tensors
-            n_rows, n_src = adj.sparse_sizes()
-            K = gy.shape[1]
-            gx = torch.zeros(n_src, K, dtype=torch.float32, device=gy.device)
-            if adj.nnz() == 0:   # no stored entry: nothing receives gradient
-                return gx, None, None, (colsum(gy) if ctx.has_bias and ctx.needs_input_grad[3] else None), None, None
-            _, col, bits = adj._index_arrays()
-            rc = _lib.load().egnn_spmm_csr_max_bwd_f32(n_rows, K, _lib.ptr(col), bits, _lib.ptr(adj._value), _lib.ptr(arg),
-                                                       _lib.ptr(gy), gy.stride(0), _lib.ptr(gx), gx.stride(0), _lib.stream())
-            _lib.check(rc, "egnn_spmm_csr_max_bwd_f32")
+        gx = _spmm_dx(adj, reduce, gy, ctx.saved_tensors[0] if reduce == "max" else None)
         gb = colsum(gy) if ctx.has_bias and ctx.needs_input_grad[3] else None
         return _fresh(gx, ctx.tap_box), None, None, gb, None, None
+
+
+class _SpMMValued(torch.autograd.Function):
+    """``_SpMM`` with the adjacency's VALUES as a tensor input: the call of a valued adjacency whose values require grad (learnable edge
+    weights, edge gates).  Forward: the same ``spmm_raw`` call on the detached values (Y bit-equal to ``_SpMM``'s for the same numbers).
+    Backward: dX as in ``_SpMM``; dval = ``sddmm`` over the pattern (torch-sparse's ``spmm`` value backward)."""
+
+    @staticmethod
+    def forward(ctx, x, value, adj, reduce, bias=None, stat_shift=None, want_stats=False):
+        adj = adj.set_value(value.detach())      # same structure (and structure caches), values outside the graph
+        y, arg, stats = _spmm_forward(adj, x, reduce, bias, stat_shift, want_stats)
+        ctx.adj, ctx.reduce, ctx.has_bias = adj, reduce, bias is not None
+        ctx.tap_box = getattr(x, "_egnn_tap", None)
+        ctx.save_for_backward(x, arg)
+        if stats is None:
+            return y, None, None
+        ctx.mark_non_differentiable(*stats)
+        return y, stats[0], stats[1]
+
+    @staticmethod
+    def backward(ctx, gy, _gm=None, _gv=None):
+        adj, reduce = ctx.adj, ctx.reduce
+        x, arg = ctx.saved_tensors
+        gy = _rowmajor(gy)
+        gx = _fresh(_spmm_dx(adj, reduce, gy, arg), ctx.tap_box) if ctx.needs_input_grad[0] else None
+        gv = sddmm(adj, gy, x, reduce, arg) if ctx.needs_input_grad[1] else None
+        gb = colsum(gy) if ctx.has_bias and ctx.needs_input_grad[4] else None
+        return gx, gv, None, None, gb, None, None
+
+
+def sddmm(adj, g: Tensor, x: Tensor, reduce: str = "sum", argmax: Tensor | None = None) -> Tensor:
+    """Gradient of ``REDUCE(adj, x)`` with respect to the values of ``adj`` given ``g`` = dY (egnn_sddmm_csr_f32): the [nnz] vector
+    dval[e] = <g[row(e)], x[col[e]]> for ``sum``; times 1 / max(stored entries of the row, 1) for ``mean`` (mean divides by the entry
+    count, not by the sum of the values: SURVEY 9.6); restricted to the columns where ``argmax`` [n_rows, K] picked entry e for ``max``.
+    Only the pattern of ``adj`` is read; every entry is written, no atomics, run-to-run bit-stable."""
+    if reduce not in _REDUCE:
+        raise ValueError(f"unknown reduce '{reduce}'")
+    _lib.require_gpu(g, x, adj._col)
+    g, x = _rowmajor(g), _rowmajor(x)
+    n_rows, n_src = adj.sparse_sizes()
+    K = x.shape[1]
+    if tuple(g.shape) != (n_rows, K) or x.shape[0] != n_src:
+        raise ValueError(f"sddmm: adjacency is {n_rows} x {n_src}, g is {tuple(g.shape)}, x is {tuple(x.shape)}")
+    red = _REDUCE[reduce]
+    if red == 2:
+        if argmax is None or tuple(argmax.shape) != (n_rows, K) or argmax.dtype != torch.int64 or not argmax.is_contiguous():
+            raise ValueError("sddmm(reduce='max') needs the forward's contiguous int64 [n_rows, K] argmax")
+    else:
+        argmax = None
+    nnz = adj.nnz()
+    dval = torch.empty(nnz, dtype=torch.float32, device=x.device)
+    if nnz == 0:
+        return dval
+    rowptr, col, bits = adj._index_arrays()
+    scale = adj._inv_rowcount() if red == 1 else None
+    rc = _lib.load().egnn_sddmm_csr_f32(n_rows, n_src, K, _lib.ptr(rowptr), _lib.ptr(col), bits, nnz, _lib.ptr(g), g.stride(0),
+                                        _lib.ptr(x), x.stride(0), _lib.ptr(scale), _lib.ptr(argmax), _lib.ptr(dval), _lib.stream())
+    _lib.check(rc, "egnn_sddmm_csr_f32")
+    return dval
 
 
 def _fresh(g, tap_box):
@@ -299,6 +368,11 @@ def add_bias(x: Tensor, bias: Tensor | None) -> Tensor:
     return _AddBias.apply(x, bias)
 
 
+def _value_needs_grad(adj) -> bool:
+    v = getattr(adj, "_value", None)
+    return v is not None and v.requires_grad and torch.is_grad_enabled()
+
+
 def spmm(adj, x: Tensor, reduce: str = "sum", bias: Tensor | None = None, bn_stats_shift: Tensor | None = None,
          want_bn_stats: bool = False, addend: Tensor | None = None) -> Tensor:
     """adj @ x with the given reduction; ``bias`` ([K]) is added in the kernel's store (sum / mean only).
@@ -310,12 +384,21 @@ def spmm(adj, x: Tensor, reduce: str = "sum", bias: Tensor | None = None, bn_sta
     if reduce not in _REDUCE:
         raise ValueError(f"unknown reduce '{reduce}'")
     if addend is not None:   # accumulating form (adj @ x + addend), used without autograd by the sharded run's own Functions
-        if torch.is_grad_enabled() and (x.requires_grad or addend.requires_grad):
+        if torch.is_grad_enabled() and (x.requires_grad or addend.requires_grad or _value_needs_grad(adj)):
             raise NotImplementedError("spmm(addend=...) is a forward-only form")
         return spmm_raw(adj, x, reduce, bias=bias, addend=addend)[0]
+    if _value_needs_grad(adj):   # learnable entry values: the Function that takes them as a tensor input and returns their gradient
+        if adj._value.dtype != torch.float32 or adj._value.dim() != 1:
+            raise TypeError("spmm: the values of the adjacency must be a float32 [nnz] vector")
+
+        def apply(*rest):
+            return _SpMMValued.apply(x, adj._value, adj, reduce, *rest)
+    else:
+        def apply(*rest):
+            return _SpMM.apply(x, adj, reduce, *rest)
     if bias is not None and (reduce == "max" or (x.shape[1] % 4 == 0 and bias.data_ptr() % 16 != 0)):
-        return _SpMM.apply(x, adj, reduce, None)[0] + bias
-    y, mean, var = _SpMM.apply(x, adj, reduce, bias, bn_stats_shift, bool(want_bn_stats) and reduce != "max")
+        return apply(None)[0] + bias
+    y, mean, var = apply(bias, bn_stats_shift, bool(want_bn_stats) and reduce != "max")
     if mean is not None:
         y._egnn_bn_stats = (mean, var, y._version)   # version-checked by bn_act: an in-place edit of y voids the statistics
     return y

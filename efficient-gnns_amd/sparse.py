@@ -393,15 +393,94 @@ def csr_from_coo(row: Tensor, col: Tensor, n: int, symmetric: bool):
     return rowptr, col_out
 
 
+def _segment_sum(ptr: Tensor, x: Tensor) -> Tensor:
+    """out[i] = sum of x[ptr[i] : ptr[i + 1]] in a fixed order (egnn_segment_sum_f32: no atomics, run-to-run bit-stable)."""
+    n = ptr.numel() - 1
+    out = torch.empty(n, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().egnn_segment_sum_f32(_lib.ptr(ptr), _lib.ptr(x.contiguous()), n, _lib.ptr(out), _lib.stream()),
+               "egnn_segment_sum_f32")
+    return out
+
+
+def _gcn_scale_raw(struct: SparseTensor, wt: Tensor):
+    """(val, dinv) of the normalisation on a filled structure: deg = row sums of ``wt`` in entry order, dinv = deg^-1/2 (inf -> 0),
+    val[e] = (wt[e] * dinv[row]) * dinv[col]."""
+    n = struct.sparse_size(0)
+    rowptr, col, _ = struct.csr()
+    wt = wt.contiguous()
+    deg = _segment_sum(rowptr, wt)
+    dinv = torch.empty(n, dtype=torch.float32, device=wt.device)
+    val = torch.empty(wt.numel(), dtype=torch.float32, device=wt.device)
+    _lib.check(_lib.load().egnn_gcn_norm_scale_i64(_lib.ptr(rowptr), _lib.ptr(col), n, _lib.ptr(wt), _lib.ptr(deg), _lib.ptr(dinv),
+                                                   _lib.ptr(val), _lib.stream()), "egnn_gcn_norm_scale_i64")
+    return val, dinv
+
+
+class _GcnNormValues(torch.autograd.Function):
+    """val = (w~ * dinv[row]) * dinv[col] on the filled structure ``struct`` as a function of the weights ``w``.  ``wt`` = w~ holds the
+    filled values (``w`` carried to its new slots, 1.0 on the inserted diagonal) and ``slot`` [nnz_in] the new position of every input
+    entry, -1 for a dropped stored diagonal; ``slot`` None: ``w`` is in the structure's entry order already (edge-index branch).
+    Backward, with g = dL/dval:  s_i = sum_{row(e)=i} g w~ dinv[col] + sum_{col(e)=i} g w~ dinv[row],  ddeg = -1/2 dinv^3 s,
+    dw~_e = g_e dinv[row] dinv[col] + ddeg[row(e)] -- the two sums as fixed-order segment sums over the CSR and, through the cached
+    csr2csc permutation, the CSC view: no atomics."""
+
+    @staticmethod
+    def forward(ctx, w, wt, struct, slot):
+        val, dinv = _gcn_scale_raw(struct, wt)
+        ctx.struct, ctx.slot = struct, slot
+        ctx.save_for_backward(wt, dinv)
+        return val
+
+    @staticmethod
+    def backward(ctx, g):
+        wt, dinv = ctx.saved_tensors
+        struct, slot = ctx.struct, ctx.slot
+        rowptr, col, _ = struct.csr()
+        row = struct._row()
+        colptr, perm = struct._transpose_meta()
+        a = g * wt
+        s = _segment_sum(rowptr, a * dinv[col]) + _segment_sum(colptr, (a * dinv[row])[perm])
+        ddeg = -0.5 * dinv * dinv * dinv * s
+        dwt = g * dinv[row] * dinv[col] + ddeg[row]
+        if slot is None:
+            return dwt, None, None, None
+        dw = torch.where(slot >= 0, dwt[slot.clamp(min=0)], torch.zeros((), dtype=dwt.dtype, device=dwt.device))
+        return dw, None, None, None
+
+
+def _gcn_scale(struct: SparseTensor, w: Tensor, wt: Tensor, slot: Tensor | None) -> SparseTensor:
+    """``struct`` with the normalised values; differentiable with respect to ``w`` when it requires grad."""
+    if w.requires_grad and torch.is_grad_enabled():
+        val = _GcnNormValues.apply(w, wt.detach(), struct, slot)
+    else:
+        val = _gcn_scale_raw(struct, wt.detach())[0]
+    out = struct.set_value(val)
+    out._cols_sorted = struct._cols_sorted
+    return out
+
+
+def gcn_norm_weighted_csr(adj_t: SparseTensor) -> SparseTensor:
+    """D^-1/2 W D^-1/2 on a valued CSR that holds its self loops already (PyG <= 1.7 ``gcn_norm``, edge-index branch, after
+    ``add_remaining_self_loops``): deg = row sums of the values, no fill step.  Differentiable in the values."""
+    w = adj_t._value
+    _lib.require_gpu(adj_t._col, w)
+    if w.dtype != torch.float32:
+        raise TypeError(f"gcn_norm: float32 weights, got {w.dtype}")
+    return _gcn_scale(adj_t.set_value(None), w, w, None)
+
+
 def gcn_norm(adj_t: SparseTensor) -> SparseTensor:
-    """A^ = D^-1/2 (A + I) D^-1/2 with ``fill_diag(1)`` (PyG ``gcn_norm``, SparseTensor branch) on the GPU."""
-    if adj_t.has_value():
-        raise NotImplementedError("gcn_norm on a valued adjacency is not used by the reference")
-    rowptr, col, _ = adj_t.csr()
-    _lib.require_gpu(rowptr, col)
+    """A^ = D^-1/2 (A + I) D^-1/2 with ``fill_diag(1)`` (PyG ``gcn_norm``, SparseTensor branch) on the GPU.  On a valued adjacency
+    (SURVEY 9.3): the fill drops any stored diagonal entry whatever its weight and inserts (i, i, 1.0); deg = row sums of the filled
+    values; val = (w * dinv[row]) * dinv[col].  The structure equals the value-less result bit for bit, and the result is
+    differentiable with respect to the values when they require grad."""
+    rowptr, col, w = adj_t.csr()
+    _lib.require_gpu(rowptr, col, w)
     n = adj_t.sparse_size(0)
     if adj_t.sparse_size(1) != n:
         raise ValueError("gcn_norm needs a square adjacency")
+    if w is not None and (w.dtype != torch.float32 or w.dim() != 1):
+        raise TypeError("gcn_norm: the values of the adjacency must be a float32 [nnz] vector")
     if adj_t._cols_sorted is None:
         # caller-provided CSR arrays: the fill kernel places entries by (col < row | col > row) rank and needs ascending
         # columns per row (torch-sparse's own invariant).  One check per structure (one host read), one sort if violated.
@@ -409,8 +488,9 @@ def gcn_norm(adj_t: SparseTensor) -> SparseTensor:
         key = row * n + col
         if key.numel() > 1 and bool((key[1:] < key[:-1]).any()):
             order = torch.argsort(key, stable=True)
-            adj_t = SparseTensor(rowptr=rowptr, col=col[order].contiguous(), sparse_sizes=(n, n))
-            rowptr, col, _ = adj_t.csr()
+            w = None if w is None else w[order]          # the values travel with their columns
+            adj_t = SparseTensor(rowptr=rowptr, col=col[order].contiguous(), value=w, sparse_sizes=(n, n))
+            rowptr, col, w = adj_t.csr()
         adj_t._cols_sorted = True
     lib, st = _lib.load(), _lib.stream()
     dev = col.device
@@ -421,6 +501,14 @@ def gcn_norm(adj_t: SparseTensor) -> SparseTensor:
     nnz_out = adj_t.nnz() + n  # upper bound; exact count below (one host read, once per run)
     nnz_out = int(rowptr_out[-1])
     col_out = torch.empty(nnz_out, dtype=torch.int64, device=dev)
+    if w is not None:
+        wt = torch.empty(nnz_out, dtype=torch.float32, device=dev)
+        slot = torch.empty(adj_t.nnz(), dtype=torch.int64, device=dev) if w.requires_grad and torch.is_grad_enabled() else None
+        _lib.check(lib.egnn_gcn_norm_fill_val_i64(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(w.detach()), n, _lib.ptr(rowptr_out),
+                                                  _lib.ptr(col_out), _lib.ptr(wt), _lib.ptr(slot), st), "egnn_gcn_norm_fill_val_i64")
+        struct = SparseTensor(rowptr=rowptr_out, col=col_out, sparse_sizes=(n, n))
+        struct._cols_sorted = True
+        return _gcn_scale(struct, w, wt, slot)
     dinv = torch.empty(n, dtype=torch.float32, device=dev)
     val = torch.empty(nnz_out, dtype=torch.float32, device=dev)
     _lib.check(lib.egnn_gcn_norm_fill_i64(_lib.ptr(rowptr), _lib.ptr(col), n, _lib.ptr(rowptr_out), _lib.ptr(col_out),

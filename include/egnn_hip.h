@@ -192,6 +192,25 @@ int egnn_spmm_csr_max_bwd_rows_f32(int64_t n_src, int64_t n_rows, int64_t K, con
                                    const int64_t* t_eid, const float* val, const int64_t* argmax, const float* dY, int64_t ldy,
                                    const float* addend, int64_t ld_addend, float* dX, int64_t ldx, void* stream);
 
+/* Gradient of an aggregation with respect to its ENTRY VALUES -- a sampled dense-dense product (SDDMM) over the CSR pattern
+ * (csrc/sddmm.hip; torch-sparse `spmm` value backward):
+ *   dval[e] = row_scale[r] * sum_k m(e,k) * G[r,k] * X[col[e],k],   r = row of entry e,  e in [0, nnz)
+ *   G          [n_rows, ldg]  the incoming dY;  X [n_src, ldx]  the aggregation's dense operand
+ *   rowptr     [n_rows + 1], col [nnz]: index_bits (32 | 64) wide, as in egnn_spmm_t; nnz = rowptr[n_rows], passed by the caller
+ *   row_scale  nullable [n_rows] (= 1.0): EGNN_MEAN passes 1 / max(stored entries of the row, 1) -- mean divides by the entry count,
+ *              not by the sum of the values
+ *   argmax     nullable [n_rows, K] int64 (leading dimension K).  NULL: m = 1 (EGNN_SUM / EGNN_MEAN).  Otherwise m(e,k) =
+ *              (argmax[r,k] == e): the subgradient of EGNN_MAX at the entry the forward picked (the first maximal one in CSR order,
+ *              the tie rule of dX)
+ *   dval       [nnz]: EVERY entry is written exactly once -- no zero-fill by the caller; nnz == 0 launches nothing
+ * Work is cut over entries, not rows: a wavefront owns 256 consecutive entries and finds their rows from rowptr (one wave-uniform binary
+ * search, then a forward walk), so a hub row is no wavefront's serial job.  A group of G lanes owns one entry (G = the power of two at or
+ * above ceil(K / 4), at most 64; float4 lanes, looping when K > 256); K % 4 != 0 or rows that are not 16-byte aligned take scalar lanes.
+ * No atomics, fixed summation order per entry: two calls on the same inputs are bit-equal. */
+int egnn_sddmm_csr_f32(int64_t n_rows, int64_t n_src, int64_t K, const void* rowptr, const void* col, int index_bits, int64_t nnz,
+                       const float* G, int64_t ldg, const float* X, int64_t ldx, const float* row_scale, const int64_t* argmax,
+                       float* dval, void* stream);
+
 /* Algorithmic (compulsory) HBM bytes of one egnn_spmm_csr_f32 call, SURVEY.md 8(d):
  * 4*n_src*K (read X) + 4*n_rows*K (write Y) + nnz*(index bytes + value bytes) + rowptr. */
 int64_t egnn_spmm_algorithmic_bytes(int64_t n_rows, int64_t n_src, int64_t K, int64_t nnz, int index_bits,
@@ -237,6 +256,19 @@ int egnn_gcn_norm_fill_i64(const int64_t* rowptr, const int64_t* col, int64_t n,
                            int64_t* col_out, float* dinv, void* stream);
 int egnn_gcn_norm_values_i64(const int64_t* rowptr_out, const int64_t* col_out, int64_t n, const float* dinv,
                              float* val_out, void* stream);
+
+/* gcn_norm on a VALUED row-sorted CSR (PyG gcn_norm, SparseTensor branch with weights): same structure as above
+ * (step 1 and rowptr_out are shared, col_out comes out bit-equal), then
+ *  fill:  every off-diagonal entry carries its value to its new slot (val_out), the inserted diagonal gets 1.0; a stored diagonal
+ *         entry is dropped whatever its weight.  slot (nullable, [nnz]): new position of input entry e, -1 for a dropped one -- the
+ *         map the backward reads the weight gradients through.
+ *  (the caller forms deg = row sums of the filled values in entry order: egnn_segment_sum_f32 over rowptr_out)
+ *  scale: dinv[i] = deg[i]^-1/2 (inf -> 0), val_out[e] = (w[e] * dinv[row(e)]) * dinv[col_out[e]]; w = the filled values.  Also the
+ *         PyG <= 1.7 edge-index branch with edge_weight, on the target-major CSR of the edges after add_remaining_self_loops. */
+int egnn_gcn_norm_fill_val_i64(const int64_t* rowptr, const int64_t* col, const float* val, int64_t n, const int64_t* rowptr_out,
+                               int64_t* col_out, float* val_out, int64_t* slot, void* stream);
+int egnn_gcn_norm_scale_i64(const int64_t* rowptr_out, const int64_t* col_out, int64_t n, const float* w, const float* deg,
+                            float* dinv, float* val_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Dense fp32 GEMM on the f32-input MFMA (v_mfma_f32_32x32x2_f32, exact fp32 == fmaf chain).
