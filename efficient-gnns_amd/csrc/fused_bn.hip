@@ -116,6 +116,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const BnParams q, float
   const int lane = egnn_lane();
   const int wave = egnn_wave_id();
   const int chunks = (int)((q.C + 255) / 256);
+  const BnGate gt = bn_gate(q);
   for (int j = 0; j < chunks; ++j) {
     const int64_t c = j * 256 + lane * 4;
     if (c >= q.C) continue;
@@ -132,10 +133,11 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const BnParams q, float
       const float4 v = *reinterpret_cast<const float4*>(q.x + src * q.ldx + c);
       const float xv[4] = {v.x, v.y, v.z, v.w};
       float o[4];
+      const unsigned keep = bn_keep4_hash(q, gt, src, c);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float xhat, gate;
-        bn_elem(q, xv[k], mean[k], rstd[k], g[k], b[k], src, c + k, xhat, gate);
+        bn_elem(q, gt, (keep >> k) & 1u, xv[k], mean[k], rstd[k], g[k], b[k], xhat, gate);
         o[k] = (g[k] * xhat + b[k]) * gate;
       }
       *reinterpret_cast<float4*>(y + row * ldy + c) = make_float4(o[0], o[1], o[2], o[3]);
@@ -150,6 +152,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(const BnParams q
   const int lane = egnn_lane();
   const int wave = egnn_wave_id();
   const int chunks = (int)((q.C + 255) / 256);
+  const BnGate gt = bn_gate(q);
   for (int j = 0; j < chunks; ++j) {
     const int64_t c = j * 256 + lane * 4;
     float sd[4] = {0.f, 0.f, 0.f, 0.f}, sx[4] = {0.f, 0.f, 0.f, 0.f};
@@ -179,10 +182,11 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(const BnParams q
         for (int u = 0; u < 4; ++u) {
           const float xv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
           const float gv[4] = {gd[u].x, gd[u].y, gd[u].z, gd[u].w};
+          const unsigned keep = bn_keep4_hash(q, gt, src[u], c);
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             float xhat, gate;
-            bn_elem(q, xv[k], mean[k], rstd[k], g[k], b[k], src[u], c + k, xhat, gate);
+            bn_elem(q, gt, (keep >> k) & 1u, xv[k], mean[k], rstd[k], g[k], b[k], xhat, gate);
             const float d = gv[k] * gate;
             sd[k] += d;
             sx[k] = fmaf(d, xhat, sx[k]);
@@ -195,10 +199,11 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(const BnParams q
         const float4 gd = *reinterpret_cast<const float4*>(dy + row * ldd + c);
         const float xv[4] = {v.x, v.y, v.z, v.w};
         const float gv[4] = {gd.x, gd.y, gd.z, gd.w};
+        const unsigned keep = bn_keep4_hash(q, gt, src, c);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           float xhat, gate;
-          bn_elem(q, xv[k], mean[k], rstd[k], g[k], b[k], src, c + k, xhat, gate);
+          bn_elem(q, gt, (keep >> k) & 1u, xv[k], mean[k], rstd[k], g[k], b[k], xhat, gate);
           const float d = gv[k] * gate;
           sd[k] += d;
           sx[k] = fmaf(d, xhat, sx[k]);
@@ -247,6 +252,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const BnParams q,
   const int lane = egnn_lane();
   const int wave = egnn_wave_id();
   const int chunks = (int)((q.C + 255) / 256);
+  const BnGate gt = bn_gate(q);
   for (int j = 0; j < chunks; ++j) {
     const int64_t c = j * 256 + lane * 4;
     float so[4] = {0.f, 0.f, 0.f, 0.f};
@@ -285,11 +291,13 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const BnParams q,
         float4 prev = make_float4(0.f, 0.f, 0.f, 0.f);
         if constexpr (MODE == 2) prev = *reinterpret_cast<const float4*>(dx + src * ldx_out + c);
         const float pv[4] = {prev.x, prev.y, prev.z, prev.w};
+        unsigned keep = 0xFu;
+        if constexpr (MODE != 3) keep = bn_keep4_hash(q, gt, src, c);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           float xhat, gate;
           if constexpr (MODE == 3) { xhat = (xv[k] - mean[k]) * rstd[k]; gate = 1.f; }   // dy is d = g * gate already
-          else bn_elem(q, xv[k], mean[k], rstd[k], g[k], b[k], src, c + k, xhat, gate);
+          else bn_elem(q, gt, (keep >> k) & 1u, xv[k], mean[k], rstd[k], g[k], b[k], xhat, gate);
           const float d = gv[k] * gate;
           if constexpr (MODE == 2) o[k] = pv[k] + g[k] * rstd[k] * d;
           else o[k] = g[k] * rstd[k] * (d - sb[k] - xhat * sg[k]);
@@ -362,12 +370,14 @@ int row_blocks(int64_t n) {
 
 // The checks every entry point makes of the descriptor, and the two parameter blocks it stands for: `all` = every row of x (the
 // statistics' rows, dx), `out` = the output rows x[pick[i]] (pick == NULL: every row again).
+// `wide` is decided HERE and nowhere else: the hash takes the 64-bit element index only when the rows of x hold more than 2^32 elements.
 int bn_unpack(const egnn_bn_act_t* b, BnParams& all, BnParams& out) {
   EGNN_CHECK_ARG(b && b->n > 0 && b->x && b->mean && b->var && b->ld >= b->C);
   EGNN_CHECK_ARG(!b->pick || (b->n_pick >= 0 && b->n_pick <= b->n));
   if (!shape_ok(b->x, b->ld, b->C)) return EGNN_EALIGN;
+  const int wide = b->n > (int64_t)((1ULL << 32) / (unsigned long long)b->C) ? 1 : 0;   // n * C > 2^32
   all = BnParams{b->x, b->ld, b->n, b->C, b->mean, b->var, b->eps, b->gamma, b->beta, b->relu, b->p, (unsigned long long)b->seed,
-                 (const unsigned long long*)b->seed_dev, nullptr};
+                 (const unsigned long long*)b->seed_dev, nullptr, wide};
   out = all;
   if (b->pick) { out.n = b->n_pick; out.pick = b->pick; }
   return EGNN_OK;
@@ -563,6 +573,7 @@ __global__ __launch_bounds__(256, OCC) void skinny_dx_bn_kernel(const float* __r
   const int64_t mbeg = sb * RB * rblocks;
   if (mbeg >= M) return;
   const int c0 = cb * 64 + 4 * r16;
+  const BnGate gt = bn_gate(q);
   float4 bf[KSTEPS];
 #pragma unroll
   for (int s = 0; s < KSTEPS; ++s) {
@@ -644,10 +655,11 @@ __global__ __launch_bounds__(256, OCC) void skinny_dx_bn_kernel(const float* __r
         if constexpr (ADD) { dh[0] += av[r].x; dh[1] += av[r].y; dh[2] += av[r].z; dh[3] += av[r].w; }
         const float xv[4] = {yv[r].x, yv[r].y, yv[r].z, yv[r].w};
         float d[4];
+        const unsigned keep = bn_keep4_hash(q, gt, (int64_t)rowc[r], c0);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           float xhat, gate;
-          bn_elem(q, xv[k], mean[k], rstd[k], gm[k], bt[k], (int64_t)rowc[r], c0 + k, xhat, gate);
+          bn_elem(q, gt, (keep >> k) & 1u, xv[k], mean[k], rstd[k], gm[k], bt[k], xhat, gate);
           d[k] = live ? dh[k] * gate : 0.f;
           sd[k] += d[k];
           sx[k] = fmaf(d[k], xhat, sx[k]);
@@ -689,6 +701,7 @@ __global__ __launch_bounds__(256, 3) void tail_bwd_tile_kernel(const float* __re
   const int64_t M = q.n;
   // phase-2 ownership: columns 4 lane .. 4 lane + 3 of whole rows
   const int c2 = 4 * lane;
+  const BnGate gt = bn_gate(q);
   float mean[4], rstd[4], gm[4], bt[4], sd[4] = {0.f, 0.f, 0.f, 0.f}, sx[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -775,10 +788,11 @@ __global__ __launch_bounds__(256, 3) void tail_bwd_tile_kernel(const float* __re
         if constexpr (ADD) { dh[0] += av[u].x; dh[1] += av[u].y; dh[2] += av[u].z; dh[3] += av[u].w; }
         const float xv[4] = {yv[u].x, yv[u].y, yv[u].z, yv[u].w};
         float d[4];
+        const unsigned keep = bn_keep4_hash(q, gt, (int64_t)rowc[u], c2);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           float xhat, gate;
-          bn_elem(q, xv[k], mean[k], rstd[k], gm[k], bt[k], (int64_t)rowc[u], c2 + k, xhat, gate);
+          bn_elem(q, gt, (keep >> k) & 1u, xv[k], mean[k], rstd[k], gm[k], bt[k], xhat, gate);
           d[k] = live ? dh[k] * gate : 0.f;
           sd[k] += d[k];
           sx[k] = fmaf(d[k], xhat, sx[k]);
@@ -831,6 +845,7 @@ __global__ __launch_bounds__(256, 4) void tail_fwd_tile_kernel(const BnParams q,
   const int r16 = lane & 15, qq = lane >> 4;
   const int64_t M = q.n;
   const int c2 = 4 * lane;
+  const BnGate gt = bn_gate(q);
   float mean[4], rstd[4], gm[4], bt[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -868,10 +883,11 @@ __global__ __launch_bounds__(256, 4) void tail_fwd_tile_kernel(const BnParams q,
         if constexpr (BN) {
           const float xv[4] = {yv[u].x, yv[u].y, yv[u].z, yv[u].w};
           float o[4];
+          const unsigned keep = bn_keep4_hash(q, gt, (int64_t)rowc[u], c2);
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             float xhat, gate;
-            bn_elem(q, xv[k], mean[k], rstd[k], gm[k], bt[k], (int64_t)rowc[u], c2 + k, xhat, gate);
+            bn_elem(q, gt, (keep >> k) & 1u, xv[k], mean[k], rstd[k], gm[k], bt[k], xhat, gate);
             o[k] = (gm[k] * xhat + bt[k]) * gate;
           }
           const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
