@@ -169,6 +169,10 @@ SIGNATURES = {
     "egnn_rows_plan_build_i64": (_i32, [_p, _i64, _i64, _p, _p, _p, _sz, _p]),
     "egnn_rows_add_runs_ws_bytes": (_sz, [_i64, _i64]),
     "egnn_rows_add_runs_f32": (_i32, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _i64, _i32, _p, _sz, _p]),
+    "egnn_rows_wrap_i64": (_i32, [_p, _i64, _i64, _p, _p]),
+    "egnn_scatter_runs_ws_bytes": (_sz, [_i64, _i64, _i32]),
+    "egnn_scatter_runs_f32": (_i32, [_p, _i64, _i64, _p, _p, _p, _i64, _i32, _p, _i64, _i64, _i32, _p, _sz, _p]),
+    "egnn_scatter_bwd_f32": (_i32, [_p, _i64, _i64, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _p]),
     "egnn_feature_loss_ws_floats": (_sz, [_i64]),
     "egnn_fitnet_fwd_f32": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _sz, _p]),
     "egnn_fitnet_bwd_f32": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _i64, _p, _i64, _p]),

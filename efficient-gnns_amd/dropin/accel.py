@@ -86,6 +86,7 @@ def enable() -> None:
         return lin_forward(self, x)
     torch.nn.BatchNorm1d.forward = fast_bn
     torch.nn.Linear.forward = fast_linear
+    L.ACCEL_ACTIVE = True     # nn.MessagePassing asks: a lifted x_j is handed out as LazyRows only while Linear.forward consumes one
 
     # the package's own convs (what the script's `from torch_geometric.nn import GCNConv, SAGEConv` resolves to) as CONSUMERS of a deferred
     # activation: one fused launch; for a GCNConv with a narrow output together with its h @ W (ops.bn_act_linear, gnn.py:47-52)
@@ -216,7 +217,9 @@ def disable() -> None:
         return
     torch.nn.BatchNorm1d.forward = _orig.pop("bn")
     torch.nn.Linear.forward = _orig.pop("lin")
+    from efficient_gnns_amd import lazy as L
     from efficient_gnns_amd import nn as PN
+    L.ACCEL_ACTIVE = False
     PN.GCNConv.forward = _orig.pop("gcn")
     PN.SAGEConv.forward = _orig.pop("sage")
     torch.optim.Adam.__init__ = _orig.pop("adam")

@@ -32,6 +32,9 @@ import torch.nn.functional as F
 from . import _cache, ops
 
 
+ACCEL_ACTIVE = False   # set by dropin/accel.py's enable() / disable(): torch.nn.Linear.forward consumes a LazyRows
+
+
 def materialise(x, pick=None):
     """``x`` as a real tensor (``x[pick]`` when ``pick`` is given): deferred objects are formed now, tensors pass through."""
     m = getattr(x, "_egnn_materialise", None)
@@ -237,8 +240,10 @@ class LazyRows(_TensorLike):
     unique ids take the same kernels as before).  A ``torch.Tensor`` base is read when the rows are formed, not when they were asked for:
     its version is recorded, and a base changed in place in between raises instead of handing out the changed rows."""
 
-    def __init__(self, base, idx, const_base=False, base_version=None):
-        self._base, self._idx, self._value, self._const = base, idx, None, const_base
+    def __init__(self, base, idx, const_base=False, base_version=None, plan=None):
+        # ``plan``: a callable returning the ready ``ops.RowsPlan`` of ``idx`` (nn.MessagePassing shares one per endpoint: the gather,
+        # its backward and the aggregation walk the same keys); None: the host-checked plan of ``idx`` is built (and cached)
+        self._base, self._idx, self._value, self._const, self._plan = base, idx, None, const_base, plan
         self._base_version = base_version if base_version is not None else (base._version if isinstance(base, torch.Tensor) else None)
 
     shape = property(lambda self: torch.Size((self._idx.numel(),) + tuple(self._base.shape[1:])))
@@ -257,19 +262,19 @@ class LazyRows(_TensorLike):
             base = self._formed_base()
             if pick is not None:
                 return self._take(base, self._composed(pick))
-            self._value = self._take(base, self._idx)
+            self._value = self._take(base, self._idx if self._plan is None else self._plan())
         return self._value if pick is None else self._value[pick]
 
     @staticmethod
     def _take(base, idx):
         # (accel only defers GPU indices; rows of a CPU tensor are torch's own indexing, which has x[idx]'s rules by definition)
-        return ops.take_rows(base, idx, duplicates="sum") if idx.is_cuda else base[idx]
+        return ops.take_rows(base, idx, duplicates="sum") if isinstance(idx, ops.RowsPlan) or idx.is_cuda else base[idx]
 
     def linear(self, weight, bias):
         base = self._formed_base()
         # ``const_base``: the gathered-from tensor is a leaf outside autograd (accel's deferred constant gather): its rows as once-cut planes
         const = bool(self._const and not base.requires_grad and base.grad_fn is None)
-        return ops.linear_rows(base, self._idx, weight, bias, const_input=const, duplicates="sum")
+        return ops.linear_rows(base, self._idx if self._plan is None else self._plan(), weight, bias, const_input=const, duplicates="sum")
 
     def _composed(self, idx2):
         """``idx[idx2]``, memoised on the pair: a script composes it anew every step, its plan is built once."""

@@ -6,6 +6,7 @@ reference's ``state_dict`` files hold (/root/reference/arxiv_pyg/gnn.py:13,28-35
 """
 from __future__ import annotations
 
+import inspect
 import math
 
 import torch
@@ -512,3 +513,197 @@ class RGCNConv(nn.Module):
 
     def __repr__(self):
         return f"RGCNConv({self.in_channels}, {self.out_channels}, node_types={self.num_node_types}, edge_types={self.num_edge_types})"
+
+
+# ------------------------------------------------------------------------------------------------
+# user-defined convs in PyG's own idiom: gather x_j / x_i, message, aggregate by target, update
+# ------------------------------------------------------------------------------------------------
+_MP_AGGRS = ("add", "sum", "mean", "max", "min")
+_MP_FLOWS = ("source_to_target", "target_to_source")
+_MP_SPECIAL = ("edge_index", "edge_index_i", "edge_index_j", "index", "size", "size_i", "size_j", "dim_size", "ptr", "adj_t")
+_MP_EMPTY = inspect.Parameter.empty
+
+
+class _Propagation:
+    """One ``propagate`` call: the two endpoint id vectors (0: source side, 1: target side of ``edge_index``), the node counts seen so
+    far, and AT MOST ONE deferred ``ops.rows_plan`` per endpoint, built when first asked for and shared by the lift (``x_j`` / ``x_i``),
+    the lift's backward and the aggregation."""
+
+    def __init__(self, ends, size, ptr=None, edge_index=None, adj_t=None):
+        self.ends, self.size, self.ptr, self.edge_index, self.adj_t = ends, size, ptr, edge_index, adj_t
+        self.plans = [None, None]
+
+    def see(self, end: int, n: int, what: str) -> None:
+        if self.size[end] is None:
+            self.size[end] = int(n)
+        elif self.size[end] != int(n):
+            raise ValueError(f"MessagePassing.propagate: `{what}` has {int(n)} rows, but side {end} of the graph has {self.size[end]} nodes")
+
+    def plan(self, end: int):
+        if self.plans[end] is None:
+            self.plans[end] = ops.rows_plan(self.ends[end].contiguous(), self.size[end], check="deferred")
+        return self.plans[end]
+
+    def lift(self, t, end: int, node_dim: int, what: str):
+        from . import lazy
+        t = _lib.real(t)
+        if not isinstance(t, Tensor):
+            raise TypeError(f"MessagePassing.propagate: `{what}` must be a tensor, a (source, target) pair of tensors or None")
+        if node_dim == -2 and t.dim() > 2:
+            raise NotImplementedError("MessagePassing: node_dim=-2 is supported for node tensors of at most 2 dimensions (the node axis is 0)")
+        self.see(end, t.shape[0], what)
+        _lib.require_gpu(t)
+        idx = self.ends[end]
+        if lazy.ACCEL_ACTIVE and t.dim() == 2 and t.dtype == torch.float32 and idx.numel() > 0:
+            # under accel: not gathered yet -- a Linear in `message` runs the gather-fused GEMM (ops.linear_rows), anything else forms the rows
+            return lazy.LazyRows(t, idx, plan=lambda: self.plan(end))
+        return ops.take_rows(t, self.plan(end))
+
+
+class MessagePassing(nn.Module):
+    """``torch_geometric.nn.MessagePassing`` (PyG <= 1.7) on the package's kernels, for convs written in PyG's own idiom::
+
+        class MyConv(MessagePassing):
+            def __init__(self): super().__init__(aggr="mean")
+            def forward(self, x, edge_index, w): return self.propagate(edge_index, x=x, w=w)
+            def message(self, x_i, x_j, w): return w.view(-1, 1) * (x_j - x_i)
+            def update(self, aggr_out, x): return aggr_out + x
+
+    ``propagate(edge_index, size=None, **kwargs)`` reads the parameter names of ``message`` / ``aggregate`` / ``update`` /
+    ``message_and_aggregate`` (``inspect``, once per class).  With ``(j, i) = (0, 1)`` for ``flow="source_to_target"`` and ``(1, 0)``
+    otherwise, a message parameter ``name_j`` / ``name_i`` receives ``kwargs[name]`` lifted to the edges by ``edge_index[j]`` /
+    ``edge_index[i]`` (None stays None; of a ``(source, target)`` pair -- source_to_target only -- element 0 / 1); every other
+    parameter receives ``kwargs[name]`` as it is (an int such as ``edge_type``, a per-edge tensor such as ``edge_weight``).  Special
+    names: ``edge_index``, ``edge_index_i``, ``edge_index_j``, ``index`` (= ``edge_index[i]``), ``size``, ``size_i``, ``size_j``,
+    ``dim_size`` (the target side), ``ptr`` (None for an edge list) and ``adj_t``.  Node counts come from ``size`` or from the node
+    tensors.  Defaults: ``message(x_j) -> x_j``, ``aggregate`` = ``ops.scatter`` by ``index`` with the class's ``aggr``, ``update`` =
+    identity.  A ``SparseTensor`` (the transposed adjacency, source_to_target only) goes to ``message_and_aggregate`` when the subclass
+    defines it, and is otherwise taken apart (row -> i, col -> j, ``ptr`` = rowptr).
+
+    The lift is ``ops.take_rows`` and the aggregation ``ops.scatter``, both over ONE ``ops.rows_plan(check="deferred")`` per endpoint
+    and call: no host read per fresh ``edge_index[:, mask]``; an id out of range is dropped and counted (``ops.rows_oob``), not
+    raised.  Under ``accel`` a lifted 2-D fp32 tensor is handed out as ``lazy.LazyRows``: ``self.lin(x_j)`` runs as the gather-fused
+    ``ops.linear_rows``.  GPU only, like every operator of the package."""
+
+    def __init__(self, aggr: str = "add", flow: str = "source_to_target", node_dim: int = -2):
+        super().__init__()
+        if aggr not in _MP_AGGRS:
+            raise ValueError(f"MessagePassing: aggr must be one of {_MP_AGGRS}, got {aggr!r}")
+        if flow not in _MP_FLOWS:
+            raise ValueError(f"MessagePassing: flow must be one of {_MP_FLOWS}, got {flow!r}")
+        if node_dim not in (0, -2):
+            raise NotImplementedError(f"MessagePassing: node_dim must be 0 or -2 (the node axis is the first one), got {node_dim!r}")
+        self.aggr, self.flow, self.node_dim = aggr, flow, node_dim
+        self._mp_call = None
+
+    # ---- what a subclass overrides -------------------------------------------------------------
+    def message(self, x_j):
+        return x_j
+
+    def aggregate(self, inputs, index, ptr=None, dim_size=None):
+        call = self._mp_call
+        plan = None
+        if call is not None:
+            i = 1 if self.flow == "source_to_target" else 0
+            if index is call.ends[i]:
+                if dim_size is not None:
+                    call.see(i, dim_size, "dim_size")
+                elif call.size[i] is None:
+                    call.size[i] = int(index.max()) + 1 if index.numel() else 0     # (no node tensor was seen: one host read, as PyG)
+                plan, dim_size = call.plan(i), call.size[i]
+        if plan is None:
+            if dim_size is None:
+                dim_size = int(index.max()) + 1 if index.numel() else 0
+            plan = ops.rows_plan(index.contiguous(), dim_size, check="deferred")
+        return ops.scatter(inputs, index, dim_size, reduce=self.aggr, plan=plan)
+
+    def message_and_aggregate(self, adj_t):
+        raise NotImplementedError
+
+    def update(self, inputs):
+        return inputs
+
+    # ---- propagate -----------------------------------------------------------------------------
+    @classmethod
+    def _mp_params(cls):
+        """{function name: [(parameter name, has a default)]}, read once per class (``aggregate`` / ``update`` without their first,
+        positional, parameter)."""
+        got = cls.__dict__.get("_mp_params_cache")
+        if got is None:
+            got = {}
+            for fn, skip in (("message", 1), ("aggregate", 2), ("update", 2), ("message_and_aggregate", 2)):
+                ps = list(inspect.signature(getattr(cls, fn)).parameters.values())[skip:]
+                got[fn] = [(p.name, p.default is not _MP_EMPTY) for p in ps if p.kind in (p.POSITIONAL_OR_KEYWORD, p.KEYWORD_ONLY)]
+            cls._mp_params_cache = got
+        return got
+
+    def _mp_collect(self, fn: str, call: _Propagation, kwargs: dict, lifted: dict) -> dict:
+        j, i = (0, 1) if self.flow == "source_to_target" else (1, 0)
+        params = self._mp_params()[fn]
+        if fn == "message":
+            # the lifts first: they settle the node counts the special names report
+            for name, has_default in params:
+                if name in _MP_SPECIAL or not name.endswith(("_i", "_j")):
+                    continue
+                base = name[:-2]
+                if base not in kwargs:
+                    if has_default:
+                        continue
+                    raise TypeError(f"MessagePassing.propagate: `message` needs `{name}`, but no `{base}` was given")
+                data = kwargs[base]
+                if isinstance(data, (tuple, list)):
+                    if self.flow != "source_to_target":
+                        raise NotImplementedError("MessagePassing: (source, target) pairs are supported for flow='source_to_target' only")
+                    if len(data) != 2:
+                        raise ValueError(f"MessagePassing.propagate: `{base}` must be a (source, target) pair")
+                    data = data[0 if name.endswith("_j") else 1]
+                lifted[name] = None if data is None else call.lift(data, j if name.endswith("_j") else i, self.node_dim, base)
+            for e in (0, 1):     # a side no node tensor settled: the other side's count, as PyG does for a single node set
+                if call.size[e] is None:
+                    call.size[e] = call.size[1 - e]
+        special = {"edge_index": call.edge_index, "edge_index_i": call.ends[i], "edge_index_j": call.ends[j], "index": call.ends[i],
+                   "size": call.size, "size_i": call.size[i], "size_j": call.size[j], "dim_size": call.size[i], "ptr": call.ptr,
+                   "adj_t": call.adj_t}
+        out = {}
+        for name, has_default in params:
+            if name in special:
+                out[name] = special[name]
+            elif name in lifted:
+                out[name] = lifted[name]
+            elif name in kwargs:
+                out[name] = kwargs[name]
+            elif not has_default:
+                raise TypeError(f"MessagePassing.propagate: `{fn}` needs `{name}`, which was not given")
+        return out
+
+    def propagate(self, edge_index, size=None, **kwargs):
+        size = [None, None] if size is None else [None if s is None else int(s) for s in size]
+        if len(size) != 2:
+            raise ValueError("MessagePassing.propagate: `size` is None or a pair (sources, targets)")
+        if isinstance(edge_index, SparseTensor):
+            if self.flow != "source_to_target":
+                raise NotImplementedError("MessagePassing: a SparseTensor adjacency is supported for flow='source_to_target' only")
+            _lib.require_gpu(edge_index._col)
+            if type(self).message_and_aggregate is not MessagePassing.message_and_aggregate:
+                call = _Propagation((None, None), [edge_index.sparse_size(1), edge_index.sparse_size(0)], edge_index._rowptr, None, edge_index)
+                out = self.message_and_aggregate(edge_index, **self._mp_collect("message_and_aggregate", call, kwargs, {}))
+                return self.update(out, **self._mp_collect("update", call, kwargs, {}))
+            row, col, _ = edge_index.coo()
+            call = _Propagation((col, row), [edge_index.sparse_size(1), edge_index.sparse_size(0)], edge_index._rowptr, None, edge_index)
+        else:
+            if not (isinstance(edge_index, Tensor) and edge_index.dtype == torch.int64 and edge_index.dim() == 2 and edge_index.shape[0] == 2):
+                raise TypeError("MessagePassing.propagate: `edge_index` must be an int64 tensor [2, E] or a SparseTensor")
+            _lib.require_gpu(edge_index)
+            call = _Propagation((edge_index[0], edge_index[1]), size, None, edge_index, None)
+        outer, self._mp_call = self._mp_call, call
+        try:
+            lifted: dict = {}
+            msg_kwargs = self._mp_collect("message", call, kwargs, lifted)
+            out = self.message(**msg_kwargs)
+            out = self.aggregate(out, **self._mp_collect("aggregate", call, kwargs, lifted))
+            return self.update(out, **self._mp_collect("update", call, kwargs, lifted))
+        finally:
+            self._mp_call = outer
+
+    def __repr__(self):
+        return f"{type(self).__name__}()"

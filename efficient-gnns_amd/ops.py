@@ -474,24 +474,100 @@ def spmm_max_bwd_rows(t_adj, t_eid: Tensor, val: Tensor | None, argmax: Tensor, 
 # ------------------------------------------------------------------------------------------------
 class RowsPlan:
     """What ``duplicates="sum"`` knows about one index tensor: ``idx`` (the wrapped copy when an entry was negative), the counters, and
-    -- only when a row is named more than once -- the sorted (row, position) keys ``egnn_rows_add_runs_f32`` walks."""
-    __slots__ = ("idx", "n_rows", "S", "dups", "negatives", "longest", "keys", "shift")
+    -- only when a row is named more than once -- the sorted (row, position) keys ``egnn_rows_add_runs_f32`` walks.  ``all_keys`` are
+    the sorted keys whether or not a row repeats (``scatter`` always walks them) and ``rows`` the row ids as ``egnn_scatter_bwd_f32``
+    reads them.  A ``deferred`` plan (``rows_plan(check="deferred")``) was built without a host read: ``dups`` / ``negatives`` /
+    ``longest`` are unknown (None: "may repeat", the keys are kept), ``idx`` is safe to gather by (an id out of range reads row 0)
+    and ``rows`` marks such an id with -1, so it gets no gradient."""
+    __slots__ = ("idx", "n_rows", "S", "dups", "negatives", "longest", "keys", "shift", "all_keys", "rows", "deferred")
 
-    def __init__(self, idx, n_rows, S, dups=0, negatives=0, longest=0, keys=None, shift=1):
+    def __init__(self, idx, n_rows, S, dups=0, negatives=0, longest=0, keys=None, shift=1, all_keys=None, rows=None, deferred=False):
         self.idx, self.n_rows, self.S, self.dups, self.negatives, self.longest, self.keys, self.shift = idx, n_rows, S, dups, negatives, longest, keys, shift
+        self.all_keys, self.rows, self.deferred = all_keys, idx if rows is None else rows, deferred
 
 
 _ROWS_PLANS = _cache.TensorKeyedCache(capacity=16, max_bytes=1 << 30)
+_ROWS_OOB: dict = {}      # device -> int32 [1]: row ids that deferred plans found out of range (and the kernels therefore dropped)
 
 
-def rows_plan(idx: Tensor, n_rows: int) -> RowsPlan:
-    """The plan of ``idx`` (1-D int64, GPU) over a tensor of ``n_rows`` rows, built once per index tensor (identity + version, like the
-    package's other integer preprocessing) with ONE host read, of the four counters.  An id outside [-n_rows, n_rows) raises
-    ``IndexError``; the build cannot happen inside a graph capture (it reads the counters): a warm-up step builds it."""
+def rows_oob(device, reset: bool = True) -> int:
+    """How many row ids the plans built with ``rows_plan(check="deferred")`` on ``device`` found outside [-n_rows, n_rows) since the
+    last reset; the kernels dropped those entries.  A host read, made on demand (the deferred plans themselves make none)."""
+    c = _ROWS_OOB.get(_indexed_device(device))
+    if c is None:
+        return 0
+    n = int(c.item())
+    if reset and n:
+        c.zero_()
+    return n
+
+
+def _indexed_device(device) -> torch.device:
+    dev = torch.device(device)
+    return dev if dev.index is not None or dev.type != "cuda" else torch.device(dev.type, torch.cuda.current_device())
+
+
+def _rows_plan_launch(ids: Tensor, n_rows: int):
+    lib = _lib.load()
+    S = ids.numel()
+    keys = torch.empty(S, dtype=torch.int64, device=ids.device)      # the bits of the uint64 keys
+    counters = torch.empty(4, dtype=torch.int32, device=ids.device)
+    nws = lib.egnn_rows_plan_ws_bytes(S, n_rows)
+    ws = torch.empty(nws, dtype=torch.uint8, device=ids.device)
+    _lib.check(lib.egnn_rows_plan_build_i64(_lib.ptr(ids), S, n_rows, _lib.ptr(keys), _lib.ptr(counters), _lib.ptr(ws), nws, _lib.stream()),
+               "egnn_rows_plan_build_i64")
+    return keys, counters
+
+
+def _rows_plan_deferred(idx: Tensor, n_rows: int) -> RowsPlan:
+    ids, S = idx.contiguous(), idx.numel()
+    if S == 0:
+        return RowsPlan(ids, n_rows, 0, None, None, None, deferred=True)
+    if n_rows <= 0:     # (known without a read: every id is out of range, and there is no row 0 a dropped id could be gathered as)
+        raise IndexError(f"index out of range: {S} row ids into a tensor of {n_rows} rows")
+    dev = ids.device
+    counter = _ROWS_OOB.get(dev)
+    if counter is None:
+        if torch.cuda.graphs.is_current_stream_capturing():
+            raise RuntimeError("rows_plan(check='deferred'): the device's out-of-range counter does not exist yet and must outlive the graph: "
+                               "run one warm-up step (or call ops.rows_oob_counter(device)) before the capture")
+        counter = rows_oob_counter(dev)
+    keys, counters = _rows_plan_launch(ids, n_rows)
+    counter += counters[:1]
+    rows = torch.empty_like(ids)
+    _lib.check(_lib.load().egnn_rows_wrap_i64(_lib.ptr(ids), S, n_rows, _lib.ptr(rows), _lib.stream()), "egnn_rows_wrap_i64")
+    return RowsPlan(rows.clamp_min(0), n_rows, S, None, None, None, keys, max(1, (S - 1).bit_length()), keys, rows, True)
+
+
+def rows_oob_counter(device) -> Tensor:
+    """The int32 [1] counter behind ``rows_oob`` (created on first use; a graph capture needs it to exist beforehand)."""
+    dev = _indexed_device(device)
+    c = _ROWS_OOB.get(dev)
+    if c is None:
+        c = _ROWS_OOB[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return c
+
+
+def rows_plan(idx: Tensor, n_rows: int, check: str = "host") -> RowsPlan:
+    """The plan of ``idx`` (1-D int64, GPU) over a tensor of ``n_rows`` rows.
+
+    ``check="host"`` (default): built once per index tensor (identity + version, like the package's other integer preprocessing) with
+    ONE host read, of the four counters.  An id outside [-n_rows, n_rows) raises ``IndexError``; the build cannot happen inside a graph
+    capture (it reads the counters): a warm-up step builds it.
+
+    ``check="deferred"``: for index tensors that are new every step (``edge_index[:, mask]`` of a mini-batch).  No host read and no
+    entry in the identity cache (fresh tensors would evict the long-lived plans); usable inside a graph capture.  Negative ids are
+    wrapped on the device, the keys are always kept (``dups`` is unknown: "may repeat"), and an id out of range is DROPPED by the
+    kernels -- gathered as row 0, without a gradient, and left out of every aggregation -- and added to the per-device counter that
+    ``rows_oob`` reads on demand."""
     if not (isinstance(idx, Tensor) and idx.dtype == torch.int64 and idx.dim() == 1):
         raise TypeError("rows_plan: `idx` must be a 1-D int64 tensor")
+    if check not in ("host", "deferred"):
+        raise ValueError(f"check must be 'host' or 'deferred', got {check!r}")
     _lib.require_gpu(idx)
     n_rows = int(n_rows)
+    if check == "deferred":
+        return _rows_plan_deferred(idx, n_rows)
 
     def build():
         if torch.cuda.graphs.is_current_stream_capturing():
@@ -500,20 +576,23 @@ def rows_plan(idx: Tensor, n_rows: int) -> RowsPlan:
         ids, S = idx.contiguous(), idx.numel()
         if S == 0:
             return RowsPlan(ids, n_rows, 0)
-        lib = _lib.load()
-        keys = torch.empty(S, dtype=torch.int64, device=idx.device)      # the bits of the uint64 keys
-        counters = torch.empty(4, dtype=torch.int32, device=idx.device)
-        nws = lib.egnn_rows_plan_ws_bytes(S, n_rows)
-        ws = torch.empty(nws, dtype=torch.uint8, device=idx.device)
-        _lib.check(lib.egnn_rows_plan_build_i64(_lib.ptr(ids), S, n_rows, _lib.ptr(keys), _lib.ptr(counters), _lib.ptr(ws), nws, _lib.stream()),
-                   "egnn_rows_plan_build_i64")
+        keys, counters = _rows_plan_launch(ids, n_rows)
         oob, dups, neg, longest = counters.tolist()                      # the one host read
         if oob:
             raise IndexError(f"index out of range: {oob} of {S} row ids are outside [-{n_rows}, {n_rows})")
         if neg:
             ids = torch.where(ids < 0, ids + n_rows, ids)
-        return RowsPlan(ids, n_rows, S, dups, neg, longest, keys if dups else None, max(1, (S - 1).bit_length()))
+        return RowsPlan(ids, n_rows, S, dups, neg, longest, keys if dups else None, max(1, (S - 1).bit_length()), keys)
     return _ROWS_PLANS.get((idx,), (n_rows,), build)
+
+
+def _plan_for(idx, n_rows: int, what: str) -> RowsPlan:
+    """``idx`` as a plan over ``n_rows`` rows: a ready ``RowsPlan`` (checked against the operand) or the host-checked plan of a tensor."""
+    if isinstance(idx, RowsPlan):
+        if idx.n_rows != int(n_rows):
+            raise ValueError(f"{what}: the plan was built for {idx.n_rows} rows, the operand has {int(n_rows)}")
+        return idx
+    return rows_plan(idx, n_rows)
 
 
 def _check_duplicates(duplicates) -> bool:
@@ -568,11 +647,90 @@ class _TakeRows(torch.autograd.Function):
 def take_rows(x: Tensor, idx: Tensor, duplicates: str = "unique") -> Tensor:
     """``x[idx]`` for a 1-D int64 ``idx``.  ``duplicates="unique"`` (default): the caller knows the ids to be unique and in range;
     nothing is checked.  ``"sum"``: torch's rules for any ``idx`` -- negative ids wrap, an id out of range raises ``IndexError``, and
-    the gradients of a row named several times are summed (``rows_plan``; with unique ids the same kernels and bits as "unique")."""
-    if not _check_duplicates(duplicates):
+    the gradients of a row named several times are summed (``rows_plan``; with unique ids the same kernels and bits as "unique").
+    ``idx`` may be a ready ``RowsPlan`` (``duplicates`` is then not consulted): nothing is built, and the same plan can serve
+    ``scatter``."""
+    if isinstance(idx, RowsPlan):
+        _lib.require_gpu(x)
+    elif not _check_duplicates(duplicates):
         return _TakeRows.apply(x, idx)
-    plan = rows_plan(idx, x.shape[0])
-    return _TakeRows.apply(x, plan.idx, plan if plan.dups else None)
+    plan = _plan_for(idx, x.shape[0], "take_rows")
+    return _TakeRows.apply(x, plan.idx, plan if plan.keys is not None else None)
+
+
+# ------------------------------------------------------------------------------------------------
+# aggregation by an unsorted index (csrc/scatter.hip): torch_scatter.scatter along dim 0, the aggregate step of nn.MessagePassing
+# ------------------------------------------------------------------------------------------------
+_SCATTER_REDUCE = {"sum": 0, "add": 0, "mean": 1, "max": 2, "min": 3}
+
+
+class _Scatter(torch.autograd.Function):
+    """out[r] = reduce of src[p] over index[p] == r (egnn_scatter_runs_f32 over the plan's sorted keys); the backward is the gather
+    form egnn_scatter_bwd_f32 into an uninitialised gradient.  First derivatives only."""
+
+    @staticmethod
+    def forward(ctx, src, plan, red):
+        src = _rowmajor(src)
+        lib = _lib.load()
+        S, C = src.shape
+        n, dev = plan.n_rows, src.device
+        out = torch.empty((n, C), dtype=torch.float32, device=dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev) if red == 1 else None
+        arg = torch.empty((n, C), dtype=torch.int64, device=dev) if red >= 2 else None
+        nws = lib.egnn_scatter_runs_ws_bytes(S, C, red)
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+        _lib.check(lib.egnn_scatter_runs_f32(_lib.ptr(out), out.stride(0), n, _lib.ptr(count), _lib.ptr(arg), _lib.ptr(plan.all_keys), S,
+                                             plan.shift if S else 0, _lib.ptr(src), src.stride(0), C, red, _lib.ptr(ws), nws, _lib.stream()),
+                   "egnn_scatter_runs_f32")
+        ctx.plan, ctx.red, ctx.S, ctx.count, ctx.arg = plan, red, S, count, arg
+        if arg is None:
+            return out, None
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, g, _garg=None):
+        g = _rowmajor(g)
+        plan, C = ctx.plan, g.shape[1]
+        dsrc = torch.empty((ctx.S, C), dtype=torch.float32, device=g.device)
+        _lib.check(_lib.load().egnn_scatter_bwd_f32(_lib.ptr(dsrc), dsrc.stride(0), ctx.S, _lib.ptr(plan.rows), plan.n_rows, _lib.ptr(g),
+                                                    g.stride(0), C, ctx.red, _lib.ptr(ctx.count), _lib.ptr(ctx.arg), _lib.stream()),
+                   "egnn_scatter_bwd_f32")
+        return dsrc, None, None
+
+
+def scatter(src: Tensor, index, dim_size: int, reduce: str = "sum", plan: RowsPlan | None = None, return_arg: bool = False):
+    """``out[r] = reduce(src[p] for p with index[p] == r)`` -> [dim_size, ...]: ``torch_scatter.scatter(src, index, 0, dim_size=dim_size)``.
+    ``src`` float32 GPU [E, ...] (trailing dims are flattened for the kernel), ``index`` 1-D int64 [E] in any order, with repeats and
+    negative ids; ``reduce`` in sum | add | mean | max | min.  No float atomics: sum (and mean's sum) add in the run-sum's documented
+    order, so two calls are bit-equal; max / min are exact, a row no id names is 0 and ``arg`` (``return_arg=True``: ``(out, arg)``,
+    arg None for sum / mean) holds the smallest position attaining the extreme, E for such a row.  ``plan``: a ready ``rows_plan`` of
+    ``index`` over ``dim_size`` rows (``index`` itself may then be None) -- the plan a gather by the same ids used; without one the
+    host-checked plan of ``index`` is built (cached per index tensor).  First derivatives."""
+    if reduce not in _SCATTER_REDUCE:
+        raise ValueError(f"reduce must be one of {sorted(_SCATTER_REDUCE)}, got {reduce!r}")
+    src = _lib.real(src)
+    _lib.require_gpu(src, index if isinstance(index, Tensor) else None)
+    if src.dtype != torch.float32 or src.dim() < 1:
+        raise TypeError("scatter: `src` must be a float32 tensor [E, ...]")
+    if plan is None:
+        plan = rows_plan(index, dim_size)
+    elif plan.n_rows != int(dim_size):
+        raise ValueError(f"scatter: the plan was built for {plan.n_rows} rows, dim_size is {int(dim_size)}")
+    if plan.S != src.shape[0] or (isinstance(index, Tensor) and index.numel() != src.shape[0]):
+        raise ValueError(f"scatter: {src.shape[0]} rows of src, {plan.S} ids")
+    tail = tuple(src.shape[1:])
+    C = 1
+    for d in tail:
+        C *= d
+    if C == 0 or int(dim_size) == 0:
+        out = src.new_zeros((int(dim_size),) + tail)
+        return (out, None) if return_arg else out
+    out, arg = _Scatter.apply(src.reshape(src.shape[0], C), plan, _SCATTER_REDUCE[reduce])
+    out = out.view((plan.n_rows,) + tail)
+    if return_arg:
+        return out, (arg.view((plan.n_rows,) + tail) if arg is not None else None)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1032,12 +1190,12 @@ def linear_rows(x: Tensor, idx: Tensor, weight: Tensor, bias: Tensor | None = No
     ONCE per (x, idx) identity + version as tile-packed bf16 planes (6 bytes per element, held by a byte-bounded cache) and the forward /
     weight-gradient products run on the planes x planes forms.  Without the flag no plane image is ever built: activations under
     ``no_grad`` (requires_grad False as well) or RGCN's per-node-type calls take the gather-fused GEMM."""
-    summing = _check_duplicates(duplicates)
+    summing = isinstance(idx, RowsPlan) or _check_duplicates(duplicates)   # (a ready plan in place of the ids: nothing is built)
     _lib.require_gpu(x)
     plan = None
     if summing:
-        plan = rows_plan(idx, x.shape[0])
-        idx, plan = plan.idx, plan if plan.dups else None
+        plan = _plan_for(idx, x.shape[0], "linear_rows")
+        idx, plan = plan.idx, plan if plan.keys is not None else None
     return _LinearRows.apply(x, idx, weight, bias, getattr(x, "_egnn_tap", None) if torch.is_grad_enabled() else None, const_input, plan)
 
 

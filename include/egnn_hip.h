@@ -696,6 +696,49 @@ size_t egnn_rows_add_runs_ws_bytes(int64_t S, int64_t C);
 int egnn_rows_add_runs_f32(float* dst, int64_t ld_dst, int64_t n_rows, const uint64_t* keys_sorted, int64_t S, int shift,
                            const float* src, int64_t ld_src, int64_t C, int accumulate, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Aggregation by an UNSORTED index (csrc/scatter.hip): out[r, :] = reduce of src[p, :] over the positions p with index[p] == r --
+ * torch_scatter.scatter along dim 0, the aggregation step of a user-defined message-passing layer (nn.MessagePassing) -- and its
+ * backward.  No float atomics, no integer atomics.
+ *
+ * egnn_scatter_runs_f32   walks the sorted (row, position) keys of egnn_rows_plan_build_i64 (keys_sorted, S, shift as there).
+ *     src [S, ld_src], out [n_rows, ld_out], C columns; reduce: 0 sum, 1 mean, 2 max, 3 min (anything else: EGNN_EINVAL).  EVERY row
+ *     of out is written (out may be uninitialised: no memset needed).
+ *     count int32 [n_rows] (nullable; required for mean, else EGNN_EINVAL): the length of row r's run.
+ *     arg int64 [n_rows, C] contiguous (nullable; max / min only, else EGNN_EINVAL).
+ *     sum:  bit-equal to egnn_rows_add_runs_f32(accumulate = 0) on the same keys -- the same code runs -- so the order of the
+ *           additions is the one documented there, a function of (index, C) only.
+ *     mean: that sum divided by (float)count[r], one correctly rounded division per element; a row that no key names is 0.
+ *     max / min: exact.  arg[r, c] is the SMALLEST position p attaining the extreme of column c (ties are decided by edge order); a
+ *           row that no key names gets the value 0 and arg = S (torch_scatter's convention).  A run longer than
+ *           EGNN_ROWS_SUM_CHUNK is cut like the run-sum's, its chunks are folded by different lane groups into (value, position)
+ *           pairs in ws, and a second launch merges the pairs in ascending chunk order; a pair is replaced only by a strictly
+ *           better value, and where a chunk starts is read off the keys, so the result does not depend on the launch geometry.
+ *           NaN inputs: unspecified (a NaN never compares better, so what a column holding one returns depends on its position).
+ *     Lane groups as in the run-sum: 16 bytes per lane when C % 4 == 0, both pitches % 4 == 0 and out and src are 16-byte aligned;
+ *     a scalar path in the same entry point otherwise (any C, any pitch).
+ *     ws: egnn_scatter_runs_ws_bytes(S, C, reduce) bytes, 16-byte aligned (0 for S <= EGNN_ROWS_SUM_CHUNK: ws may be NULL); missing
+ *     or short: EGNN_EWORKSPACE, misaligned ws / keys / count / arg: EGNN_EALIGN.  Every check happens before the first launch.
+ *     S == 0: EGNN_OK; with a non-NULL out the n_rows rows and counts are zeroed and arg is filled with S = 0.
+ *     A position or row that does not fit S / n_rows (keys built for other operands) is skipped, never used as an address.
+ *
+ * egnn_scatter_bwd_f32    the backward in gather form: ONE pass over dsrc [S, ld_dsrc]; every element is written with a plain store (no
+ *     zero-fill needed, no atomics).  index int64 [S] holds row ids already wrapped; r = index[p] outside [0, n_rows) writes a zero
+ *     row and reads nothing.  g [n_rows, ld_g].
+ *       sum:  dsrc[p, c] = g[r, c];   mean: g[r, c] / (float)count[r];   max / min: arg[r, c] == p ? g[r, c] : 0
+ *     with count / arg as the forward wrote them (required for mean / max, min; else EGNN_EINVAL).  S == 0: EGNN_OK.
+ *
+ * egnn_rows_wrap_i64      wrapped[p] = idx[p] (+ n_rows when negative), or -1 when idx[p] is outside [-n_rows, n_rows): the row ids of
+ *     a plan whose range check is left to the device (no host read), in the form egnn_scatter_bwd_f32 takes.  S == 0: EGNN_OK.
+ * ---------------------------------------------------------------------------------------------- */
+int egnn_rows_wrap_i64(const int64_t* idx, int64_t S, int64_t n_rows, int64_t* wrapped, void* stream);
+size_t egnn_scatter_runs_ws_bytes(int64_t S, int64_t C, int reduce);
+int egnn_scatter_runs_f32(float* out, int64_t ld_out, int64_t n_rows, int32_t* count, int64_t* arg, const uint64_t* keys_sorted,
+                          int64_t S, int shift, const float* src, int64_t ld_src, int64_t C, int reduce, void* ws, size_t ws_bytes,
+                          void* stream);
+int egnn_scatter_bwd_f32(float* dsrc, int64_t ld_dsrc, int64_t S, const int64_t* index, int64_t n_rows, const float* g, int64_t ld_g,
+                         int64_t C, int reduce, const int32_t* count, const int64_t* arg, void* stream);
+
 /* FitNet (/root/reference/arxiv_pyg/criterion.py:24-36, ppi_pyg/criterion.py:21-33): loss[0] = mean over n * D of
  * (F.normalize(f) - F.normalize(t))^2, F.normalize(x) = x / max(||x||_2, eps); one wave per row, fixed-order sums.
  * bwd: df / dt (nullable) = g[0] * dloss/df, dloss/dt.  ws: egnn_feature_loss_ws_floats(n) floats. */
