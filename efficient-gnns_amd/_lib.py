@@ -173,6 +173,9 @@ SIGNATURES = {
     "egnn_scatter_runs_ws_bytes": (_sz, [_i64, _i64, _i32]),
     "egnn_scatter_runs_f32": (_i32, [_p, _i64, _i64, _p, _p, _p, _i64, _i32, _p, _i64, _i64, _i32, _p, _sz, _p]),
     "egnn_scatter_bwd_f32": (_i32, [_p, _i64, _i64, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _p]),
+    "egnn_scatter_softmax_ws_bytes": (_sz, [_i64, _i64]),
+    "egnn_scatter_softmax_fwd_f32": (_i32, [_p, _i64, _p, _p, _i64, _p, _i64, _i32, _p, _p, _i64, _i64, _f32, _i32, _p, _sz, _p]),
+    "egnn_scatter_softmax_bwd_f32": (_i32, [_p, _i64, _p, _i64, _p, _i64, _i32, _p, _p, _i64, _p, _i64, _i64, _i32, _p, _sz, _p]),
     "egnn_feature_loss_ws_floats": (_sz, [_i64]),
     "egnn_fitnet_fwd_f32": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _sz, _p]),
     "egnn_fitnet_bwd_f32": (_i32, [_p, _i64, _p, _i64, _i64, _i64, _f32, _p, _p, _i64, _p, _i64, _p]),

@@ -1,5 +1,7 @@
 """Drop-in shim for ``torch_scatter``'s reductions along dim 0 on ``efficient_gnns_amd.ops.scatter`` (csrc/scatter.hip): what a
-user-defined ``MessagePassing.aggregate`` calls.  ``src`` float32 on the GPU, ``index`` 1-D int64; no float atomics."""
+user-defined ``MessagePassing.aggregate`` calls -- and for its composite softmax functions on ``ops.scatter_softmax``
+(csrc/scatter_softmax.hip; also importable from ``torch_scatter.composite``).  ``src`` float32 on the GPU, ``index`` 1-D int64; no float
+atomics."""
 from efficient_gnns_amd import ops as _ops
 
 
@@ -41,3 +43,22 @@ def scatter_max(src, index, dim=-1, out=None, dim_size=None):
 
 def scatter_min(src, index, dim=-1, out=None, dim_size=None):
     return _ops.scatter(src, index, _checked(src, index, dim, out, dim_size), "min", return_arg=True)
+
+
+def _softmax(src, index, dim, dim_size, log):
+    """The composite functions on ``ops.scatter_softmax`` (csrc/scatter_softmax.hip; eps 0, as torch_scatter): inside a running
+    ``MessagePassing.propagate`` whose target-side endpoint tensor ``index`` is, the call's own plan is used."""
+    from efficient_gnns_amd.nn import running_plan
+    _checked(src, index, dim, None, 0)                                   # the shim's `dim` / `index` errors (no host read)
+    found = running_plan(index, dim_size, "dim_size")
+    if found is not None:
+        return _ops.scatter_softmax(src, index, found[1], plan=found[0], eps=0.0, log=log)
+    return _ops.scatter_softmax(src, index, _checked(src, index, dim, None, dim_size), eps=0.0, log=log)
+
+
+def scatter_softmax(src, index, dim=-1, dim_size=None):
+    return _softmax(src, index, dim, dim_size, False)
+
+
+def scatter_log_softmax(src, index, dim=-1, dim_size=None):
+    return _softmax(src, index, dim, dim_size, True)

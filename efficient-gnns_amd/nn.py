@@ -522,12 +522,28 @@ _MP_AGGRS = ("add", "sum", "mean", "max", "min")
 _MP_FLOWS = ("source_to_target", "target_to_source")
 _MP_SPECIAL = ("edge_index", "edge_index_i", "edge_index_j", "index", "size", "size_i", "size_j", "dim_size", "ptr", "adj_t")
 _MP_EMPTY = inspect.Parameter.empty
+_MP_RUNNING: list = []     # (the _Propagation, its target side) of every propagate call in progress, innermost last
+
+
+def running_plan(index, n=None, what: str = "num_nodes"):
+    """``(plan, node count)`` of the running ``propagate`` call whose TARGET-side endpoint tensor ``index`` is (identity, innermost call
+    first), None when there is none: how ``utils.softmax`` and the ``torch_scatter`` shim share the plan of the lift and the
+    aggregation.  A node count the call has not settled yet is taken from ``n`` (``num_nodes`` / ``dim_size``), else read off
+    ``index`` (one host read, as PyG)."""
+    for call, i in reversed(_MP_RUNNING):
+        if call.ends[i] is not None and index is call.ends[i]:
+            if n is not None:
+                call.see(i, n, what)
+            elif call.size[i] is None:
+                call.size[i] = int(index.max()) + 1 if index.numel() else 0
+            return call.plan(i), call.size[i]
+    return None
 
 
 class _Propagation:
     """One ``propagate`` call: the two endpoint id vectors (0: source side, 1: target side of ``edge_index``), the node counts seen so
     far, and AT MOST ONE deferred ``ops.rows_plan`` per endpoint, built when first asked for and shared by the lift (``x_j`` / ``x_i``),
-    the lift's backward and the aggregation."""
+    the lift's backward, a softmax over ``index`` inside ``message`` (``running_plan``) and the aggregation."""
 
     def __init__(self, ends, size, ptr=None, edge_index=None, adj_t=None):
         self.ends, self.size, self.ptr, self.edge_index, self.adj_t = ends, size, ptr, edge_index, adj_t
@@ -582,7 +598,9 @@ class MessagePassing(nn.Module):
 
     The lift is ``ops.take_rows`` and the aggregation ``ops.scatter``, both over ONE ``ops.rows_plan(check="deferred")`` per endpoint
     and call: no host read per fresh ``edge_index[:, mask]``; an id out of range is dropped and counted (``ops.rows_oob``), not
-    raised.  Under ``accel`` a lifted 2-D fp32 tensor is handed out as ``lazy.LazyRows``: ``self.lin(x_j)`` runs as the gather-fused
+    raised.  ``utils.softmax(alpha, index, ptr, size_i)`` on [E, heads] scores inside ``message`` (and the ``torch_scatter`` softmax
+    functions) finds the running call through ``running_plan`` and walks the target side's plan: no plan of its own, no host read.
+    Under ``accel`` a lifted 2-D fp32 tensor is handed out as ``lazy.LazyRows``: ``self.lin(x_j)`` runs as the gather-fused
     ``ops.linear_rows``.  GPU only, like every operator of the package."""
 
     def __init__(self, aggr: str = "add", flow: str = "source_to_target", node_dim: int = -2):
@@ -696,6 +714,7 @@ class MessagePassing(nn.Module):
             _lib.require_gpu(edge_index)
             call = _Propagation((edge_index[0], edge_index[1]), size, None, edge_index, None)
         outer, self._mp_call = self._mp_call, call
+        _MP_RUNNING.append((call, 1 if self.flow == "source_to_target" else 0))
         try:
             lifted: dict = {}
             msg_kwargs = self._mp_collect("message", call, kwargs, lifted)
@@ -703,6 +722,7 @@ class MessagePassing(nn.Module):
             out = self.aggregate(out, **self._mp_collect("aggregate", call, kwargs, lifted))
             return self.update(out, **self._mp_collect("update", call, kwargs, lifted))
         finally:
+            _MP_RUNNING.pop()
             self._mp_call = outer
 
     def __repr__(self):

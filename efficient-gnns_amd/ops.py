@@ -734,6 +734,79 @@ def scatter(src: Tensor, index, dim_size: int, reduce: str = "sum", plan: RowsPl
 
 
 # ------------------------------------------------------------------------------------------------
+# softmax over the groups of an unsorted index (csrc/scatter_softmax.hip): torch_scatter.scatter_softmax along dim 0, the attention
+# step of a user-defined conv between the lift and the aggregation
+# ------------------------------------------------------------------------------------------------
+class _ScatterSoftmax(torch.autograd.Function):
+    """out[p] = softmax (log: log-softmax) of src[p] among the positions that share index[p] (egnn_scatter_softmax_fwd_f32 over the
+    plan's sorted keys); the backward is one more run walk and a gather (egnn_scatter_softmax_bwd_f32) into an uninitialised
+    gradient.  Saves ``out`` and the plan.  First derivatives only."""
+
+    @staticmethod
+    def forward(ctx, src, plan, eps, log):
+        src = _rowmajor(src)
+        lib = _lib.load()
+        S, C = src.shape
+        n, dev = plan.n_rows, src.device
+        out = torch.empty((S, C), dtype=torch.float32, device=dev)
+        stats = torch.empty((2, n, C), dtype=torch.float32, device=dev)
+        nws = lib.egnn_scatter_softmax_ws_bytes(S, C)
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+        _lib.check(lib.egnn_scatter_softmax_fwd_f32(_lib.ptr(out), out.stride(0), _lib.ptr(stats[0]), _lib.ptr(stats[1]), n,
+                                                    _lib.ptr(plan.all_keys), S, plan.shift, _lib.ptr(plan.rows), _lib.ptr(src), src.stride(0), C,
+                                                    float(eps), int(log), _lib.ptr(ws), nws, _lib.stream()), "egnn_scatter_softmax_fwd_f32")
+        ctx.plan, ctx.log = plan, int(log)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _rowmajor(g)
+        (out,) = ctx.saved_tensors
+        plan = ctx.plan
+        lib = _lib.load()
+        S, C = out.shape
+        dsrc = torch.empty((S, C), dtype=torch.float32, device=g.device)
+        dot = torch.empty((plan.n_rows, C), dtype=torch.float32, device=g.device)
+        nws = lib.egnn_scatter_softmax_ws_bytes(S, C)
+        ws = torch.empty(nws, dtype=torch.uint8, device=g.device) if nws else None
+        _lib.check(lib.egnn_scatter_softmax_bwd_f32(_lib.ptr(dsrc), dsrc.stride(0), _lib.ptr(dot), plan.n_rows, _lib.ptr(plan.all_keys), S,
+                                                    plan.shift, _lib.ptr(plan.rows), _lib.ptr(out), out.stride(0), _lib.ptr(g), g.stride(0), C,
+                                                    ctx.log, _lib.ptr(ws), nws, _lib.stream()), "egnn_scatter_softmax_bwd_f32")
+        return dsrc, None, None, None
+
+
+def scatter_softmax(src: Tensor, index, dim_size: int, plan: RowsPlan | None = None, eps: float = 0.0, log: bool = False) -> Tensor:
+    """``out[p] = exp(src[p] - M[r]) / (Z[r] + eps)`` with ``r = index[p]``, ``M[r]`` the maximum and ``Z[r] = sum exp(src - M[r])`` over
+    the positions that name ``r`` (``log=True``: ``(src[p] - M[r]) - log(Z[r] + eps)``): ``torch_scatter.scatter_softmax`` /
+    ``scatter_log_softmax`` along dim 0 (``eps=0``) and ``torch_geometric.utils.softmax`` (``eps=1e-16``).  ``src`` float32 GPU
+    [E, ...] (trailing dims -- the heads -- are flattened for the kernel; the result has the shape of ``src``), ``index`` 1-D int64
+    [E] in any order, with repeats and negative ids.  No float atomics: the sums are added in the kernel's documented order, so two
+    calls are bit-equal and the columns are independent of one another.  ``plan`` as in ``scatter``: a ready ``rows_plan`` of
+    ``index`` over ``dim_size`` rows (``index`` itself may then be None; an id that a deferred plan dropped gets 0 and no gradient);
+    without one the host-checked plan of ``index`` is built (cached per index tensor).  First derivatives."""
+    if plan is not None and plan.n_rows != int(dim_size):
+        raise ValueError(f"scatter_softmax: the plan was built for {plan.n_rows} rows, dim_size is {int(dim_size)}")
+    src = _lib.real(src)
+    _lib.require_gpu(src, index if isinstance(index, Tensor) else None)
+    if src.dtype != torch.float32 or src.dim() < 1:
+        raise TypeError("scatter_softmax: `src` must be a float32 tensor [E, ...]")
+    if plan is None and not isinstance(index, Tensor):
+        raise TypeError("scatter_softmax: `index` must be a 1-D int64 tensor when no plan is given")
+    ids = plan.S if plan is not None else index.numel()
+    if ids != src.shape[0] or (isinstance(index, Tensor) and index.numel() != src.shape[0]):
+        raise ValueError(f"scatter_softmax: {src.shape[0]} rows of src, {ids} ids")
+    C = 1
+    for d in src.shape[1:]:
+        C *= d
+    if C == 0 or src.shape[0] == 0 or int(dim_size) == 0:      # nothing to normalise: no plan, no launch
+        return torch.zeros_like(src)
+    if plan is None:
+        plan = rows_plan(index, dim_size)
+    return _ScatterSoftmax.apply(src.reshape(src.shape[0], C), plan, float(eps), bool(log)).view(src.shape)
+
+
+# ------------------------------------------------------------------------------------------------
 # dense GEMM (fp32 MFMA)
 # ------------------------------------------------------------------------------------------------
 def gemm_backend() -> str:

@@ -30,11 +30,39 @@ def subgraph(subset: Tensor, edge_index: Tensor, edge_attr=None, relabel_nodes: 
     return ei, ea
 
 
-def softmax(src: Tensor, index: Tensor, ptr=None, num_nodes: int | None = None) -> Tensor:
-    """Segment softmax over entries grouped by ``index``: exp(src - max) / (sum + 1e-16)."""
-    from . import _lib
-    from .ops_edge import segment_softmax
-    return segment_softmax(_lib.real(src), index, num_nodes)
+def softmax(src: Tensor, index: Tensor | None = None, ptr=None, num_nodes: int | None = None, dim: int = 0) -> Tensor:
+    """Softmax over entries grouped by ``index`` (any order): exp(src - max) / (sum + 1e-16), per trailing element.
+
+    A 1-D ``src`` with an ``index`` takes the sorted-segment path of the LSP loss (``ops_edge.segment_softmax``).  ``src`` of two or
+    more dimensions -- the [E, heads] scores of an attention conv -- goes to ``ops.scatter_softmax`` over the run keys of a
+    ``rows_plan``: the running ``propagate`` call's own plan when ``index`` is that call's target-side endpoint tensor (the ``index``
+    that ``message`` receives), else a deferred plan over ``num_nodes`` rows (no host read), else ``num_nodes = index.max() + 1`` (one
+    host read, as PyG).  ``index=None`` with ``ptr``: the groups are the consecutive ranges ``ptr[i]:ptr[i+1]``.  The node axis is 0."""
+    from . import _lib, ops
+    src = _lib.real(src)
+    if dim not in (0, -src.dim()):
+        raise NotImplementedError(f"softmax: `dim` must be 0 (or {-src.dim()}): the entries are grouped along the first axis, got {dim}")
+    if index is None:
+        if ptr is None:
+            raise ValueError("softmax: one of `index` and `ptr` is needed")
+        _lib.require_gpu(src, ptr)
+        counts = ptr[1:] - ptr[:-1]
+        index = torch.repeat_interleave(torch.arange(counts.numel(), dtype=torch.int64, device=ptr.device), counts, output_size=src.shape[0])
+        if num_nodes is None:
+            num_nodes = counts.numel()
+    if src.dim() == 1:
+        from .ops_edge import segment_softmax
+        return segment_softmax(src, index, num_nodes)
+    _lib.require_gpu(src, index)
+    from .nn import running_plan
+    found = running_plan(index, num_nodes)
+    if found is not None:
+        plan, num_nodes = found
+    else:
+        if num_nodes is None:
+            num_nodes = int(index.max()) + 1 if index.numel() else 0
+        plan = ops.rows_plan(index.contiguous(), num_nodes, check="deferred") if num_nodes > 0 else None
+    return ops.scatter_softmax(src, index, num_nodes, plan=plan, eps=1e-16)
 
 
 def dgl_bidirected_with_self_loops(adj_t):

@@ -739,6 +739,56 @@ int egnn_scatter_runs_f32(float* out, int64_t ld_out, int64_t n_rows, int32_t* c
 int egnn_scatter_bwd_f32(float* dsrc, int64_t ld_dsrc, int64_t S, const int64_t* index, int64_t n_rows, const float* g, int64_t ld_g,
                          int64_t C, int reduce, const int32_t* count, const int64_t* arg, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Softmax over the groups of an UNSORTED index (csrc/scatter_softmax.hip): torch_scatter.scatter_softmax / scatter_log_softmax along
+ * dim 0 and torch_geometric.utils.softmax on multi-head scores [E, H] -- the step between the lift and the aggregation of an attention
+ * conv -- and its backward.  No float atomics, no integer atomics; first derivatives only.
+ *
+ * Operands of both calls: keys_sorted, S, shift as egnn_rows_plan_build_i64 produced them; rows int64 [S], the row ids already
+ * wrapped, -1 (anything outside [0, n_rows)) for a dropped id -- the form egnn_scatter_bwd_f32 takes; C >= 1 columns (the flattened
+ * trailing shape: usually the head count); form: 0 softmax, 1 log-softmax (anything else: EGNN_EINVAL).
+ *
+ * egnn_scatter_softmax_fwd_f32   src [S, ld_src], out [S, ld_out].  With r = rows[p] and the max and the sum over the positions q of
+ *     row r's run,  M[r, c] = max_q src[q, c],  Z[r, c] = sum_q exp(src[q, c] - M[r, c]):
+ *       form 0:  out[p, c] = exp(src[p, c] - M[r, c]) / (Z[r, c] + eps)        one true division per element
+ *       form 1:  out[p, c] = (src[p, c] - M[r, c]) - log(Z[r, c] + eps)
+ *     (PyG passes eps = 1e-16, torch_scatter 0).  A run walk leaves M and Z in row_max / row_den, float [n_rows, C] contiguous, which
+ *     the caller provides and need not initialise: EVERY row is written, a row that no key names gets 0 in both.  A gather over
+ *     [S, C] then writes EVERY element of out with a plain store; a position with rows[p] outside [0, n_rows) gets 0 in both forms.
+ *     ORDER OF THE ADDITIONS, per column, a function of (index, C) only: a run is cut from its head into chunks of
+ *     K = EGNN_ROWS_SUM_CHUNK positions exactly as egnn_rows_add_runs_f32 cuts it (read off the keys, never off the launch
+ *     geometry).  Chunk j yields m_j (its exact maximum) and z_j = sum of e_o = exp(src - m_j) over its offsets o = 0 .. K - 1 in
+ *     this order: for l = 0 .. 15,  s_l = ((e_l + e_(l+16)) + e_(l+32)) + ... + e_(l+112)  (offsets past the chunk's end left out, an
+ *     empty s_l is 0), then
+ *       z_j = (((s_0 + s_8) + (s_4 + s_12)) + ((s_2 + s_10) + (s_6 + s_14))) + (((s_1 + s_9) + (s_5 + s_13)) + ((s_3 + s_11) + (s_7 + s_15))).
+ *     A run of one chunk: M = m_0, Z = z_0.  A longer run parks its pairs in ws and a second launch merges them in ascending chunk
+ *     order:  M = max_j m_j,  Z = ((z_0 exp(m_0 - M) + z_1 exp(m_1 - M)) + ...).  The bits of out are therefore a function of
+ *     (index, C, values, eps, form) only -- not of a pitch, an alignment or the addressing path (16 bytes per lane when C % 4 == 0,
+ *     all pitches % 4 == 0 and all float operands are 16-byte aligned; a scalar path in the same entry point otherwise) -- two calls
+ *     are bit-equal, and column c of a [S, C] call equals the [S, 1] call on that column bit for bit.
+ *     Lanes run along positions: one 16-lane group per chunk, lane l reading the chunk's offsets l, l + 16, ... (csrc/scatter_softmax.hip).
+ *     UNSPECIFIED: NaN, +inf, and a run whose values are all -inf.
+ *
+ * egnn_scatter_softmax_bwd_f32   out as the forward wrote it, g the gradient of out, dsrc [S, ld_dsrc].  One more run walk, with the
+ *     same cut and the same order of additions, leaves row_dot float [n_rows, C] contiguous (every row written, 0 for a row that
+ *     no key names), and a gather writes EVERY element of dsrc (0 for a dropped position):
+ *       form 0:  row_dot[r, c] = sum_q out[q, c] * g[q, c]  (products formed in registers),  dsrc[p, c] = out[p, c] * (g[p, c] - row_dot[r, c])
+ *       form 1:  row_dot[r, c] = sum_q g[q, c],                                              dsrc[p, c] = g[p, c] - exp(out[p, c]) * row_dot[r, c]
+ *
+ * Both: S and n_rows < 2^31 - 1, C >= 1, every pitch >= C, shift = the number of bits of S - 1 (at least 1), form 0 | 1, no NULL
+ *     operand (else EGNN_EINVAL).  ws: egnn_scatter_softmax_ws_bytes(S, C) bytes, 16-byte aligned (0 for S <= EGNN_ROWS_SUM_CHUNK: ws
+ *     may be NULL); missing or short: EGNN_EWORKSPACE; misaligned ws / keys / rows / float operands: EGNN_EALIGN.  Every check happens
+ *     before the first launch.  S == 0: EGNN_OK; the per-row buffers are zero-filled when they are non-NULL (everything else may be NULL).
+ *     A key whose position or row does not fit S / n_rows (keys built for other operands) is skipped, never used as an address.
+ * ---------------------------------------------------------------------------------------------- */
+size_t egnn_scatter_softmax_ws_bytes(int64_t S, int64_t C);
+int egnn_scatter_softmax_fwd_f32(float* out, int64_t ld_out, float* row_max, float* row_den, int64_t n_rows, const uint64_t* keys_sorted,
+                                 int64_t S, int shift, const int64_t* rows, const float* src, int64_t ld_src, int64_t C, float eps, int form,
+                                 void* ws, size_t ws_bytes, void* stream);
+int egnn_scatter_softmax_bwd_f32(float* dsrc, int64_t ld_dsrc, float* row_dot, int64_t n_rows, const uint64_t* keys_sorted, int64_t S,
+                                 int shift, const int64_t* rows, const float* out, int64_t ld_out, const float* g, int64_t ld_g, int64_t C,
+                                 int form, void* ws, size_t ws_bytes, void* stream);
+
 /* FitNet (/root/reference/arxiv_pyg/criterion.py:24-36, ppi_pyg/criterion.py:21-33): loss[0] = mean over n * D of
  * (F.normalize(f) - F.normalize(t))^2, F.normalize(x) = x / max(||x||_2, eps); one wave per row, fixed-order sums.
  * bwd: df / dt (nullable) = g[0] * dloss/df, dloss/dt.  ws: egnn_feature_loss_ws_floats(n) floats. */
