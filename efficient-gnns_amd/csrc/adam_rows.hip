@@ -18,29 +18,26 @@
 // the bits they use, and the lane group at the first key of a row's run walks the run forward: the row's gradient rows are added in
 // registers in ascending entry order, scaled once, and the row takes ONE step through the same device functions.  Only the head's
 // group touches the row, so runs that cross a workgroup boundary need no hand-over.
-#include "rows_keys.h"
+#include "rows_runs.h"
 
 namespace {
 
 using egnn_rows::NO_KEY;               // an entry of another type or outside the table: sorts behind every row
+using egnn_rows::THREADS;
 using egnn_rows::align_up;
 using egnn_rows::bits_for;
+using egnn_rows::blocks_for;
+using egnn_rows::is_run_head;
 using egnn_rows::kAlign;
 using egnn_rows::make_key;
 using egnn_rows::sort_keys;
 using egnn_rows::sort_keys_temp;
 
-constexpr int THREADS = 256;
 constexpr int MAX_TABLES = 8;
 constexpr int RING = EGNN_ADAM_MAX_LAG;
 static_assert((RING & (RING - 1)) == 0 && 2 * RING <= THREADS, "the ring is indexed with tau & (RING - 1) and staged by one workgroup pass");
 
 static int lanes_lg(int64_t D) { return egnn_rows::lanes_lg(D / 4); }
-
-static int64_t blocks_for(int64_t n, int lg) {
-  const int64_t rows_per_block = THREADS >> lg;
-  return (n + rows_per_block - 1) / rows_per_block;
-}
 
 // ONE Adam step of one element, in torch.optim.Adam's single-tensor order (no fused multiply-add: the library is built with
 // -ffp-contract=off).  g = 0 is the replayed step of a row outside the batch.
@@ -194,7 +191,7 @@ __global__ __launch_bounds__(THREADS) void adam_rows_step_sum_kernel(egnn_adam_r
   const uint64_t key = sorted[j];
   if (key == NO_KEY) return;
   const uint64_t r = key >> shift;
-  if (j > 0 && (sorted[j - 1] >> shift) == r) return;          // not the head of its run
+  if (!is_run_head(sorted, shift, j, r)) return;
   int win = 0;
   if (sub == 0) {
     int old = atomicCAS(a.last + r, a.step - 1, a.step);

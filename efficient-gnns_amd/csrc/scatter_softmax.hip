@@ -14,11 +14,10 @@
 //
 // LANE MAPPING.  C is the head count (1 - 16), so the lanes run along POSITIONS, not along columns.  One wave takes a window of 64
 // consecutive sorted positions; lane i decides whether position (window + i) starts a chunk, the wave ballots those flags, and its
-// four 16-lane groups take the window's chunk starts four at a time, in ascending position.  A run is cut from its head into chunks
-// of EGNN_ROWS_SUM_CHUNK = 128 positions exactly as the run-sum cuts it (whether a position starts a chunk is read off the keys: the
-// run's head is found by a binary search, and only for positions whose key CHUNK places earlier names the same row), and no lane
-// group walks more than one chunk: lane l of the group reads the chunk's offsets l, l + 16, ..., l + 112 (eight loads in flight per
-// column), so a hub of degree 13 000 is ~100 groups of 8 steps each, and a run of the common degrees is one group's single step.
+// four 16-lane groups take the window's chunk starts four at a time, in ascending position.  The cut of a run into chunks of
+// EGNN_ROWS_SUM_CHUNK = 128 positions is the one of rows_runs.h (chunk_start), and no lane group walks more than one chunk: lane l of
+// the group reads the chunk's offsets l, l + 16, ..., l + 112 (eight loads in flight per column), so a hub of degree 13 000 is ~100
+// groups of 8 steps each, and a run of the common degrees is one group's single step.
 // Columns are an outer loop of the group (four at a time, 16 bytes per lane, when C % 4 == 0 and every pitch and pointer allows it;
 // one at a time otherwise): each column's arithmetic is the same scalar sequence on either path.
 //
@@ -28,52 +27,27 @@
 // and the 16 lane sums meet in the xor butterfly of egnn_group_sum<16> (an empty lane adds 0):
 //     t = (((s_0 + s_8) + (s_4 + s_12)) + ((s_2 + s_10) + (s_6 + s_14))) + (((s_1 + s_9) + (s_5 + s_13)) + ((s_3 + s_11) + (s_7 + s_15)))
 // (every lane forms the same tree with commuted operands, hence the same bits).  The chunk maximum m_j is exact.  A run of one chunk
-// goes straight to the row buffers.  The chunks of a longer run park their pairs (m_j, z_j) -- or their sums -- in the workspace (slot
-// 2 (q / CHUNK) + (q is not its run's head) for the chunk starting at sorted position q, as in rows_sum.hip), and a second launch
-// merges them in ascending chunk order:  M = max_j m_j,  Z = ((z_0 e^(m_0 - M) + z_1 e^(m_1 - M)) + ...)  |  T = ((t_0 + t_1) + ...).
+// goes straight to the row buffers.  The chunks of a longer run park their pairs (m_j, z_j) -- or their sums -- in the workspace (the
+// slot rule of rows_runs.h), and a second launch merges them in ascending chunk order:
+//     M = max_j m_j,  Z = ((z_0 e^(m_0 - M) + z_1 e^(m_1 - M)) + ...)  |  T = ((t_0 + t_1) + ...).
 // Nothing above depends on the launch geometry, a pitch or the addressing path: the bits of out are a function of
 // (index, C, values, eps, form) only, and column c of a [S, C] call equals the [S, 1] call on that column.
 //
 // A key whose position or row does not fit S / n_rows (keys built for other operands) is skipped and never used as an address.
 // UNSPECIFIED inputs: NaN, +inf, and a run whose values are all -inf.
-#include "rows_keys.h"
+#include "rows_runs.h"
 
 namespace {
 
 using namespace egnn_rows;
 
-constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / EGNN_WAVE;
-constexpr int64_t CHUNK = EGNN_ROWS_SUM_CHUNK;
-constexpr int GL = 16;                        // lanes of the group that walks one chunk
+constexpr int LG_ONE = 0, LG_WAVE = 6;        // log2 of the lanes per item: one thread, one wave
+constexpr int GL = 16;                       // lanes of the group that walks one chunk
 constexpr int STEPS = (int)(CHUNK / GL);      // positions per lane
 static_assert(CHUNK % GL == 0 && EGNN_WAVE % GL == 0, "a chunk is a whole number of group steps");
 enum { SOFTMAX = 0, LOG_SOFTMAX = 1 };
 enum { STATS = 0, DOT = 1, SUM = 2 };        // what the walk folds: (max, sum of exp) of a | sum of a * b | sum of a
-
-template <int W> struct Vec;
-template <> struct Vec<1> { using type = float; };
-template <> struct Vec<4> { using type = float4; };
-
-template <int W> __device__ __forceinline__ void load_w(const float* p, float (&v)[W]) {
-  const typename Vec<W>::type t = *reinterpret_cast<const typename Vec<W>::type*>(p);
-  __builtin_memcpy(v, &t, sizeof(t));
-}
-template <int W> __device__ __forceinline__ void store_w(float* p, const float (&v)[W]) {
-  typename Vec<W>::type t;
-  __builtin_memcpy(&t, v, sizeof(t));
-  *reinterpret_cast<typename Vec<W>::type*>(p) = t;
-}
-
-// first position in [lo, hi) whose key is >= key (hi when there is none)
-__device__ __forceinline__ int64_t lower_bound(const uint64_t* __restrict__ sorted, int64_t lo, int64_t hi, uint64_t key) {
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (sorted[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ float group_max(float v) {
 #pragma unroll
@@ -81,15 +55,11 @@ __device__ __forceinline__ float group_max(float v) {
   return v;
 }
 
-__device__ __forceinline__ int64_t part_slot(int64_t q, bool is_head) { return 2 * (q / CHUNK) + (is_head ? 0 : 1); }
-
 // rows that no key names: 0 in every statistic (one thread per row)
 __global__ __launch_bounds__(THREADS) void ssm_absent_kernel(float* __restrict__ row_a, float* __restrict__ row_b, int64_t n_rows,
                                                              const uint64_t* __restrict__ sorted, int64_t S, int shift, int64_t C) {
   const int64_t row = (int64_t)blockIdx.x * THREADS + threadIdx.x;
-  if (row >= n_rows) return;
-  const int64_t q = lower_bound(sorted, 0, S, (uint64_t)row << shift);
-  if (q < S && (sorted[q] >> shift) == (uint64_t)row) return;
+  if (row >= n_rows || row_has_run(sorted, S, shift, row)) return;
   for (int64_t c = 0; c < C; ++c) {
     row_a[row * C + c] = 0.f;
     if (row_b != nullptr) row_b[row * C + c] = 0.f;
@@ -103,18 +73,17 @@ __device__ __forceinline__ void walk_chunk(int64_t j0, bool head, int sub, float
                                            int64_t lda, const float* __restrict__ xb, int64_t ldb, int64_t C, float* __restrict__ part_a,
                                            float* __restrict__ part_b, int64_t ldp) {
   const uint64_t r = sorted[j0] >> shift;
-  const bool long_run = !head || (j0 + CHUNK < S && (sorted[j0 + CHUNK] >> shift) == r);
+  const bool long_run = chunk_is_long(sorted, S, shift, j0, head, r);
   if (long_run && part_a == nullptr) return;                           // (the entry points refuse this: S > CHUNK without a workspace)
-  const int64_t limit = j0 + CHUNK < S ? j0 + CHUNK : S;
-  const uint64_t mask = (uint64_t(1) << shift) - 1;
+  const int64_t limit = chunk_limit(j0, S);
   int64_t p[STEPS];
   bool ok[STEPS];
 #pragma unroll
   for (int u = 0; u < STEPS; ++u) {
     const int64_t q = j0 + sub + GL * u;
     const uint64_t k = q < limit ? sorted[q] : NO_KEY;
-    ok[u] = (k >> shift) == r && (k & mask) < (uint64_t)S;              // a position outside [0, S) is never used as an address
-    p[u] = (int64_t)(k & mask);
+    ok[u] = key_usable(k, r, shift, S);
+    p[u] = (int64_t)key_pos(k, shift);
   }
   float* out_a = long_run ? part_a + part_slot(j0, head) * ldp : row_a + (int64_t)r * C;
   float* out_b = nullptr;
@@ -180,22 +149,10 @@ __global__ __launch_bounds__(THREADS) void ssm_walk_kernel(float* __restrict__ r
                                                            int64_t ldp) {
   const int lane = egnn_lane();
   const int64_t base = ((int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6)) * EGNN_WAVE;
-  const int64_t j = base + lane;
-  bool start = false, head = false;
-  if (j < S) {
-    const uint64_t key = sorted[j];
-    const uint64_t r = key >> shift;
-    if (key != NO_KEY && r < (uint64_t)n_rows) {
-      head = j == 0 || (sorted[j - 1] >> shift) != r;
-      start = head;
-      if (!head && j >= CHUNK && (sorted[j - CHUNK] >> shift) == r) {   // (otherwise: inside its run's first chunk)
-        const int64_t h = lower_bound(sorted, 0, j - CHUNK + 1, r << shift);   // the run's head
-        start = (j - h) % CHUNK == 0;
-      }
-    }
-  }
-  unsigned long long starts = __ballot(start);
-  const unsigned long long heads = __ballot(head);
+  int flags = 0;                                                       // 1: starts a chunk, 2: and is its run's head
+  chunk_start(sorted, S, shift, n_rows, base + lane, [&flags](bool head, uint64_t) { flags = head ? 3 : 1; });
+  unsigned long long starts = __ballot(flags & 1);
+  const unsigned long long heads = __ballot(flags & 2);
   const int grp = lane / GL, sub = lane % GL;
   while (starts != 0) {
     int mine = -1;
@@ -219,22 +176,10 @@ __global__ __launch_bounds__(THREADS) void ssm_parts_kernel(float* __restrict__ 
                                                             const float* __restrict__ part_a, const float* __restrict__ part_b,
                                                             int64_t ldp) {
   const int lane = egnn_lane();
-  const int64_t base = ((int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6)) * CHUNK;   // (base >= S: the loop below is empty)
-  int64_t found = -1;
-  for (int64_t j = base + lane; j < base + CHUNK && j + CHUNK < S; j += EGNN_WAVE) {
-    const uint64_t key = sorted[j];
-    const uint64_t r = key >> shift;
-    if (key != NO_KEY && r < (uint64_t)n_rows && (j == 0 || (sorted[j - 1] >> shift) != r) && (sorted[j + CHUNK] >> shift) == r) found = j;
-  }
-#pragma unroll
-  for (int o = EGNN_WAVE / 2; o > 0; o >>= 1) {
-    const int64_t other = __shfl_xor(found, o);
-    found = other > found ? other : found;
-  }
+  const int64_t found = long_run_head(sorted, S, shift, n_rows, ((int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6)) * CHUNK, lane, LG_WAVE);
   if (found < 0) return;
-  const uint64_t r = sorted[found] >> shift;
-  const int64_t end = lower_bound(sorted, found + CHUNK + 1, S, (r + 1) << shift);
-  const int64_t chunks = (end - found + CHUNK - 1) / CHUNK;
+  uint64_t r;
+  const int64_t chunks = run_chunks(sorted, S, shift, found, r);
   const int64_t s0 = part_slot(found, true);
   for (int64_t c = lane; c < C; c += EGNN_WAVE) {
     if (MODE == STATS) {
@@ -311,11 +256,6 @@ __global__ __launch_bounds__(THREADS) void ssm_bwd_gather_kernel(float* __restri
   store_w<W>(dsrc + p * ldd + c, v);
 }
 
-int64_t blocks_of(int64_t n, int64_t per_block) { return (n + per_block - 1) / per_block; }
-int64_t part_pitch(int64_t C) { return (C + 3) / 4 * 4; }
-int64_t part_slots(int64_t S) { return 2 * ((S + CHUNK - 1) / CHUNK); }
-
-bool sizes_ok(int64_t S, int64_t n_rows) { return S >= 0 && S < 0x7fffffffLL && n_rows >= 0 && n_rows < 0x7fffffffLL; }
 bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // absent rows, pass 1 and (S > CHUNK) pass 2 of one walk
@@ -325,14 +265,23 @@ void launch_walk(float* row_a, float* row_b, int64_t n_rows, const uint64_t* sor
   const int64_t ldp = part_pitch(C);
   float* part_a = S > CHUNK ? (float*)ws : nullptr;
   float* part_b = S > CHUNK && MODE == STATS ? part_a + part_slots(S) * ldp : nullptr;
-  hipLaunchKernelGGL(ssm_absent_kernel, dim3((unsigned)blocks_of(n_rows, THREADS)), dim3(THREADS), 0, st, row_a, row_b, n_rows, sorted, S, shift,
+  hipLaunchKernelGGL(ssm_absent_kernel, dim3((unsigned)blocks_for(n_rows, LG_ONE)), dim3(THREADS), 0, st, row_a, row_b, n_rows, sorted, S, shift,
                      C);
   if (S == 0) return;
-  hipLaunchKernelGGL((ssm_walk_kernel<W, MODE>), dim3((unsigned)blocks_of(S, THREADS)), dim3(THREADS), 0, st, row_a, row_b, n_rows, sorted, S,
+  hipLaunchKernelGGL((ssm_walk_kernel<W, MODE>), dim3((unsigned)blocks_for(S, LG_ONE)), dim3(THREADS), 0, st, row_a, row_b, n_rows, sorted, S,
                      shift, xa, lda, xb, ldb, C, part_a, part_b, ldp);
   if (S > CHUNK)
-    hipLaunchKernelGGL((ssm_parts_kernel<MODE>), dim3((unsigned)blocks_of((S + CHUNK - 1) / CHUNK, WAVES)), dim3(THREADS), 0, st, row_a, row_b,
+    hipLaunchKernelGGL((ssm_parts_kernel<MODE>), dim3((unsigned)blocks_for(part_slots(S) / 2, LG_WAVE)), dim3(THREADS), 0, st, row_a, row_b,
                        n_rows, sorted, S, shift, C, (const float*)part_a, (const float*)part_b, ldp);
+}
+
+// launch(W, FORM), both integral constants: a launch list names its arguments once for 16-byte / scalar x softmax / log-softmax
+template <class L>
+void dispatch_w_form(bool vec4, int form, L&& launch) {
+  dispatch_w(vec4, [&](auto w) {
+    if (form == SOFTMAX) launch(w, std::integral_constant<int, SOFTMAX>{});
+    else launch(w, std::integral_constant<int, LOG_SOFTMAX>{});
+  });
 }
 
 // the checks both directions share, in the order the header documents; OK_EMPTY: S == 0 and nothing more to check
@@ -372,25 +321,14 @@ extern "C" int egnn_scatter_softmax_fwd_f32(float* out, int64_t ld_out, float* r
   if (!aligned(out, 4) || !aligned(src, 4)) return EGNN_EALIGN;
   const bool vec4 = C % 4 == 0 && ld_out % 4 == 0 && ld_src % 4 == 0 && egnn_aligned16(out) && egnn_aligned16(src) &&
                     egnn_aligned16(row_max) && egnn_aligned16(row_den);
-  const unsigned blocks = (unsigned)blocks_of(S * (C / (vec4 ? 4 : 1)), THREADS);
-  EGNN_CHECK_ARG(blocks_of(S * (C / (vec4 ? 4 : 1)), THREADS) < 0x7fffffffLL);
-  if (vec4) {
-    launch_walk<4, STATS>(row_max, row_den, n_rows, keys_sorted, S, shift, src, ld_src, nullptr, 0, C, ws, st);
-    if (form == SOFTMAX)
-      hipLaunchKernelGGL((ssm_fwd_gather_kernel<4, SOFTMAX>), dim3(blocks), dim3(THREADS), 0, st, out, ld_out, src, ld_src, rows, S, n_rows, C,
-                         (const float*)row_max, (const float*)row_den, eps);
-    else
-      hipLaunchKernelGGL((ssm_fwd_gather_kernel<4, LOG_SOFTMAX>), dim3(blocks), dim3(THREADS), 0, st, out, ld_out, src, ld_src, rows, S, n_rows,
-                         C, (const float*)row_max, (const float*)row_den, eps);
-  } else {
-    launch_walk<1, STATS>(row_max, row_den, n_rows, keys_sorted, S, shift, src, ld_src, nullptr, 0, C, ws, st);
-    if (form == SOFTMAX)
-      hipLaunchKernelGGL((ssm_fwd_gather_kernel<1, SOFTMAX>), dim3(blocks), dim3(THREADS), 0, st, out, ld_out, src, ld_src, rows, S, n_rows, C,
-                         (const float*)row_max, (const float*)row_den, eps);
-    else
-      hipLaunchKernelGGL((ssm_fwd_gather_kernel<1, LOG_SOFTMAX>), dim3(blocks), dim3(THREADS), 0, st, out, ld_out, src, ld_src, rows, S, n_rows,
-                         C, (const float*)row_max, (const float*)row_den, eps);
-  }
+  const int64_t blocks = blocks_for(S * (C / (vec4 ? 4 : 1)), LG_ONE);
+  EGNN_CHECK_ARG(blocks < 0x7fffffffLL);
+  dispatch_w_form(vec4, form, [&](auto w, auto f) {
+    constexpr int W = decltype(w)::value, FORM = decltype(f)::value;
+    launch_walk<W, STATS>(row_max, row_den, n_rows, keys_sorted, S, shift, src, ld_src, nullptr, 0, C, ws, st);
+    hipLaunchKernelGGL((ssm_fwd_gather_kernel<W, FORM>), dim3((unsigned)blocks), dim3(THREADS), 0, st, out, ld_out, src, ld_src, rows, S, n_rows, C,
+                       (const float*)row_max, (const float*)row_den, eps);
+  });
   return egnn_launch_status();
 }
 
@@ -411,28 +349,14 @@ extern "C" int egnn_scatter_softmax_bwd_f32(float* dsrc, int64_t ld_dsrc, float*
   if (!aligned(dsrc, 4) || !aligned(out, 4) || !aligned(g, 4)) return EGNN_EALIGN;
   const bool vec4 = C % 4 == 0 && ld_dsrc % 4 == 0 && ld_out % 4 == 0 && ld_g % 4 == 0 && egnn_aligned16(dsrc) && egnn_aligned16(out) &&
                     egnn_aligned16(g) && egnn_aligned16(row_dot);
-  const unsigned blocks = (unsigned)blocks_of(S * (C / (vec4 ? 4 : 1)), THREADS);
-  EGNN_CHECK_ARG(blocks_of(S * (C / (vec4 ? 4 : 1)), THREADS) < 0x7fffffffLL);
-  if (form == SOFTMAX) {
-    if (vec4) {
-      launch_walk<4, DOT>(row_dot, nullptr, n_rows, keys_sorted, S, shift, out, ld_out, g, ld_g, C, ws, st);
-      hipLaunchKernelGGL((ssm_bwd_gather_kernel<4, SOFTMAX>), dim3(blocks), dim3(THREADS), 0, st, dsrc, ld_dsrc, out, ld_out, g, ld_g, rows, S,
-                         n_rows, C, (const float*)row_dot);
-    } else {
-      launch_walk<1, DOT>(row_dot, nullptr, n_rows, keys_sorted, S, shift, out, ld_out, g, ld_g, C, ws, st);
-      hipLaunchKernelGGL((ssm_bwd_gather_kernel<1, SOFTMAX>), dim3(blocks), dim3(THREADS), 0, st, dsrc, ld_dsrc, out, ld_out, g, ld_g, rows, S,
-                         n_rows, C, (const float*)row_dot);
-    }
-  } else {
-    if (vec4) {
-      launch_walk<4, SUM>(row_dot, nullptr, n_rows, keys_sorted, S, shift, g, ld_g, nullptr, 0, C, ws, st);
-      hipLaunchKernelGGL((ssm_bwd_gather_kernel<4, LOG_SOFTMAX>), dim3(blocks), dim3(THREADS), 0, st, dsrc, ld_dsrc, out, ld_out, g, ld_g, rows,
-                         S, n_rows, C, (const float*)row_dot);
-    } else {
-      launch_walk<1, SUM>(row_dot, nullptr, n_rows, keys_sorted, S, shift, g, ld_g, nullptr, 0, C, ws, st);
-      hipLaunchKernelGGL((ssm_bwd_gather_kernel<1, LOG_SOFTMAX>), dim3(blocks), dim3(THREADS), 0, st, dsrc, ld_dsrc, out, ld_out, g, ld_g, rows,
-                         S, n_rows, C, (const float*)row_dot);
-    }
-  }
+  const int64_t blocks = blocks_for(S * (C / (vec4 ? 4 : 1)), LG_ONE);
+  EGNN_CHECK_ARG(blocks < 0x7fffffffLL);
+  dispatch_w_form(vec4, form, [&](auto w, auto f) {
+    constexpr int W = decltype(w)::value, FORM = decltype(f)::value;
+    if (FORM == SOFTMAX) launch_walk<W, DOT>(row_dot, nullptr, n_rows, keys_sorted, S, shift, out, ld_out, g, ld_g, C, ws, st);
+    else launch_walk<W, SUM>(row_dot, nullptr, n_rows, keys_sorted, S, shift, g, ld_g, nullptr, 0, C, ws, st);
+    hipLaunchKernelGGL((ssm_bwd_gather_kernel<W, FORM>), dim3((unsigned)blocks), dim3(THREADS), 0, st, dsrc, ld_dsrc, out, ld_out, g, ld_g, rows, S,
+                       n_rows, C, (const float*)row_dot);
+  });
   return egnn_launch_status();
 }

@@ -52,7 +52,12 @@ def test_the_abi_is_still_9_and_the_source_is_listed():
     build = importlib.import_module("efficient_gnns_amd.build")
     assert "scatter.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "scatter.hip"))
     text = open(os.path.join(build.CSRC, "scatter.hip")).read()
-    assert '#include "rows_keys.h"' in text and "atomic" not in text.split("namespace {", 1)[1]     # no atomics of any kind in the code
+    assert '#include "rows_runs.h"' in text and "atomic" not in text.split("namespace {", 1)[1]     # no atomics of any kind in the code
+    runs = open(os.path.join(build.CSRC, "rows_runs.h")).read()
+    assert '#include "rows_keys.h"' in runs and "atomic" not in runs and "CHUNK = EGNN_ROWS_SUM_CHUNK;" in runs
+    # the cut, the slot rule and the size helpers are the shared header's
+    for own in ("int64_t lower_bound", "int64_t part_slot", "int64_t part_pitch", "bool sizes_ok", "int64_t blocks_for", "EGNN_ROWS_SUM_CHUNK;"):
+        assert own not in text and own in runs, own
     assert "egnn_rows_add_runs_f32(" in text                                      # sum / mean run the existing run-sum itself
 
 

@@ -45,10 +45,31 @@ def test_the_abi_is_still_9_and_the_source_is_listed():
     assert _lib.load().egnn_abi_version() == 9
     build = __import__("importlib").import_module("efficient_gnns_amd.build")
     assert "rows_sum.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "rows_keys.h"))
-    # the key / sort helpers live in the shared header only
+    # the key / sort helpers live in the shared key header only, which a file reaches directly or through the run-cut header
+    runs = open(os.path.join(build.CSRC, "rows_runs.h")).read()
+    assert '#include "rows_keys.h"' in runs and "DeviceRadixSort" not in runs and "int bits_for" not in runs
     for f in ("adam_rows.hip", "rows_sum.hip"):
         text = open(os.path.join(build.CSRC, f)).read()
-        assert '#include "rows_keys.h"' in text and "DeviceRadixSort" not in text and "int bits_for" not in text
+        assert '#include "rows_keys.h"' in text or '#include "rows_runs.h"' in text
+        assert "DeviceRadixSort" not in text and "int bits_for" not in text
+
+
+def test_the_run_cut_is_defined_in_rows_runs_h_only():
+    build = __import__("importlib").import_module("efficient_gnns_amd.build")
+    runs = open(os.path.join(build.CSRC, "rows_runs.h")).read()
+    assert re.search(r"constexpr int64_t CHUNK = EGNN_ROWS_SUM_CHUNK;", runs)     # the chunk is the header's, not a number of its own
+    assert "atomic" not in runs                                                   # nothing shared reads-modifies-writes memory
+    shared = ("lower_bound", "row_has_run", "is_run_head", "chunk_start", "chunk_is_long", "chunk_limit", "long_run_head", "run_chunks",
+              "part_slot", "part_slots", "part_pitch", "sizes_ok", "blocks_for", "key_usable", "fold_chunk4", "load_w", "store_w")
+    defines = lambda name, text: re.search(r"^[^/\n]*[\w>&*]\s+" + name + r"\s*\([^;{]*\)\s*\{", text, flags=re.M)  # noqa: E731
+    for name in shared:
+        assert defines(name, runs), f"rows_runs.h does not define {name}"
+    for f in ("rows_sum.hip", "scatter.hip", "scatter_softmax.hip", "adam_rows.hip"):
+        text = open(os.path.join(build.CSRC, f)).read()
+        assert '#include "rows_runs.h"' in text
+        for name in shared:
+            assert not defines(name, text), f"{f} defines {name} again"
+        assert "EGNN_ROWS_SUM_CHUNK;" not in text and "% CHUNK" not in text and "sorted[j - 1]" not in text   # no cut written out again
 
 
 def test_plan_workspace_is_monotone_in_the_list():

@@ -212,5 +212,9 @@ if __name__ == "__main__":
     ap.add_argument("--stages", action="store_true", help="time the pieces of one propagate call on synthetic endpoints only")
     ap.add_argument("--stage-nodes", type=int, default=38_155)
     ap.add_argument("--stage-edges", type=int, default=186_292)
+    ap.add_argument("--lib", default=None, help="another build of libegnn_hip.so (same ABI version) instead of the in-tree one")
     a = ap.parse_args()
+    if a.lib:                                                        # before the first load
+        sys.path.insert(0, ROOT)
+        importlib.import_module("efficient_gnns_amd._lib").LIB_PATH = os.path.abspath(a.lib)
     stages(a) if a.stages else main(a)

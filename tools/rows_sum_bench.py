@@ -20,6 +20,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (cap_cpu_threads)
 import efficient_gnns_amd.data as D  # noqa: E402
 import efficient_gnns_amd.ops as ops  # noqa: E402
+from efficient_gnns_amd import _lib  # noqa: E402
 from efficient_gnns_amd.utils import subgraph  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -28,7 +29,10 @@ ap.add_argument("--C", type=int, default=256)
 ap.add_argument("--reps", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--out", default=None, help="also write the result line to this file")
+ap.add_argument("--lib", default=None, help="another build of libegnn_hip.so (same ABI version) instead of the in-tree one")
 args = ap.parse_args()
+if args.lib:
+    _lib.LIB_PATH = os.path.abspath(args.lib)                       # before the first load
 bench.cap_cpu_threads()
 if not torch.cuda.is_available():
     sys.exit("rows_sum_bench.py measures on the GPU only")

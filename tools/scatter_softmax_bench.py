@@ -31,8 +31,10 @@ def main(args):
     import bench  # noqa: E402  (cap_cpu_threads)
     import efficient_gnns_amd.data as D
     import efficient_gnns_amd.utils as PU
-    from efficient_gnns_amd import ops
+    from efficient_gnns_amd import _lib, ops
 
+    if args.lib:
+        _lib.LIB_PATH = os.path.abspath(args.lib)                   # before the first load
     bench.cap_cpu_threads()
     assert torch.cuda.is_available(), "scatter_softmax_bench needs a GPU"
     dev = torch.device("cuda", 0)
@@ -107,4 +109,5 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sorted", action="store_true", help="keep the edges grouped by target instead of a random order")
+    ap.add_argument("--lib", default=None, help="another build of libegnn_hip.so (same ABI version) instead of the in-tree one")
     main(ap.parse_args())
