@@ -20,20 +20,11 @@ __device__ __forceinline__ int egnn_lane() { return threadIdx.x & 63; }
 // wave index inside the workgroup as a provably wave-uniform (SGPR) value
 __device__ __forceinline__ int egnn_wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
-__device__ __forceinline__ float egnn_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
+#include "block_reduce.h"
+
+// the float butterflies under their historical names
+__device__ __forceinline__ float egnn_wave_sum(float v) { return egnn_reduce::group_sum<EGNN_WAVE>(v); }
 // sum over the aligned group of G consecutive lanes (G a power of two <= 64) the calling lane sits in; every lane of the group gets it
 template <int G>
-__device__ __forceinline__ float egnn_group_sum(float v) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float egnn_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
+__device__ __forceinline__ float egnn_group_sum(float v) { return egnn_reduce::group_sum<G>(v); }
+__device__ __forceinline__ float egnn_wave_max(float v) { return egnn_reduce::group_max<EGNN_WAVE>(v); }

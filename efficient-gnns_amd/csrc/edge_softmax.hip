@@ -6,8 +6,11 @@
 // straight into registers by one wavefront (never written back), and segments are CSR rows, so the softmax
 // needs no atomics and has a fixed summation order.  HBM/L2-bound gather work: no MFMA.
 #include "common.h"
+#include "block_reduce.h"
 
 namespace {
+
+using namespace egnn_reduce;
 
 enum { K_COSINE = 0, K_POLY = 1, K_L2 = 2, K_RBF = 3 };
 constexpr float kCosEps = 1e-8f;
@@ -140,8 +143,7 @@ __global__ __launch_bounds__(256) void seg_sum_kernel(const int64_t* __restrict_
     const bool small = e - b <= 256;
     float d = 0.f;
     if (small) for (int64_t i = b + sl; i < e; i += 16) d += x[i];
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) d += __shfl_xor(d, o);
+    d = group_sum<16>(d);
     if (small && sl == 0 && s < n_seg) out[s] = d;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -170,26 +172,15 @@ constexpr int kLspBlocks = 1024;
 // fixed reduction order: deterministic.
 constexpr int kSubMax = 256;
 
-__device__ __forceinline__ float sub16_sum(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float sub16_max(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-// (max, sum exp + 1e-16) of x[b, e) walked by lanes first, first + step, ... and reduced over the walking group
+// (max, sum exp + 1e-16) of x[b, e) walked by lanes first, first + step, ... and reduced over the walking group (the wave or 16 lanes)
 template <bool WAVE>
 __device__ __forceinline__ void seg_softmax_stats(const float* __restrict__ x, int64_t b, int64_t e, int first, int step, float& m, float& den) {
   m = -INFINITY;
   for (int64_t i = b + first; i < e; i += step) m = fmaxf(m, x[i]);
-  m = WAVE ? egnn_wave_max(m) : sub16_max(m);
+  m = group_max<WAVE ? 64 : 16>(m);
   float z = 0.f;
   for (int64_t i = b + first; i < e; i += step) z += expf(x[i] - m);
-  den = (WAVE ? egnn_wave_sum(z) : sub16_sum(z)) + 1e-16f;
+  den = group_sum<WAVE ? 64 : 16>(z) + 1e-16f;
 }
 
 template <bool WAVE>
@@ -228,24 +219,8 @@ __global__ __launch_bounds__(256) void lsp_loss_fwd_kernel(const int64_t* __rest
       if (eg - bg > kSubMax) acc += lsp_fwd_segment<true>(xs, xt, bg, eg, lane, 64, mse, ps, pt);
     }
   }
-  acc = egnn_wave_sum(acc);
-  if (lane == 0) s_part[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
-}
-
-__global__ __launch_bounds__(256) void lsp_loss_final_kernel(const float* __restrict__ partials, int nblocks, float inv_count,
-                                                             float* __restrict__ loss) {
-  __shared__ float s[256];
-  float a = 0.f;
-  for (int i = threadIdx.x; i < nblocks; i += 256) a += partials[i];
-  s[threadIdx.x] = a;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = s[0] * inv_count;
+  const float tot = waves4_sum<PAIRWISE>(egnn_wave_sum(acc), s_part);
+  if (threadIdx.x == 0) partials[blockIdx.x] = tot;
 }
 
 // d loss / d sim_s (and, when asked for, d loss / d sim_t) through the two softmaxes: gx = p * (gp - sum_seg p * gp) with
@@ -266,8 +241,8 @@ __device__ __forceinline__ void lsp_bwd_segment(const float* __restrict__ ps, co
       if (gxt != nullptr && t > 0.f) d_t = fmaf(t, gs * (logf(t) - logf(a) + 1.f), d_t);
     }
   }
-  d_s = WAVE ? egnn_wave_sum(d_s) : sub16_sum(d_s);
-  if (gxt != nullptr) d_t = WAVE ? egnn_wave_sum(d_t) : sub16_sum(d_t);
+  d_s = group_sum<WAVE ? 64 : 16>(d_s);
+  if (gxt != nullptr) d_t = group_sum<WAVE ? 64 : 16>(d_t);
   for (int64_t i = b + first; i < e; i += step) {
     const float a = ps[i], t = pt[i];
     if (mse) {
@@ -302,7 +277,8 @@ __global__ __launch_bounds__(256) void lsp_loss_bwd_kernel(const int64_t* __rest
 
 // Column sums of a [n, C] matrix: fixed row stripes per block, fixed-order finalize (bias gradients; no torch reduction, see above).
 // HBM-bound streaming read: 256 threads = RPB row lanes x CW column lanes (CW = the power of two >= C, <= 256; wider matrices walk
-// column chunks), four independent row streams per thread, one partial row per block; the finalize gives one wave per column.
+// column chunks), four independent row streams per thread, one partial row per block; the finalize gives one wave per column
+// (colsum_partials of block_reduce.h).
 constexpr int kColsumBlocks = 1024;
 
 template <int CW>
@@ -342,21 +318,7 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
   }
 }
 
-__global__ __launch_bounds__(256) void colsum_wave_final_kernel(const float* __restrict__ partials, int nblocks, int64_t C,
-                                                                float* __restrict__ out) {
-  const int lane = egnn_lane();
-  const int64_t c = (int64_t)blockIdx.x * 4 + egnn_wave_id();
-  if (c >= C) return;
-  float t = 0.f;
-  for (int b = lane; b < nblocks; b += 64) t += partials[(int64_t)b * C + c];
-  t = egnn_wave_sum(t);
-  if (lane == 0) out[c] = t;
-}
-
-inline unsigned wave_grid(int64_t n) {
-  const int64_t b = (n + 3) / 4;
-  return (unsigned)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
-}
+inline unsigned wave_grid(int64_t n) { return (unsigned)capped_blocks(n, 4, 16384); }
 
 // GAT attention coefficients of one target row per wavefront (PyG <=1.7 GATConv.message + utils.softmax):
 //   s_e,h = leaky_relu(alpha_src[col[e],h] + alpha_dst[i,h]);  att[h,e] = exp(s - max_e s) / (sum_e exp(s - max) + 1e-16)
@@ -424,8 +386,7 @@ extern "C" int egnn_edge_sim_coef_f32(const float* g, const float* sim, const fl
   EGNN_CHECK_ARG(E >= 0 && kernel >= 0 && kernel <= 3);
   if (E == 0) return EGNN_OK;
   EGNN_CHECK_ARG(g && sim && aux3 && alpha && beta_a && beta_b);
-  const int64_t blocks = (E + 255) / 256;
-  hipLaunchKernelGGL(edge_coef_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, g, sim,
+  hipLaunchKernelGGL(edge_coef_kernel, dim3((unsigned)capped_blocks(E, 256, 4096)), dim3(256), 0, (hipStream_t)stream, g, sim,
                      aux3, E, kernel, alpha, beta_a, beta_b);
   return egnn_launch_status();
 }
@@ -462,10 +423,9 @@ extern "C" int egnn_lsp_loss_fwd_f32(const int64_t* seg_ptr, const float* sim_s,
   EGNN_CHECK_ARG(n_seg >= 0 && E > 0 && (criterion == 0 || criterion == 1));
   EGNN_CHECK_ARG(seg_ptr && sim_s && sim_t && p_s && p_t && loss && ws && n_seg > 0);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t want = (n_seg + 15) / 16;   // 16 segments per workgroup pass
-  const int nb = (int)(want < kLspBlocks ? want : kLspBlocks);
+  const int nb = (int)capped_blocks(n_seg, 16, kLspBlocks);   // 16 segments per workgroup pass
   hipLaunchKernelGGL(lsp_loss_fwd_kernel, dim3(nb), dim3(256), 0, st, seg_ptr, sim_s, sim_t, n_seg, criterion, p_s, p_t, ws);
-  hipLaunchKernelGGL(lsp_loss_final_kernel, dim3(1), dim3(256), 0, st, ws, nb, 1.f / (float)E, loss);
+  hipLaunchKernelGGL((sum_partials_kernel<256, float>), dim3(1), dim3(256), 0, st, ws, 0, nb, 1.f / (float)E, loss);
   return egnn_launch_status();
 }
 
@@ -485,14 +445,13 @@ extern "C" int egnn_colsum_f32(const float* x, int64_t ld, int64_t n, int64_t C,
   hipStream_t st = (hipStream_t)stream;
   const int cw = C > 128 ? 256 : (C > 64 ? 128 : (C > 32 ? 64 : 32));
   const int rpb = 256 / cw;
-  const int64_t want = (n + 4 * rpb - 1) / (4 * rpb);   // >= 4 rows per row lane before another block is worth its partial row
-  const int nb = (int)(want < 1 ? 1 : (want < kColsumBlocks ? want : kColsumBlocks));
+  const int nb = (int)capped_blocks(n, 4 * rpb, kColsumBlocks);   // >= 4 rows per row lane before another block is worth its partial row
   switch (cw) {
     case 256: hipLaunchKernelGGL(colsum_partial_kernel<256>, dim3(nb), dim3(256), 0, st, x, ld, n, C, ws); break;
     case 128: hipLaunchKernelGGL(colsum_partial_kernel<128>, dim3(nb), dim3(256), 0, st, x, ld, n, C, ws); break;
     case 64: hipLaunchKernelGGL(colsum_partial_kernel<64>, dim3(nb), dim3(256), 0, st, x, ld, n, C, ws); break;
     default: hipLaunchKernelGGL(colsum_partial_kernel<32>, dim3(nb), dim3(256), 0, st, x, ld, n, C, ws); break;
   }
-  hipLaunchKernelGGL(colsum_wave_final_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, ws, nb, C, out);
+  colsum_partials(ws, nb, C, out, st);
   return egnn_launch_status();
 }

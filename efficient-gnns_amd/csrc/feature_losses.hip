@@ -4,19 +4,13 @@
 //                                                           loss = mse(F.normalize(e_s), F.normalize(e_t))  (norm ACROSS nodes)
 // F.normalize(x) = x / max(||x||_2, eps), eps = 1e-12: where the clamp is active the denominator is a constant.
 #include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
-constexpr int kFlBlocks = 1024;   // partial sums per launch (fixed => deterministic finalize)
+using namespace egnn_reduce;
 
-__device__ __forceinline__ float block4_sum(float v, float* sh) {   // sum of the four waves' lane-0 values; result on every thread
-  const int wave = egnn_wave_id();
-  if (egnn_lane() == 0) sh[wave] = v;
-  __syncthreads();
-  const float r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return r;
-}
+constexpr int kFlBlocks = 1024;   // partial sums per launch (fixed => deterministic finalize)
 
 // ---- FitNet --------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fitnet_fwd_kernel(const float* __restrict__ f, int64_t ldf, const float* __restrict__ t, int64_t ldt,
@@ -35,7 +29,7 @@ __global__ __launch_bounds__(256) void fitnet_fwd_kernel(const float* __restrict
     for (int64_t d = lane; d < D; d += 64) { const float u = fp[d] * inf_ - tp[d] * int_; s = fmaf(u, u, s); }
     acc += egnn_wave_sum(s);
   }
-  const float tot = block4_sum(acc, sh);
+  const float tot = waves4_sum<PAIRWISE>(acc, sh);
   if (threadIdx.x == 0) partials[blockIdx.x] = tot;
 }
 
@@ -70,19 +64,6 @@ __global__ __launch_bounds__(256) void fitnet_bwd_kernel(const float* __restrict
   }
 }
 
-__global__ __launch_bounds__(256) void fl_sum_kernel(const float* __restrict__ partials, int nb, float scale, float* __restrict__ out) {
-  __shared__ float red[256];
-  float v = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 256) v += partials[i];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = red[0] * scale;
-}
-
 // ---- attention transfer ------------------------------------------------------------------------------------------
 // pass 1: row energies of both sides + per-block partials of sum e^2
 __global__ __launch_bounds__(256) void at_energy_kernel(const float* __restrict__ f, int64_t ldf, int64_t Df, const float* __restrict__ t, int64_t ldt,
@@ -101,7 +82,7 @@ __global__ __launch_bounds__(256) void at_energy_kernel(const float* __restrict_
     if (lane == 0) { es[row] = a; et[row] = b; }
     a2 = fmaf(a, a, a2); b2 = fmaf(b, b, b2);
   }
-  const float ta = block4_sum(a2, sh), tb = block4_sum(b2, sh);
+  const float ta = waves4_sum<PAIRWISE>(a2, sh), tb = waves4_sum<PAIRWISE>(b2, sh);
   if (threadIdx.x == 0) { partials[blockIdx.x] = ta; partials[kFlBlocks + blockIdx.x] = tb; }
 }
 
@@ -110,29 +91,18 @@ __global__ __launch_bounds__(1024) void at_finish_kernel(const float* __restrict
                                                          const float* __restrict__ partials, float eps, float* __restrict__ scal,
                                                          float* __restrict__ loss) {
   __shared__ float red[3][1024];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 1024) { a += partials[i]; b += partials[kFlBlocks + i]; }
-  red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-    __syncthreads();
-  }
+  float ab[2] = {0.f, 0.f};
+  for (int i = threadIdx.x; i < nb; i += 1024) { ab[0] += partials[i]; ab[1] += partials[kFlBlocks + i]; }
+  block_tree_sum<1024>(ab, red);
   const float raw_s = sqrtf(red[0][0]), raw_t = sqrtf(red[1][0]);
   const float ns = fmaxf(raw_s, eps), nt = fmaxf(raw_t, eps);
   __syncthreads();
-  float d2 = 0.f, ds = 0.f, dt_ = 0.f;
+  float m[3] = {0.f, 0.f, 0.f};   // sum d^2, sum d e_s, sum d e_t
   for (int64_t i = threadIdx.x; i < n; i += 1024) {
     const float d = es[i] / ns - et[i] / nt;
-    d2 = fmaf(d, d, d2); ds = fmaf(d, es[i], ds); dt_ = fmaf(d, et[i], dt_);
+    m[0] = fmaf(d, d, m[0]); m[1] = fmaf(d, es[i], m[1]); m[2] = fmaf(d, et[i], m[2]);
   }
-  red[0][threadIdx.x] = d2; red[1][threadIdx.x] = ds; red[2][threadIdx.x] = dt_;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o)
-      for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + o];
-    __syncthreads();
-  }
+  block_tree_sum<1024>(m, red);
   if (threadIdx.x == 0) {
     loss[0] = red[0][0] / (float)n;
     scal[0] = ns; scal[1] = nt; scal[2] = red[1][0]; scal[3] = red[2][0]; scal[4] = raw_s; scal[5] = raw_t;
@@ -163,20 +133,6 @@ __global__ __launch_bounds__(256) void at_bwd_kernel(const float* __restrict__ f
 // would do, but that closed form cancels (tens of per cent off at e_s ~ k e_t in fp32, the direct form below 1e-5).
 constexpr int kAtPartBlocks = 512;   // 3 partial arrays of the second step fit the 2 kFlBlocks floats the first one uses
 
-__global__ __launch_bounds__(256) void fl_sumq_kernel(const float* __restrict__ partials, int stride, int nb, float* __restrict__ out) {
-  __shared__ float red[256];   // block q: out[q] = sum of partials[q * stride .. + nb), fixed order
-  const float* p = partials + (int64_t)blockIdx.x * stride;
-  float v = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 256) v += p[i];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = red[0];
-}
-
 // this rank's partials of sum d^2, sum d e_s, sum d e_t under the GLOBAL norms; scal = {ns, nt, raw |e_s|, raw |e_t|}
 __global__ __launch_bounds__(256) void at_partial_kernel(const float* __restrict__ es, const float* __restrict__ et, int64_t n,
                                                          const float* __restrict__ sumsq_global, float eps, float* __restrict__ scal,
@@ -184,18 +140,12 @@ __global__ __launch_bounds__(256) void at_partial_kernel(const float* __restrict
   __shared__ float red[3][256];
   const float raw_s = sqrtf(sumsq_global[0]), raw_t = sqrtf(sumsq_global[1]);
   const float ns = fmaxf(raw_s, eps), nt = fmaxf(raw_t, eps);
-  float d2 = 0.f, ds = 0.f, dt_ = 0.f;
+  float m[3] = {0.f, 0.f, 0.f};   // sum d^2, sum d e_s, sum d e_t
   for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float d = es[i] / ns - et[i] / nt;
-    d2 = fmaf(d, d, d2); ds = fmaf(d, es[i], ds); dt_ = fmaf(d, et[i], dt_);
+    m[0] = fmaf(d, d, m[0]); m[1] = fmaf(d, es[i], m[1]); m[2] = fmaf(d, et[i], m[2]);
   }
-  red[0][threadIdx.x] = d2; red[1][threadIdx.x] = ds; red[2][threadIdx.x] = dt_;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o)
-      for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + o];
-    __syncthreads();
-  }
+  block_tree_sum<256>(m, red);
   if (threadIdx.x == 0) {
     for (int q = 0; q < 3; ++q) partials[q * kAtPartBlocks + blockIdx.x] = red[q][0];
     if (blockIdx.x == 0) { scal[0] = ns; scal[1] = nt; scal[2] = raw_s; scal[3] = raw_t; }
@@ -231,10 +181,9 @@ extern "C" int egnn_fitnet_fwd_f32(const float* f, int64_t ldf, const float* t, 
   EGNN_CHECK_ARG(n > 0 && D > 0 && f && t && loss && ws && ldf >= D && ldt >= D && eps > 0.f);
   if (ws_floats < egnn_feature_loss_ws_floats(n)) return EGNN_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t want = (n + 3) / 4;
-  const int nb = (int)(want < kFlBlocks ? want : kFlBlocks);
+  const int nb = (int)capped_blocks(n, 4, kFlBlocks);
   hipLaunchKernelGGL(fitnet_fwd_kernel, dim3(nb), dim3(256), 0, st, f, ldf, t, ldt, n, D, eps, ws);
-  hipLaunchKernelGGL(fl_sum_kernel, dim3(1), dim3(256), 0, st, ws, nb, 1.f / ((float)n * (float)D), loss);
+  hipLaunchKernelGGL((sum_partials_kernel<256, float>), dim3(1), dim3(256), 0, st, ws, 0, nb, 1.f / ((float)n * (float)D), loss);
   return egnn_launch_status();
 }
 
@@ -255,8 +204,7 @@ extern "C" int egnn_at_fwd_f32(const float* f, int64_t ldf, int64_t Df, const fl
   float* es = ws + 2 * kFlBlocks;
   float* et = es + n;
   float* scal = et + n;
-  const int64_t want = (n + 3) / 4;
-  const int nb = (int)(want < kFlBlocks ? want : kFlBlocks);
+  const int nb = (int)capped_blocks(n, 4, kFlBlocks);
   hipLaunchKernelGGL(at_energy_kernel, dim3(nb), dim3(256), 0, st, f, ldf, Df, t, ldt, Dt, n, es, et, ws);
   hipLaunchKernelGGL(at_finish_kernel, dim3(1), dim3(1024), 0, st, es, et, n, nb, ws, eps, scal, loss);
   return egnn_launch_status();
@@ -279,10 +227,9 @@ extern "C" int egnn_at_energy_f32(const float* f, int64_t ldf, int64_t Df, const
   EGNN_CHECK_ARG(n > 0 && Df > 0 && Dt > 0 && f && t && es && et && sumsq && ws && ldf >= Df && ldt >= Dt);
   if (ws_floats < egnn_feature_loss_ws_floats(n)) return EGNN_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t want = (n + 3) / 4;
-  const int nb = (int)(want < kFlBlocks ? want : kFlBlocks);
+  const int nb = (int)capped_blocks(n, 4, kFlBlocks);
   hipLaunchKernelGGL(at_energy_kernel, dim3(nb), dim3(256), 0, st, f, ldf, Df, t, ldt, Dt, n, es, et, ws);
-  hipLaunchKernelGGL(fl_sumq_kernel, dim3(2), dim3(256), 0, st, ws, kFlBlocks, nb, sumsq);
+  hipLaunchKernelGGL((sum_partials_kernel<256, float>), dim3(2), dim3(256), 0, st, ws, kFlBlocks, nb, 1.f, sumsq);
   return egnn_launch_status();
 }
 
@@ -292,10 +239,9 @@ extern "C" int egnn_at_partial_f32(const float* es, const float* et, int64_t n, 
   static_assert(3 * kAtPartBlocks <= 2 * kFlBlocks, "the partials of at_partial_kernel must fit egnn_feature_loss_ws_floats");
   if (ws_floats < egnn_feature_loss_ws_floats(n)) return EGNN_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t want = (n + 255) / 256;
-  const int nb = (int)(want < kAtPartBlocks ? want : kAtPartBlocks);
+  const int nb = (int)capped_blocks(n, 256, kAtPartBlocks);
   hipLaunchKernelGGL(at_partial_kernel, dim3(nb), dim3(256), 0, st, es, et, n, sumsq_global, eps, scal, ws);
-  hipLaunchKernelGGL(fl_sumq_kernel, dim3(3), dim3(256), 0, st, ws, kAtPartBlocks, nb, sums);
+  hipLaunchKernelGGL((sum_partials_kernel<256, float>), dim3(3), dim3(256), 0, st, ws, kAtPartBlocks, nb, 1.f, sums);
   return egnn_launch_status();
 }
 

@@ -20,8 +20,11 @@
 // with go' = q_i go_i,  g_e = m_e r_{col e} <go'_i, xl[col e]>,  dxl[j] = r_j (sum att m go' + d_a_src[j] att_l) + d_a_dst[j] att_r,
 // d_att_l = sum_j r_j xl_j d_a_src[j]  (a_src comes from the scaled source features, a_dst from the unscaled ones).
 #include "common.h"
+#include "block_reduce.h"
 
 namespace {
+
+using namespace egnn_reduce;
 
 constexpr int kGatBwdBlocks = 1024;   // grid cap of the source-side kernel = row count of the d_att partials
 constexpr int64_t kGatMaxHC = 2048;   // 4 waves x 2 H*C floats of LDS accumulators (64 KiB)
@@ -182,22 +185,7 @@ __global__ __launch_bounds__(256) void gat_aggregate_bwd_kernel(const int64_t* _
     partials[(int64_t)blockIdx.x * 2 * HC + k] = (s_acc[k] + s_acc[2 * HC + k]) + (s_acc[4 * HC + k] + s_acc[6 * HC + k]);
 }
 
-// out[k] = sum over the nb block partials of column k, one wave per column, fixed order
-__global__ __launch_bounds__(256) void gat_partials_final_kernel(const float* __restrict__ partials, int nb, int64_t K,
-                                                                 float* __restrict__ out) {
-  const int lane = egnn_lane();
-  const int64_t k = (int64_t)blockIdx.x * 4 + egnn_wave_id();
-  if (k >= K) return;
-  float t = 0.f;
-  for (int b = lane; b < nb; b += 64) t += partials[(int64_t)b * K + k];
-  t = egnn_wave_sum(t);
-  if (lane == 0) out[k] = t;
-}
-
-inline int gat_bwd_blocks(int64_t n_src) {
-  const int64_t want = (n_src + 3) / 4;
-  return (int)(want < 1 ? 1 : (want < kGatBwdBlocks ? want : kGatBwdBlocks));
-}
+inline int gat_bwd_blocks(int64_t n_src) { return (int)capped_blocks(n_src, 4, kGatBwdBlocks); }
 
 // VEC floats of one load / store: float4 (16-byte aligned head blocks), float2 (8-byte: C = 250) or float
 template <int VEC> struct GatVec;
@@ -351,7 +339,7 @@ int gat_launch_aggregate_bwd(const int64_t* colptr, const int64_t* t_col, const 
     hipLaunchKernelGGL(gat_aggregate_bwd_kernel<false>, dim3(nb), dim3(256), lds, st, colptr, t_col, perm, att, mult, d_raw, go, ld_go,
                        go_head_stride, go_scale, xl, ld_xl, att_l, att_r, d_alpha_dst, n_src, nnz, H, C, r, q, dxl, ld_dxl, partials);
   if (d_att != nullptr)
-    hipLaunchKernelGGL(gat_partials_final_kernel, dim3((unsigned)((2 * HC + 3) / 4)), dim3(256), 0, st, ws, nb, 2 * HC, d_att);
+    colsum_partials(ws, nb, 2 * HC, d_att, st);   // out[k] = the nb block partials of column k in block order
   return egnn_launch_status();
 }
 

@@ -3,6 +3,7 @@
 //   gcn_norm        GCNConv first forward (cached) /root/reference/arxiv_pyg/gnn.py:28-35,47
 // HBM-bound integer/byte work: coalesced wave-per-row sweeps, no GEMM reshaping.
 #include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -37,13 +38,8 @@ __device__ __forceinline__ void diag_stats(const int64_t* col, int64_t start, in
     l += c < row;
     d += c == row;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    l += __shfl_xor(l, o);
-    d += __shfl_xor(d, o);
-  }
-  lt = l;
-  nd = d;
+  lt = egnn_reduce::group_sum<EGNN_WAVE>(l);
+  nd = egnn_reduce::group_sum<EGNN_WAVE>(d);
 }
 
 __global__ __launch_bounds__(256) void gcn_count_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,

@@ -3,36 +3,26 @@
 //                                every criterion)
 //   gather + L2 row normalise    F.normalize after `feat[sampled_inds]`, criterion.py:64-72,136-140
 #include "common.h"
+#include "block_reduce.h"
 
 namespace {
+
+using namespace egnn_reduce;
 
 constexpr int kRowsPerBlock = 4;     // one wave per row
 constexpr int kMaxBlocks = 1024;     // partial sums per launch (fixed => deterministic finalize)
 
 // A row is walked by a sub-group of SUB lanes (64: one row per wave; 16: four rows per wave -- class counts <= 64, where a
 // whole wave per 40-column row left the kernels latency-bound: 37 + 32 us for 90 941 x 40).
-template <int SUB>
-__device__ __forceinline__ float sub_max(float v) {
-#pragma unroll
-  for (int o = SUB / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-template <int SUB>
-__device__ __forceinline__ float sub_sum(float v) {
-#pragma unroll
-  for (int o = SUB / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // log-sum-exp of (x * s) over a row distributed lane-strided over the sub-group; every lane of the sub-group gets it
 template <int SUB>
 __device__ __forceinline__ float row_lse(const float* p, int64_t C, float s, int sl) {
   float m = -INFINITY;
   for (int64_t c = sl; c < C; c += SUB) m = fmaxf(m, p[c] * s);
-  m = sub_max<SUB>(m);
+  m = group_max<SUB>(m);
   float z = 0.f;
   for (int64_t c = sl; c < C; c += SUB) z += expf(p[c] * s - m);
-  z = sub_sum<SUB>(z);
+  z = group_sum<SUB>(z);
   return m + logf(z);
 }
 
@@ -46,7 +36,7 @@ __global__ __launch_bounds__(256) void ce_kd_fwd_kernel(const float* __restrict_
                                                         const int64_t* __restrict__ labels, const int64_t* __restrict__ rows,
                                                         int64_t n, int64_t C, float T, float* __restrict__ partials) {
   constexpr int RPW = 64 / SUB;   // rows per wave
-  __shared__ float s_ce[kRowsPerBlock], s_kd[kRowsPerBlock], s_nv[kRowsPerBlock];
+  __shared__ float sh[kRowsPerBlock * 3];
   const int lane = egnn_lane();
   const int wave = egnn_wave_id();
   const int sl = lane % SUB, sg = lane / SUB;
@@ -72,7 +62,7 @@ __global__ __launch_bounds__(256) void ce_kd_fwd_kernel(const float* __restrict_
         const float p = expf(logp);
         acc += p > 0.f ? p * (logp - logq) : 0.f;  // F.kl_div: 0 where target == 0
       }
-      acc = sub_sum<SUB>(acc);
+      acc = group_sum<SUB>(acc);
       if (sl == 0) kd += acc;
     }
   }
@@ -81,30 +71,21 @@ __global__ __launch_bounds__(256) void ce_kd_fwd_kernel(const float* __restrict_
     kd = egnn_wave_sum(sl == 0 ? kd : 0.f);
     nv = egnn_wave_sum(sl == 0 ? nv : 0.f);
   }
-  if (lane == 0) { s_ce[wave] = ce; s_kd[wave] = kd; s_nv[wave] = nv; }
-  __syncthreads();
+  float tot[3] = {ce, kd, nv};
+  waves4_sum<SERIAL>(tot, sh);   // the waves in order (not the pairwise form of the other losses: the bits of out3 depend on it)
   if (threadIdx.x == 0) {
-    float a = 0.f, b = 0.f, c = 0.f;
-    for (int w = 0; w < kRowsPerBlock; ++w) { a += s_ce[w]; b += s_kd[w]; c += s_nv[w]; }
-    partials[blockIdx.x] = a;
-    partials[kMaxBlocks + blockIdx.x] = b;
-    partials[2 * kMaxBlocks + blockIdx.x] = c;
+    partials[blockIdx.x] = tot[0];
+    partials[kMaxBlocks + blockIdx.x] = tot[1];
+    partials[2 * kMaxBlocks + blockIdx.x] = tot[2];
   }
 }
 
 __global__ __launch_bounds__(256) void ce_kd_finalize_kernel(const float* __restrict__ partials, int nblocks, int64_t n,
                                                              int64_t C, int has_teacher, float* __restrict__ out3) {
   __shared__ float s[3][256];
-  float a = 0.f, b = 0.f, c = 0.f;
-  for (int i = threadIdx.x; i < nblocks; i += 256) { a += partials[i]; b += partials[kMaxBlocks + i]; c += partials[2 * kMaxBlocks + i]; }
-  s[0][threadIdx.x] = a; s[1][threadIdx.x] = b; s[2][threadIdx.x] = c;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      s[0][threadIdx.x] += s[0][threadIdx.x + o]; s[1][threadIdx.x] += s[1][threadIdx.x + o]; s[2][threadIdx.x] += s[2][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  float v[3] = {0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < nblocks; i += 256) { v[0] += partials[i]; v[1] += partials[kMaxBlocks + i]; v[2] += partials[2 * kMaxBlocks + i]; }
+  block_tree_sum<256>(v, s);
   if (threadIdx.x == 0) {
     out3[0] = s[0][0] / s[2][0];   // mean over the rows whose label is valid (all of them in the reference's use); 0/0 = nan like torch
     out3[1] = has_teacher ? s[1][0] / ((float)n * (float)C) : 0.f;
@@ -201,8 +182,7 @@ extern "C" int egnn_ce_kd_fwd_f32(const float* logits, int64_t ld_logits, const 
   EGNN_CHECK_ARG(n > 0 && C > 0 && logits && labels && out3 && partials && ld_logits >= C && T > 0.f);
   EGNN_CHECK_ARG(teacher == nullptr || ld_teacher >= C);
   const int rpb = kRowsPerBlock * (C <= 64 ? 4 : 1);   // rows per block-iteration
-  const int64_t want = (n + rpb - 1) / rpb;
-  const int nblocks = (int)(want < kMaxBlocks ? want : kMaxBlocks);
+  const int nblocks = (int)capped_blocks(n, rpb, kMaxBlocks);
   hipStream_t st = (hipStream_t)stream;
   if (C <= 64) hipLaunchKernelGGL(ce_kd_fwd_kernel<16>, dim3(nblocks), dim3(256), 0, st, logits, ld_logits, teacher, ld_teacher, labels, rows, n, C, T, partials);
   else hipLaunchKernelGGL(ce_kd_fwd_kernel<64>, dim3(nblocks), dim3(256), 0, st, logits, ld_logits, teacher, ld_teacher, labels, rows, n, C, T, partials);
@@ -231,8 +211,7 @@ extern "C" int egnn_ce_kd_bwd_f32(const float* logits, int64_t ld_logits, const 
     hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)(zb < 8192 ? zb : 8192)), dim3(256), 0, st, dlogits, ld_dlogits, n_total_rows, C);
   }
   const int rpb = kRowsPerBlock * (C <= 64 ? 4 : 1);
-  const int64_t want = (n + rpb - 1) / rpb;
-  const int nblocks = (int)(want < 4096 ? want : 4096);
+  const int nblocks = (int)capped_blocks(n, rpb, 4096);
   if (C <= 64) hipLaunchKernelGGL(ce_kd_bwd_kernel<16>, dim3(nblocks), dim3(256), 0, st, logits, ld_logits, teacher, ld_teacher,
                                   labels, rows, n, C, T, out3, g_cls, g_kd, dlogits, ld_dlogits);
   else hipLaunchKernelGGL(ce_kd_bwd_kernel<64>, dim3(nblocks), dim3(256), 0, st, logits, ld_logits, teacher, ld_teacher,
@@ -270,7 +249,7 @@ constexpr int kAccBlocks = 1024;
 __global__ __launch_bounds__(256) void split_accuracy_kernel(const float* __restrict__ logits, int64_t ld, int64_t n, int64_t C,
                                                              const int64_t* __restrict__ y, const signed char* __restrict__ split_id,
                                                              int* __restrict__ part) {
-  __shared__ int sh[4][6];
+  __shared__ int sh[4 * 6];
   const int lane = egnn_lane(), wave = egnn_wave_id();
   const int sub = lane >> 4, l16 = lane & 15;
   int hits[3] = {0, 0, 0}, cnt[3] = {0, 0, 0};
@@ -287,7 +266,7 @@ __global__ __launch_bounds__(256) void split_accuracy_kernel(const float* __rest
       }
     }
 #pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {   // 16-lane butterfly: larger value wins, ties go to the smaller column
+    for (int o = 8; o > 0; o >>= 1) {   // 16-lane argmax butterfly (a compare-and-take, not a sum): larger value wins, ties go to the smaller column
       const float ov = __shfl_xor(best, o);
       const int64_t oa = __shfl_xor(arg, o);
       const bool take = (ov > best) || (ov != ov && best == best) || (ov == best && oa < arg) || (ov != ov && best != best && oa < arg);
@@ -301,47 +280,34 @@ __global__ __launch_bounds__(256) void split_accuracy_kernel(const float* __rest
       }
     }
   }
+  int tot[6];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < 3; ++k) { tot[k] = group_sum<EGNN_WAVE>(hits[k]); tot[3 + k] = group_sum<EGNN_WAVE>(cnt[k]); }
+  waves4_sum<SERIAL>(tot, sh);
+  if (threadIdx.x == 0) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { hits[k] += __shfl_xor(hits[k], o); cnt[k] += __shfl_xor(cnt[k], o); }
+    for (int k = 0; k < 6; ++k) part[blockIdx.x * 6 + k] = tot[k];
   }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { sh[wave][k] = hits[k]; sh[wave][3 + k] = cnt[k]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
 }
 
-__global__ __launch_bounds__(64) void split_accuracy_final_kernel(const int* __restrict__ part, int nblocks, double* __restrict__ acc3) {
+// RATIO: acc3 = hits / size of train / valid / test.  Otherwise the raw counts, out = (hits of train / valid / test, sizes of train /
+// valid / test) -- what a node-range shard contributes to the all-rank accuracies
+template <bool RATIO>
+__global__ __launch_bounds__(64) void split_accuracy_final_kernel(const int* __restrict__ part, int nblocks, double* __restrict__ out) {
   const int lane = threadIdx.x;
   long long v[6] = {0, 0, 0, 0, 0, 0};
   for (int b = lane; b < nblocks; b += 64)
 #pragma unroll
     for (int k = 0; k < 6; ++k) v[k] += part[b * 6 + k];
 #pragma unroll
-  for (int k = 0; k < 6; ++k)
+  for (int k = 0; k < 6; ++k) v[k] = group_sum<EGNN_WAVE>(v[k]);
+  if constexpr (RATIO) {
+    if (lane < 3) out[lane] = v[3 + lane] > 0 ? (double)v[lane] / (double)v[3 + lane] : 0.0 / 0.0;   // empty split: nan, like mean of nothing
+  } else {
+    if (lane == 0)
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-  if (lane < 3) acc3[lane] = v[3 + lane] > 0 ? (double)v[lane] / (double)v[3 + lane] : 0.0 / 0.0;   // empty split: nan, like mean of nothing
-}
-
-// the raw counts instead of the ratios: out6 = (hits of train / valid / test, sizes of train / valid / test) -- what a node-range shard
-// contributes to the all-rank accuracies
-__global__ __launch_bounds__(64) void split_counts_final_kernel(const int* __restrict__ part, int nblocks, double* __restrict__ out6) {
-  const int lane = threadIdx.x;
-  long long v[6] = {0, 0, 0, 0, 0, 0};
-  for (int b = lane; b < nblocks; b += 64)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) v[k] += part[b * 6 + k];
-#pragma unroll
-  for (int k = 0; k < 6; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) out6[k] = (double)v[k];
+      for (int k = 0; k < 6; ++k) out[k] = (double)v[k];
+  }
 }
 
 // dst[idx[r], :] += src[r, :] for UNIQUE ids (a row-compact gradient joining a dense one, ops._GradTap): one wave per row
@@ -372,10 +338,9 @@ extern "C" int egnn_split_accuracy_f32(const float* logits, int64_t ld, int64_t 
   EGNN_CHECK_ARG(n > 0 && C > 0 && ld >= C && logits && y && split_id && acc3 && ws);
   if (ws_ints < egnn_split_accuracy_ws_ints()) return EGNN_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t want = (n + 15) / 16;
-  const int nb = (int)(want < kAccBlocks ? want : kAccBlocks);
+  const int nb = (int)capped_blocks(n, 16, kAccBlocks);
   hipLaunchKernelGGL(split_accuracy_kernel, dim3(nb), dim3(256), 0, st, logits, ld, n, C, y, (const signed char*)split_id, (int*)ws);
-  hipLaunchKernelGGL(split_accuracy_final_kernel, dim3(1), dim3(64), 0, st, (const int*)ws, nb, acc3);
+  hipLaunchKernelGGL(split_accuracy_final_kernel<true>, dim3(1), dim3(64), 0, st, (const int*)ws, nb, acc3);
   return egnn_launch_status();
 }
 
@@ -384,10 +349,9 @@ extern "C" int egnn_split_counts_f32(const float* logits, int64_t ld, int64_t n,
   EGNN_CHECK_ARG(n > 0 && C > 0 && ld >= C && logits && y && split_id && out6 && ws);
   if (ws_ints < egnn_split_accuracy_ws_ints()) return EGNN_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t want = (n + 15) / 16;
-  const int nb = (int)(want < kAccBlocks ? want : kAccBlocks);
+  const int nb = (int)capped_blocks(n, 16, kAccBlocks);
   hipLaunchKernelGGL(split_accuracy_kernel, dim3(nb), dim3(256), 0, st, logits, ld, n, C, y, (const signed char*)split_id, (int*)ws);
-  hipLaunchKernelGGL(split_counts_final_kernel, dim3(1), dim3(64), 0, st, (const int*)ws, nb, out6);
+  hipLaunchKernelGGL(split_accuracy_final_kernel<false>, dim3(1), dim3(64), 0, st, (const int*)ws, nb, out6);
   return egnn_launch_status();
 }
 

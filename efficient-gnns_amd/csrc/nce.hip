@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "gemm3.h"
+#include "block_reduce.h"
 
 using namespace egnn_gemm;
 
@@ -245,7 +246,8 @@ __global__ __launch_bounds__(256, ALIGNED ? EGNN_NCE_FWD_WAVES : 1) void nce_fwd
     }
   }
 
-  // merge the 32 lanes that share a row (same lane >> 5), then the two column-waves through LDS
+  // merge the 32 lanes that share a row (same lane >> 5), then the two column-waves through LDS.  The offsets ASCEND here (1 ... 16),
+  // for the sum as for the (max, sum) merge: not the order of egnn_reduce::group_sum, so the two butterflies stay written out
   float* lm = smem;            // [2][FB]
   float* lsum = smem + 2 * FB; // [2][FB]
 #pragma unroll
@@ -291,36 +293,17 @@ constexpr int kFinalBlocks = 1024;
 __global__ __launch_bounds__(256) void nce_finalize_rows_kernel(const float* __restrict__ pm, const float* __restrict__ ps,
                                                                 const float* __restrict__ zdiag, int64_t S, int nsplit,
                                                                 float* __restrict__ lse, float* __restrict__ block_part) {
-  __shared__ float red[256];
-  float local = 0.f;
+  __shared__ float red[1][256];
+  float local[1] = {0.f};
   for (int64_t row = blockIdx.x * 256LL + threadIdx.x; row < S; row += (int64_t)gridDim.x * 256) {
     float m = -INFINITY, s = 0.f;
     for (int k = 0; k < nsplit; ++k) lse_merge(m, s, pm[row * nsplit + k], ps[row * nsplit + k]);
     const float l = m + logf(s);
     lse[row] = l;
-    local += l - zdiag[row];
+    local[0] += l - zdiag[row];
   }
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) block_part[blockIdx.x] = red[0];
-}
-
-__global__ __launch_bounds__(256) void nce_finalize_sum_kernel(const float* __restrict__ block_part, int nblocks, float inv_count,
-                                                               float* __restrict__ loss) {
-  __shared__ float red[256];
-  float local = 0.f;
-  for (int i = threadIdx.x; i < nblocks; i += 256) local += block_part[i];
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = red[0] * inv_count;
+  egnn_reduce::block_tree_sum<256>(local, red);
+  if (threadIdx.x == 0) block_part[blockIdx.x] = red[0][0];
 }
 
 // A-operand transform of the backward GEMMs: z -> exp(z - lse[i]) - [i == j]
@@ -691,9 +674,9 @@ extern "C" int egnn_nce_block_fwd_f32(const float* fhat, int64_t ld_f, const flo
 #undef EGNN_NCE_FWD
   if (rc_fwd != EGNN_OK) return rc_fwd;
   float* block_part = ps + Sr * kMaxSplit;
-  const int fb = (int)((Sr + 255) / 256 < kFinalBlocks ? (Sr + 255) / 256 : kFinalBlocks);
+  const int fb = (int)egnn_reduce::capped_blocks(Sr, 256, kFinalBlocks);
   hipLaunchKernelGGL(nce_finalize_rows_kernel, dim3(fb), dim3(256), 0, st, pm, ps, zdiag, Sr, nsplit, lse, block_part);
-  hipLaunchKernelGGL(nce_finalize_sum_kernel, dim3(1), dim3(256), 0, st, block_part, fb, inv_count, loss);
+  hipLaunchKernelGGL((egnn_reduce::sum_partials_kernel<256, float>), dim3(1), dim3(256), 0, st, block_part, 0, fb, inv_count, loss);
   return egnn_launch_status();
 }
 

@@ -1,11 +1,12 @@
 // What the all-pairs kernels of pairwise.hip (GSP) and similarity.hip (Mantel moments, median of the distances, RBF CKA) share: one
 // workgroup of 256 threads owns one 128 x 128 tile of an N x N pair matrix, runs the fp32-MFMA mainloop twice (student Gram tile,
 // teacher Gram tile) and consumes both accumulator sets in registers.  The pair predicate, the walk over a lane's accumulator
-// entries, the upper-triangle tile map and the fixed-order float64 block sum are defined here and nowhere else.
+// entries, the upper-triangle tile map are defined here and nowhere else; the fixed-order float64 block sum is block_reduce.h's.
 #pragma once
 #include <type_traits>
 
 #include "gemm_core.h"
+#include "block_reduce.h"
 
 namespace egnn_pair {
 
@@ -13,12 +14,6 @@ using namespace egnn_gemm;
 
 constexpr int GB = 128;
 using TS = TileShape<GB, GB>;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // first block index of tile row ti in the row-major walk of the upper triangle (row ti holds the T - ti tiles tj = ti .. T-1)
 __host__ __device__ __forceinline__ int64_t tri_row_start(int64_t ti, int64_t T) { return ti * T - ti * (ti - 1) / 2; }
@@ -43,18 +38,9 @@ inline int64_t pair_tiles(int64_t N) {
 // totals.  `red` holds 4 * K doubles and is free again when the call returns.
 template <int K>
 __device__ __forceinline__ void block_sum_f64(double (&m)[K], double* red) {
-  const int lane = egnn_lane();
-  const int wave = egnn_wave_id();
 #pragma unroll
-  for (int q = 0; q < K; ++q) m[q] = wave_sum_f64(m[q]);
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < K; ++q) red[wave * K + q] = m[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < K; ++q) m[q] = ((red[q] + red[K + q]) + red[2 * K + q]) + red[3 * K + q];
-  __syncthreads();
+  for (int q = 0; q < K; ++q) m[q] = egnn_reduce::group_sum<EGNN_WAVE>(m[q]);
+  egnn_reduce::waves4_sum<egnn_reduce::SERIAL>(m, red);
 }
 
 // Which entries of the tile at (i0, j0) are pairs, in tile-local 32-bit form: entry (lr, lc) is row i0 + lr, column j0 + lc, and

@@ -13,8 +13,10 @@
 // (the rowsum term only for the distance kernels): one MFMA GEMM each (egnn_gemm_f32) plus the
 // row kernels below.  All reductions have a fixed order.
 #include "pair_tile.h"
+#include "block_reduce.h"
 
 using namespace egnn_pair;
+using namespace egnn_reduce;
 
 namespace {
 
@@ -54,7 +56,7 @@ __global__ __launch_bounds__(256) void gsp_fwd_kernel(const float* __restrict__ 
   const int wave = egnn_wave_id();
   const int wm = wave >> 1, wn = wave & 1;
   const bool dist = kernel >= K_L2;
-  float local = 0.f;
+  float local[1] = {0.f};
 #pragma unroll
   for (int tn = 0; tn < TS::TN; ++tn) {
     const int64_t c = j0 + acc_col<GB, GB>(wn, tn, lane);
@@ -71,7 +73,7 @@ __global__ __launch_bounds__(256) void gsp_fwd_kernel(const float* __restrict__ 
           const PairK ks = pair_kernel(kernel, as[tm][tn][r], nsi, nsj, row == c);
           const PairK kt = pair_kernel(kernel, at[tm][tn][r], nti, ntj, row == c);
           const float d = ks.k - kt.k;
-          local = fmaf(d, d, local);
+          local[0] = fmaf(d, d, local[0]);
           // dXs = Ws Xs (- rowsum(Ws) o Xs for l2/rbf), dXt likewise: Ws = c D w_s, Wt = -c D w_t
           Ws[row * S + c] = coef * d * ks.w;
           Wt[row * S + c] = -coef * d * kt.w;
@@ -80,28 +82,9 @@ __global__ __launch_bounds__(256) void gsp_fwd_kernel(const float* __restrict__ 
     }
   }
   // block reduction in a fixed order
-  float* red = smem;
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
-}
-
-__global__ __launch_bounds__(1024) void sum_partials_kernel(const float* __restrict__ partials, int64_t n, float scale,
-                                                            float* __restrict__ out) {
-  __shared__ float red[1024];
-  float s = 0.f;
-  for (int64_t i = threadIdx.x; i < n; i += 1024) s += partials[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = red[0] * scale;
+  float (*red)[256] = reinterpret_cast<float (*)[256]>(smem);
+  block_tree_sum<256>(local, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0][0];
 }
 
 __global__ __launch_bounds__(256) void rowsum_kernel(const float* __restrict__ W, int64_t ld, int64_t n, int64_t m,
@@ -141,17 +124,12 @@ __global__ __launch_bounds__(256) void bce_pair_fwd_kernel(const float* __restri
                                                            const float* __restrict__ t, int64_t total,
                                                            float* __restrict__ partials) {
   __shared__ float red[2][256];
-  float a = 0.f, b = 0.f;
+  float ab[2] = {0.f, 0.f};
   for (int64_t i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    a += bce_logits(x[i], y[i]);
-    b += bce_logits(x[i], sigmoidf_(t[i]));
+    ab[0] += bce_logits(x[i], y[i]);
+    ab[1] += bce_logits(x[i], sigmoidf_(t[i]));
   }
-  red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-    __syncthreads();
-  }
+  block_tree_sum<256>(ab, red);
   if (threadIdx.x == 0) { partials[blockIdx.x] = red[0][0]; partials[kBceBlocks + blockIdx.x] = red[1][0]; }
 }
 
@@ -197,7 +175,7 @@ extern "C" int egnn_gsp_fwd_f32(const float* xs, int64_t ld_s, int64_t Ps, const
   dispatch_vec4(vec4, [&](auto v4) {
     hipLaunchKernelGGL(gsp_fwd_kernel<v4.value>, dim3((unsigned)nblocks), dim3(256), 0, st, xs, ld_s, Ps, xt, ld_t, Pt, S, kernel, ns, nt, coef, Ws, Wt, partials);
   });
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(1024), 0, st, partials, nblocks, 1.f / ((float)S * (float)S), loss);
+  hipLaunchKernelGGL((sum_partials_kernel<1024, float>), dim3(1), dim3(1024), 0, st, partials, 0, nblocks, 1.f / ((float)S * (float)S), loss);
   return egnn_launch_status();
 }
 
@@ -226,19 +204,17 @@ extern "C" int egnn_bce_pair_fwd_f32(const float* logits, const float* labels, c
                                      float* out2, float* ws, void* stream) {
   EGNN_CHECK_ARG(total > 0 && logits && labels && teacher && out2 && ws);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t want = (total + 255) / 256;
-  const int nb = (int)(want < kBceBlocks ? want : kBceBlocks);
+  const int nb = (int)capped_blocks(total, 256, kBceBlocks);
   hipLaunchKernelGGL(bce_pair_fwd_kernel, dim3(nb), dim3(256), 0, st, logits, labels, teacher, total, ws);
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(1024), 0, st, ws, (int64_t)nb, 1.f / (float)total, out2);
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(1024), 0, st, ws + kBceBlocks, (int64_t)nb, 1.f / (float)total, out2 + 1);
+  hipLaunchKernelGGL((sum_partials_kernel<1024, float>), dim3(1), dim3(1024), 0, st, ws, 0, nb, 1.f / (float)total, out2);
+  hipLaunchKernelGGL((sum_partials_kernel<1024, float>), dim3(1), dim3(1024), 0, st, ws + kBceBlocks, 0, nb, 1.f / (float)total, out2 + 1);
   return egnn_launch_status();
 }
 
 extern "C" int egnn_bce_pair_bwd_f32(const float* logits, const float* labels, const float* teacher, int64_t total,
                                      const float* g_cls, const float* g_kd, float* dlogits, void* stream) {
   EGNN_CHECK_ARG(total > 0 && logits && labels && teacher && dlogits);
-  const int64_t want = (total + 255) / 256;
-  hipLaunchKernelGGL(bce_pair_bwd_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream, logits,
+  hipLaunchKernelGGL(bce_pair_bwd_kernel, dim3((unsigned)capped_blocks(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, logits,
                      labels, teacher, total, g_cls, g_kd, dlogits);
   return egnn_launch_status();
 }

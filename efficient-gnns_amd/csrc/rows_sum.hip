@@ -11,6 +11,7 @@
 // (the cut, the partial slots and the second pass: rows_runs.h): the group at a chunk's first position adds that chunk's src rows in
 // registers in ascending position; a second launch adds a long run's partial rows in ascending chunk order.
 #include "rows_runs.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -50,8 +51,7 @@ __global__ __launch_bounds__(THREADS) void rows_run_stats_kernel(const uint64_t*
   count_flags(keyed && !head, counters + 1);
   int len = 0;
   if (head) len = (int)(lower_bound(sorted, j + 1, S, (r + 1) << shift) - j);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) len = max(len, __shfl_xor(len, o));
+  len = egnn_reduce::group_max<EGNN_WAVE>(len);
   if (egnn_lane() == 0 && len > 0) atomicMax(counters + 3, len);
 }
 

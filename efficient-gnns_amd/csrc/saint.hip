@@ -11,6 +11,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "bn_common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -115,8 +116,7 @@ __global__ void __launch_bounds__(kThreads) induced_count_wave_kernel(RowView v,
     if (e - b > kLongRow) continue;                     // the workgroup kernel writes this row
     int cnt = 0;
     for (int64_t p = b + lane; p < e; p += kWavePass) cnt += flag[col[p]] ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    cnt = egnn_reduce::group_sum<EGNN_WAVE>(cnt);
     if (lane == 0) counts[r] = cnt;
   }
 }
@@ -133,8 +133,7 @@ __global__ void __launch_bounds__(kThreads) induced_count_block_kernel(RowView v
     if (e - b <= kLongRow) continue;                    // uniform over the workgroup
     int cnt = 0;
     for (int64_t p = b + threadIdx.x; p < e; p += kBlockPass) cnt += flag[col[p]] ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    cnt = egnn_reduce::group_sum<EGNN_WAVE>(cnt);
     if (lane == 0) wave_cnt[w] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -36,6 +36,7 @@
 // A key whose position or row does not fit S / n_rows (keys built for other operands) is skipped and never used as an address.
 // UNSPECIFIED inputs: NaN, +inf, and a run whose values are all -inf.
 #include "rows_runs.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -48,12 +49,6 @@ constexpr int STEPS = (int)(CHUNK / GL);      // positions per lane
 static_assert(CHUNK % GL == 0 && EGNN_WAVE % GL == 0, "a chunk is a whole number of group steps");
 enum { SOFTMAX = 0, LOG_SOFTMAX = 1 };
 enum { STATS = 0, DOT = 1, SUM = 2 };        // what the walk folds: (max, sum of exp) of a | sum of a * b | sum of a
-
-__device__ __forceinline__ float group_max(float v) {
-#pragma unroll
-  for (int o = GL / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 
 // rows that no key names: 0 in every statistic (one thread per row)
 __global__ __launch_bounds__(THREADS) void ssm_absent_kernel(float* __restrict__ row_a, float* __restrict__ row_b, int64_t n_rows,
@@ -113,7 +108,7 @@ __device__ __forceinline__ void walk_chunk(int64_t j0, bool head, int sub, float
 #pragma unroll
         for (int u = 0; u < STEPS; ++u)
           if (ok[u]) m = fmaxf(m, x[u][i]);
-        m = group_max(m);
+        m = egnn_reduce::group_max<GL>(m);
         float z = 0.f;
 #pragma unroll
         for (int u = 0; u < STEPS; ++u)

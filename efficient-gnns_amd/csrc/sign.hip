@@ -13,6 +13,7 @@
 // backward accumulate in registers.  Reductions: registers -> LDS tree per workgroup -> one partial per (stripe, column) in the
 // workspace -> a finalize launch that folds the stripes in index order.  Every order is fixed: results are bit-equal from run to run.
 #include "bn_common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(THREADS) void prelu_drop_bwd_kernel(SegTable t, Geo
                                                                  const float* __restrict__ dy, int64_t ld_dy, float* __restrict__ dz,
                                                                  int64_t ld_dz, float* __restrict__ ws) {
   __shared__ float s_col[THREADS * VEC];
-  __shared__ float s_da[THREADS];
+  __shared__ float s_da[1][THREADS];
   const Where w = where<VEC>(g);
   float cs[VEC], da = 0.f;
 #pragma unroll
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(THREADS) void prelu_drop_bwd_kernel(SegTable t, Geo
   const int TX = 1 << g.lg_tx, tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> g.lg_tx;
 #pragma unroll
   for (int k = 0; k < VEC; ++k) s_col[threadIdx.x * VEC + k] = cs[k];
-  s_da[threadIdx.x] = da;
+  s_da[0][threadIdx.x] = da;
   __syncthreads();
   for (int s = (THREADS >> g.lg_tx) >> 1; s > 0; s >>= 1) {
     if (ty < s) {
@@ -192,23 +193,20 @@ __global__ __launch_bounds__(THREADS) void prelu_drop_bwd_kernel(SegTable t, Geo
     }
     __syncthreads();
   }
-  for (int s = THREADS >> 1; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) s_da[threadIdx.x] += s_da[threadIdx.x + s];
-    __syncthreads();
-  }
+  egnn_reduce::block_tree_fold<THREADS, 1>(s_da);
   const int64_t HC = (int64_t)g.H * g.Cs;
   if (ty == 0 && w.active) {
     float* o = ws + (int64_t)blockIdx.y * HC + (int64_t)w.h * g.Cs + w.c;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) o[k] = s_col[tx * VEC + k];
   }
-  if (threadIdx.x == 0) ws[(int64_t)g.stripes * HC + (int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s_da[0];
+  if (threadIdx.x == 0) ws[(int64_t)g.stripes * HC + (int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s_da[0][0];
 }
 
 // blocks [0, col_blocks): dbias[c] = the stripes' partials of column c in stripe order; block col_blocks + h: da[h]
 __global__ __launch_bounds__(THREADS) void prelu_drop_finalize_kernel(Geo g, const float* __restrict__ ws, int col_blocks,
                                                                       float* __restrict__ da, float* __restrict__ dbias) {
-  __shared__ float s[THREADS];
+  __shared__ float s[1][THREADS];
   const int64_t HC = (int64_t)g.H * g.Cs;
   if ((int)blockIdx.x < col_blocks) {
     const int64_t c = (int64_t)blockIdx.x * THREADS + threadIdx.x;
@@ -221,18 +219,13 @@ __global__ __launch_bounds__(THREADS) void prelu_drop_finalize_kernel(Geo g, con
   const int h = (int)blockIdx.x - col_blocks;
   const float* part = ws + (int64_t)g.stripes * HC;
   const int per_stripe = g.H * g.chunks, items = g.stripes * g.chunks;
-  float acc = 0.f;
+  float acc[1] = {0.f};
   for (int i = threadIdx.x; i < items; i += THREADS) {
     const int st = i / g.chunks, k = i - st * g.chunks;
-    acc += part[(int64_t)st * per_stripe + h * g.chunks + k];
+    acc[0] += part[(int64_t)st * per_stripe + h * g.chunks + k];
   }
-  s[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = THREADS >> 1; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) da[h] = s[0];
+  egnn_reduce::block_tree_sum<THREADS>(acc, s);
+  if (threadIdx.x == 0) da[h] = s[0][0];
 }
 
 bool mult4(int64_t v) { return (v & 3) == 0; }

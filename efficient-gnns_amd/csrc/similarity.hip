@@ -20,8 +20,10 @@
 //      sum a = S_a + n c_a,   sum a^2 = S_aa + 2 c_a S_a + n c_a^2,   sum ab = S_ab + c_a S_b + c_b S_a + n c_a c_b,
 // so that the float64 cancellation downstream sees inputs good to fp32 RELATIVE TO THE SPREAD, not to the mean.
 #include "pair_tile.h"
+#include "block_reduce.h"
 
 using namespace egnn_pair;
+using namespace egnn_reduce;
 
 namespace {
 
@@ -115,23 +117,11 @@ __global__ __launch_bounds__(1024) void moments_finalize_kernel(const double* __
 #pragma unroll
     for (int q = 0; q < K; ++q) m[q] += partials[i * K + q];
   }
-#pragma unroll
-  for (int q = 0; q < K; ++q) red[q][threadIdx.x] = m[q];
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-#pragma unroll
-      for (int q = 0; q < K; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  block_tree_sum<1024>(m, red);
   if (threadIdx.x < K) out[threadIdx.x] = red[threadIdx.x][0];
 }
 
-inline int64_t vec_blocks(int64_t n) {
-  const int64_t want = (n + 255) / 256;
-  return want < kVecBlocks ? want : kVecBlocks;
-}
+inline int64_t vec_blocks(int64_t n) { return capped_blocks(n, 256, kVecBlocks); }
 
 
 // ------------------------------------------------------------------------------------------------ kernel (RBF) CKA
@@ -351,11 +341,8 @@ __global__ __launch_bounds__(256) void rbf_rowsum_kernel(const float* __restrict
           }
         }
         // the 32 lanes of a half-wave hold the same row: 64 entries per sum
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) {
-          ss += __shfl_xor(ss, o);
-          st += __shfl_xor(st, o);
-        }
+        ss = group_sum<32>(ss);
+        st = group_sum<32>(st);
         if ((lane & 31) == 0) {
           racc[wn][0][lr] += (double)ss;
           racc[wn][1][lr] += (double)st;

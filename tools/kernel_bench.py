@@ -2,6 +2,7 @@
 """Per-kernel timings on one MI355X (HIP events on the launch stream), written as JSON lines.
 
     python tools/kernel_bench.py [--out gpurun_out/kernel_bench.jsonl] [--quick]
+                                 [--only spmm,gemm,nce,reduce,misc] [--lib PATH/libegnn_hip.so]
 """
 from __future__ import annotations
 
@@ -35,6 +36,22 @@ def timeit(fn, iters=20, warmup=3):
     return a.elapsed_time(b) * 1e-3 / iters
 
 
+def median_us(fn, reps=200, warmup=10):
+    """median of per-call device times in microseconds (one event pair per call)"""
+    for _ in range(warmup):
+        fn()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) * 1e3)
+    times.sort()
+    return round(times[len(times) // 2], 2)
+
+
 def emit(f, **kw):
     line = json.dumps(kw)
     print(line, flush=True)
@@ -46,8 +63,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "kernel_bench.jsonl"))
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", default="", help="comma list of sections: spmm,gemm,nce,misc")
+    ap.add_argument("--only", default="", help="comma list of sections: spmm,gemm,nce,reduce,misc")
+    ap.add_argument("--lib", default=None, help="another build of libegnn_hip.so (same ABI version) instead of the in-tree one")
     args = ap.parse_args()
+    if args.lib:
+        E._lib.LIB_PATH = os.path.abspath(args.lib)                   # before the first load
     only = set(filter(None, args.only.split(",")))
     want = lambda sec: not only or sec in only  # noqa: E731
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -129,6 +149,36 @@ def main():
         fl = 2.0 * S * S * P
         emit(f, what="nce", S=S, P=P, fwd_us=round(t_f * 1e6, 1), fwd_TF=round(fl / t_f / 1e12, 1), fwd_bwd_us=round(t_fb * 1e6, 1),
              fwd_bwd_TF=round(3 * fl / t_fb / 1e12, 1), torch_fwd_bwd_us=round(t_t * 1e6, 1))
+
+    # ---- the loss / metric forwards that end in the fixed-order partials finalize (csrc/block_reduce.h), at arxiv sizes ----------
+    if want('reduce'):
+        import efficient_gnns_amd.ops_edge as ops_edge
+        import efficient_gnns_amd.ops_pairwise as ops_pairwise
+        with torch.no_grad():
+            fs, fs2, ft = torch.randn(n_tr, 256, device=DEV), torch.randn(n_tr, 256, device=DEV), torch.randn(n_tr, 750, device=DEV)
+            lg, tl = torch.randn(n_tr, 40, device=DEV), torch.randn(n_tr, 40, device=DEV)
+            lb = torch.randint(0, 40, (n_tr,), device=DEV)
+            big, g256 = torch.randn(n, 40, device=DEV), torch.randn(n, 256, device=DEV)
+            yb = torch.randint(0, 40, (n,), device=DEV)
+            split = {k: v.to(DEV) for k, v in data.split_idx.items()}
+            xb, tb = torch.randn(44_906, 121, device=DEV), torch.randn(44_906, 121, device=DEV)      # the PPI logit shape
+            yl = (torch.rand(44_906, 121, device=DEV) < 0.3).float()
+            ei = torch.stack(adj.coo()[:2])
+            ei = ei[:, (ei < n_tr).all(0)]                                                          # edges among the first n_tr nodes
+            sub = torch.randperm(n, device=DEV)[:4096]
+            cases = {
+                "fitnet_loss": lambda: ops.fitnet_loss(fs, fs2),
+                "at_loss": lambda: ops.at_loss(fs, ft),
+                "kd_criterion_fwd": lambda: E.kd_criterion(lg, lb, tl),
+                "bce_pair_fwd": lambda: ops_pairwise.bce_with_logits_pair(xb, yl, tb),
+                "lsp_loss_fwd": lambda: ops_edge.lsp_loss(fs, ft, ei, "cosine"),
+                "gsp_loss_fwd": lambda: ops_pairwise.gsp_loss(g256, g256, sub, "cosine"),
+                "colsum_40": lambda: ops.colsum(big),
+                "colsum_256": lambda: ops.colsum(g256),
+                "split_accuracy": lambda: ops.split_accuracy(big, yb, split),
+            }
+            for name, fn in cases.items():
+                emit(f, what="reduce", kernel=name, median_us=median_us(fn))
 
     # ---- elementwise neighbours of the convs (next row f-1), torch ops today -----------------------------
     if not want('misc'):

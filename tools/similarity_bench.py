@@ -19,7 +19,7 @@ Warm-up rounds first, then alternating repeats timed with device events; peak by
 what was allocated when the call began.  Prints a table and one JSON line.
 
   python tools/similarity_bench.py [--n 29799] [--ds 256] [--dt 750] [--degree 8] [--reps 5] [--warmup 2]
-                                   [--metrics global,local,cka,kcka] [--kcka-torch-n 8192]
+                                   [--metrics global,local,cka,kcka] [--kcka-torch-n 8192] [--lib PATH/libegnn_hip.so]
 """
 import argparse
 import json
@@ -38,6 +38,8 @@ def main(args):
     import bench  # noqa: E402  (cap_cpu_threads)
     import efficient_gnns_amd as E
 
+    if args.lib:
+        E._lib.LIB_PATH = os.path.abspath(args.lib)                   # before the first load
     bench.cap_cpu_threads()
     assert torch.cuda.is_available(), "similarity_bench needs a GPU"
     dev = torch.device("cuda", 0)
@@ -168,4 +170,5 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--metrics", default="global,local,cka,kcka", help="comma-separated subset of global, local, cka, kcka")
     ap.add_argument("--kcka-torch-n", type=int, default=8192, help="rows of the kernel-CKA comparison with the torch-op form")
+    ap.add_argument("--lib", default=None, help="another build of libegnn_hip.so (same ABI version) instead of the in-tree one")
     sys.exit(main(ap.parse_args()))
