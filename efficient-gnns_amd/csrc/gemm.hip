@@ -363,13 +363,21 @@ int launch_one(const GemmArgs& g, dim3 grid, hipStream_t st) {
   return launch_dyn_lds<gemm_kernel<BM, BN, AMAJ, BMAJ, VEC4, GATHER, SPLIT>>(grid, dim3(256), shm, st, g);
 }
 
+// what the last egnn_gemm_* call of this thread ran (egnn_gemm_last_route; encoding: include/egnn_hip.h).  gemm_impl is its only writer;
+// the tile and pipeline of the general kernel are noted by launch_tile, which chooses them.
+thread_local int g_last_route = 0;
+thread_local int g_tile_form = 0;
+
 template <int BM, int BN, int AMAJ, int BMAJ, int GATHER = 0>
 int launch_tile(const GemmArgs& g, bool vec4, hipStream_t st) {
+  static_assert(BM == 128 && (BN == 64 || BN == 128), "egnn_gemm_last_route names these two tiles");
   const int64_t tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
   if (tiles > 0x7fffffffLL) return EGNN_EINVAL;
   dim3 grid((unsigned)tiles, (unsigned)g.split_k);
+  g_tile_form = BN == 64 ? 7 : 8;
   if constexpr (BM % 128 == 0 && BN % 128 == 0) {
     if (g.split_pipe) {
+      g_tile_form |= 1 << 10;
       return vec4 ? launch_one<BM, BN, AMAJ, BMAJ, true, GATHER, true>(g, grid, st)
                   : launch_one<BM, BN, AMAJ, BMAJ, false, GATHER, true>(g, grid, st);
     }
@@ -391,6 +399,7 @@ static int gemm_impl(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, 
                      const int64_t* a_rows, const float* B, int64_t ldb, const int64_t* b_rows, const float* bias, float* C,
                      int64_t ldc, int split_k, float* ws, size_t ws_bytes, void* stream, int flags = 0, const float* addend = nullptr,
                      int64_t ld_add = 0) {
+  g_last_route = 0;
   EGNN_CHECK_ARG(M >= 0 && N >= 0 && K >= 0);
   if (M == 0 || N == 0) return EGNN_OK;
   EGNN_CHECK_ARG(A && B && C && ldc >= N);
@@ -402,14 +411,21 @@ static int gemm_impl(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, 
   if (!a_rows && !b_rows && flags == 0 && !addend) {   // class-count-wide shapes: dedicated HBM-bound kernels (gemm_skinny.hip); rc 1 = shape not taken
     const int kind = skinny_kind(trans_a, trans_b, M, N, K, bias != nullptr);
     int rc = 1;
+    int form = kind == 1 ? 1 : kind + 1;   // kinds 2, 3, 4 are forms 3, 4, 5
     if (kind == 1) {
       rc = egnn_skinny_fwd_tile(A, lda, B, ldb, trans_b, bias, C, ldc, M, N, K, alpha, st0);
-      if (rc == 1) rc = egnn_skinny_fwd(A, lda, B, ldb, trans_b, bias, C, ldc, M, N, K, alpha, st0);
+      if (rc == 1) {
+        form = 2;
+        rc = egnn_skinny_fwd(A, lda, B, ldb, trans_b, bias, C, ldc, M, N, K, alpha, st0);
+      }
     }
     else if (kind == 2) rc = egnn_skinny_dx(A, lda, B, ldb, trans_b, C, ldc, M, N, K, alpha, st0);
     else if (kind == 3) rc = egnn_skinny_dw(A, lda, B, ldb, K, M, N, alpha, C, ldc, 1, ws, ws_bytes / sizeof(float), st0);
     else if (kind == 4) rc = egnn_skinny_dw(B, ldb, A, lda, K, N, M, alpha, C, 1, ldc, ws, ws_bytes / sizeof(float), st0);
-    if (rc != 1) return rc;
+    if (rc != 1) {
+      g_last_route = form;
+      return rc;
+    }
   }
   if (split_k < 1) split_k = 1;
   int64_t ksteps = (K + BK - 1) / BK;
@@ -435,10 +451,12 @@ static int gemm_impl(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, 
     g.planes = reinterpret_cast<const u32x4*>(planes);
     const int64_t tiles = ((M + 127) / 128) * (N / 128);
     if (tiles > 0x7fffffffLL) return EGNN_EINVAL;
+    g_last_route = 6 | (wide ? 1 << 9 : 0) | 1 << 10 | 1 << 16;   // (A by 16-byte DMA rows whatever B's alignment: no vec4 bit)
     rc = launch_dyn_lds<gemm_dma_kernel>(dim3((unsigned)tiles), dim3(256), (size_t)DmaTile::SMEM_BYTES, st, g);
     if (rc != EGNN_OK) return rc;
     return egnn_launch_status();
   }
+  g_tile_form = 0;
   if (a_rows) {
     rc = bmaj == KMAJOR ? launch_major<KMAJOR, KMAJOR, 1>(g, vec4, st) : launch_major<KMAJOR, MNMAJOR, 1>(g, vec4, st);
   } else if (b_rows) {
@@ -447,6 +465,8 @@ static int gemm_impl(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, 
   else if (amaj == KMAJOR) rc = launch_major<KMAJOR, MNMAJOR>(g, vec4, st);
   else if (bmaj == KMAJOR) rc = launch_major<MNMAJOR, KMAJOR>(g, vec4, st);
   else rc = launch_major<MNMAJOR, MNMAJOR>(g, vec4, st);
+  if (g_tile_form)
+    g_last_route = g_tile_form | (vec4 ? 1 << 8 : 0) | (wide ? 1 << 9 : 0) | (a_rows ? 1 << 11 : 0) | (b_rows ? 1 << 12 : 0) | (split_k << 16);
   if (rc != EGNN_OK) return rc;
   if (split_k > 1) {
     const int64_t blocks = (M * N + 63) / 64;
@@ -455,10 +475,14 @@ static int gemm_impl(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, 
   return egnn_launch_status();
 }
 
+extern "C" int egnn_gemm_last_route(void) { return g_last_route; }
+
 extern "C" size_t egnn_gemm_ws_floats(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, int split_k) {
   size_t need = split_k > 1 ? (size_t)split_k * (size_t)M * (size_t)N : 0;
   const int kind = skinny_kind(trans_a, trans_b, M, N, K, false);
-  if (kind == 0 && dma_form(trans_a, M, N, K, split_k, false)) {   // tile-packed planes of B for the DMA form (gemm3.h)
+  // tile-packed planes of B for the DMA form (gemm3.h).  Also where the bias-free call would be a skinny form (K = 64 is skinny dx):
+  // this query does not know whether the call carries a bias, and with one the DMA form would find no planes and fall through
+  if (dma_form(trans_a, M, N, K, split_k, false)) {
     const size_t dma = dma_ws_bytes(N, K) / sizeof(float) + 1;
     if (dma > need) need = dma;
   }

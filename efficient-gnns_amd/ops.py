@@ -914,6 +914,13 @@ def gemm_raw(a: Tensor, b: Tensor, trans_a: bool = False, trans_b: bool = False,
     return c
 
 
+def gemm_last_route() -> int:
+    """Which kernel this thread's last gemm_raw call ran (egnn_gemm_last_route; encoding in include/egnn_hip.h): low byte = form
+    (1 skinny_fwd_tile ... 8 general 128x128), bit 8 vec4, bit 9 wide_store, bit 10 split pipe, bits 11 / 12 gather A / B, bits 16+ the
+    split_k in effect.  0 when the call launched nothing."""
+    return int(_lib.load().egnn_gemm_last_route())
+
+
 def bn_fold(weight: Tensor, bias: Tensor | None, bn: "torch.nn.BatchNorm1d"):
     """(W', b') with  relu(bn_eval(x W + b)) == relu(x W' + b')  (egnn_bn_fold_f32): an eval-mode BatchNorm1d folded into the
     [in, out] weight and the bias of the layer in front of it -- also across a (linear) aggregation between the two."""

@@ -289,6 +289,19 @@ int egnn_gemm_f32(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, flo
                   const float* bias, float* C, int64_t ldc,
                   int split_k, float* ws, size_t ws_bytes, void* stream);
 
+/* Which kernel the last egnn_gemm_f32 / _ex_ / _add_ / _rows_ call of the calling thread ran (host-only, thread-local; 0 after a
+ * call that launched nothing: an empty output or an error found before the dispatch).  Written at the one place where the
+ * dispatcher commits to a kernel, so a test can assert the route it means to exercise:
+ *   bits 0-7   form: 1 skinny_fwd_tile (K = 256 rows through an LDS tile), 2 skinny_fwd, 3 skinny_dx, 4 skinny_dw with the narrow
+ *              matrix = A, 5 skinny_dw with the narrow matrix = B, 6 DMA form, 7 general 128x64 tile, 8 general 128x128 tile
+ *   bit 8      vec4: 16-byte operand loads (forms 7, 8)
+ *   bit 9      wide_store: 16-byte stores through LDS (forms 6, 7, 8; for split_k > 1 it describes the partial store)
+ *   bit 10     products on the bf16 split pipe (form 6 always; form 8 unless EGNN_GEMM_PIPE=f32; the 128x64 tile has no split form)
+ *   bit 11     row gather fused into A (a_rows);   bit 12   row gather fused into B (b_rows)
+ *   bits 16+   the split_k in effect after clamping to the number of k-steps (forms 6, 7, 8; >= 1)
+ * The skinny forms (1-5) report the form alone. */
+int egnn_gemm_last_route(void);
+
 /* egnn_gemm_f32 with an epilogue option: flags bit 0 (1) = C = max(alpha op(A) op(B) + bias, 0) -- the ReLU that follows an
  * eval-mode BatchNorm whose scale / shift were folded into B and bias (egnn_bn_fold_f32). */
 int egnn_gemm_ex_f32(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, float alpha, const float* A, int64_t lda,

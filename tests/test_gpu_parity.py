@@ -369,6 +369,8 @@ def test_gemm_dma_form_tall_a_small_b(M, N, K, tb):
     scale = (a.double().abs() @ (w.double().abs().t() if tb else w.double().abs())) + bias.double().abs()
     for relu in (False, True):
         y = ops.gemm_raw(a, w, False, tb, bias=bias, relu=relu)
+        if not os.environ.get("EGNN_GEMM_PIPE", "").startswith("f"):
+            assert ops.gemm_last_route() & 255 == 6, "not the DMA form"
         r = torch.relu(ref) if relu else ref
         assert float(((y.double() - r).abs() / scale).max()) < 1e-6
         assert torch.equal(y, ops.gemm_raw(a, w, False, tb, bias=bias, relu=relu))
@@ -396,6 +398,7 @@ def test_gemm_skinny_output_layer_forms(M, N, K, tb):
     bias = torch.randn(N, generator=g)
     ref = x.double() @ (w.double().t() if tb else w.double()) + bias.double()
     y = ops.gemm_raw(x.to(DEV), w.to(DEV), False, tb, bias.to(DEV))
+    assert ops.gemm_last_route() == (1 if K == 256 else 2)        # the LDS-tile form takes 256-wide rows, skinny_fwd the others
     close(y, ref, rtol=1e-5, atol_scale=1e-6)
     y2 = ops.gemm_raw(x.to(DEV), w.to(DEV), False, tb, None, alpha=0.5)
     close(y2, 0.5 * (ref - bias.double()), rtol=1e-5, atol_scale=1e-6)
@@ -405,8 +408,10 @@ def test_gemm_skinny_output_layer_forms(M, N, K, tb):
     close(dx, gy.double() @ (w.double() if tb else w.double().t()), rtol=1e-5, atol_scale=1e-6)
     # dW: both orientations of a^T b with the node count as the reduction
     dw_a = ops.gemm_raw(x.to(DEV), gy.to(DEV), True, False)      # [K, N]  (GCNConv weight gradient)
+    assert ops.gemm_last_route() & 255 == (5 if K % 64 == 0 else 7)   # the wide matrix needs whole 64-column slices
     close(dw_a, x.double().t() @ gy.double(), rtol=2e-5, atol_scale=2e-6)
     dw_b = ops.gemm_raw(gy.to(DEV), x.to(DEV), True, False)      # [N, K]  (nn.Linear weight gradient)
+    assert ops.gemm_last_route() & 255 == (4 if K % 64 == 0 else 7)
     close(dw_b, gy.double().t() @ x.double(), rtol=2e-5, atol_scale=2e-6)
     assert torch.equal(dw_a, ops.gemm_raw(x.to(DEV), gy.to(DEV), True, False)), "fixed reduction order => bit-stable"
 
