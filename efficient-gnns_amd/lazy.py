@@ -16,6 +16,9 @@ module's running-statistics update) and returns a ``LazyBnAct``: a tensor-like o
   * answers ``lazy[idx]`` for a 1-D int64 index with a ``LazyRows`` that a following ``Linear`` turns into the gather-fused GEMM
     (``ops.linear_rows``: no ``[N_tr, 256]`` copy forward, no zero-fill + scatter backward).
 
+``nn.MessagePassing`` hands out a lifted ``x_j`` as a ``LazyRows`` too; times a per-edge weight it becomes a ``LazyWeightedRows``, which
+``ops.scatter`` (sum / add / mean) runs as ONE ``ops.gather_scatter`` -- lift, weight and aggregation without an [E, C] tensor.
+
 Inference (``model.eval()`` under ``no_grad``): a ``GCNConv`` that has been SEEN feeding a ``BatchNorm1d`` (``accel`` learns the association
 from the first forward; it only decides what is deferred) hands out a ``LazyConv``; the eval-mode BatchNorm turns it into a ``LazyFold``
 that absorbs the ReLU and is formed as ONE pass -- the BatchNorm folded into the conv's weights, the ReLU in the last kernel's store.
@@ -33,6 +36,11 @@ from . import _cache, ops
 
 
 ACCEL_ACTIVE = False   # set by dropin/accel.py's enable() / disable(): torch.nn.Linear.forward consumes a LazyRows
+_MUL_FUNCS = (torch.mul, torch.multiply, torch.Tensor.mul, torch.Tensor.multiply, torch.Tensor.__mul__, torch.Tensor.__rmul__)
+
+
+def _on_gpu(t) -> bool:
+    return t.is_cuda
 
 
 def materialise(x, pick=None):
@@ -270,7 +278,59 @@ class LazyRows(_TensorLike):
         # (accel only defers GPU indices; rows of a CPU tensor are torch's own indexing, which has x[idx]'s rules by definition)
         return ops.take_rows(base, idx, duplicates="sum") if isinstance(idx, ops.RowsPlan) or idx.is_cuda else base[idx]
 
+    def _edge_weight(self, other):
+        """True when ``rows * other`` is a per-edge weight ``ops.gather_scatter`` takes: a float32 GPU tensor [E, 1] (2-D rows), [E, H, 1]
+        or [E, 1, 1] (rows [E, H, D]) -- the shapes torch broadcasts along the edges -- a 0-dim one or a Python number."""
+        if self._value is not None or not ops.FUSE_LAZY_ROWS or not isinstance(self._base, torch.Tensor) or self._base.dim() not in (2, 3):
+            return False
+        if isinstance(other, (int, float)) and not isinstance(other, bool):
+            return _on_gpu(self._base)
+        if not (type(other) in (torch.Tensor, torch.nn.Parameter) and other.dtype == torch.float32 and _on_gpu(other) and _on_gpu(self._base)):
+            return False
+        E, rest = self._idx.numel(), tuple(self._base.shape[1:])
+        if other.dim() == 0:
+            return True
+        if len(rest) == 1:
+            return tuple(other.shape) == (E, 1)
+        return tuple(other.shape) in ((E, rest[0], 1), (E, 1, 1))
+
+    def __mul__(self, other):
+        if self._edge_weight(other):
+            return LazyWeightedRows(self, other)
+        return self._egnn_materialise() * materialise(other)
+
+    __rmul__ = __mul__
+
+    @classmethod
+    def _absorb(cls, func, args, kwargs):
+        if func in _MUL_FUNCS and len(args) == 2 and not kwargs:
+            a, b = args
+            if isinstance(b, LazyRows) and not isinstance(a, _TensorLike):
+                a, b = b, a
+            if isinstance(a, LazyRows) and not isinstance(b, _TensorLike) and a._edge_weight(b):
+                return LazyWeightedRows(a, b)
+        return NotImplemented
+
+    def _egnn_gather_scatter(self, dst, dim_size, reduce, weight=None):
+        """``ops.scatter`` of these rows (times ``weight``) as one ``ops.gather_scatter``; None when the rows exist already or the
+        base is not a float32 GPU tensor (the caller then forms them)."""
+        if self._value is not None or not (isinstance(self._idx, torch.Tensor) and _on_gpu(self._idx)):
+            return None
+        base = self._formed_base()
+        if not (isinstance(base, torch.Tensor) and _on_gpu(base) and base.dtype == torch.float32 and base.dim() >= 2):
+            return None
+        E = self._idx.numel()
+        if isinstance(weight, (int, float)):
+            weight = torch.full((E,), float(weight), dtype=torch.float32, device=base.device)
+        elif weight is not None and weight.dim() == 0:
+            weight = weight.expand(E)
+        elif weight is not None and weight.dim() == 3 and weight.shape[1] == 1:
+            weight = weight.reshape(E)
+        return ops.gather_scatter(base, self._idx if self._plan is None else self._plan(), dst, dim_size, weight, reduce)
+
     def linear(self, weight, bias):
+        if len(self.shape) != 2:          # rows [E, H, D]: F.linear acts on the last axis of the formed rows
+            return F.linear(self._egnn_materialise(), weight, bias)
         base = self._formed_base()
         # ``const_base``: the gathered-from tensor is a leaf outside autograd (accel's deferred constant gather): its rows as once-cut planes
         const = bool(self._const and not base.requires_grad and base.grad_fn is None)
@@ -286,4 +346,30 @@ class LazyRows(_TensorLike):
     def __getitem__(self, idx):
         if isinstance(idx, torch.Tensor) and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_cuda and self._value is None:
             return LazyRows(self._base, self._composed(idx), self._const, self._base_version)
+        return self._egnn_materialise()[idx]
+
+
+class LazyWeightedRows(_TensorLike):
+    """``rows * weight`` for an unformed ``LazyRows`` and a per-edge weight (``LazyRows._edge_weight``), not multiplied yet: the
+    messages of a GCN-style (``edge_weight.view(-1, 1) * x_j``) or attention (``x_j * alpha.unsqueeze(-1)``) conv.  ``ops.scatter`` with
+    a summing reduce consumes it as ONE ``ops.gather_scatter`` -- no [E, C] tensor forward or backward; every other consumer (a second
+    multiply included) gets exactly ``take_rows(...) * weight``."""
+
+    def __init__(self, rows, weight):
+        self._rows, self._weight, self._value = rows, weight, None
+
+    shape = property(lambda self: self._rows.shape)
+    device = property(lambda self: self._rows.device)
+
+    def _egnn_materialise(self, pick=None):
+        if self._value is None:
+            self._value = self._rows._egnn_materialise() * self._weight
+        return self._value if pick is None else self._value[pick]
+
+    def _egnn_gather_scatter(self, dst, dim_size, reduce):
+        if self._value is not None:
+            return None
+        return self._rows._egnn_gather_scatter(dst, dim_size, reduce, self._weight)
+
+    def __getitem__(self, idx):
         return self._egnn_materialise()[idx]

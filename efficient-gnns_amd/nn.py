@@ -540,6 +540,18 @@ def running_plan(index, n=None, what: str = "num_nodes"):
     return None
 
 
+def running_end_plan(index, n, what: str = "num_nodes"):
+    """The plan of the running ``propagate`` call that has the tensor ``index`` as EITHER endpoint (identity, innermost call first) over
+    ``n`` nodes, None when there is none: how ``ops.gather_scatter`` on a call's own ``edge_index[0]`` / ``edge_index[1]`` walks the
+    keys the lift, the softmax and the aggregation share."""
+    for call, _ in reversed(_MP_RUNNING):
+        for end in (0, 1):
+            if call.ends[end] is not None and index is call.ends[end]:
+                call.see(end, n, what)
+                return call.plan(end)
+    return None
+
+
 class _Propagation:
     """One ``propagate`` call: the two endpoint id vectors (0: source side, 1: target side of ``edge_index``), the node counts seen so
     far, and AT MOST ONE deferred ``ops.rows_plan`` per endpoint, built when first asked for and shared by the lift (``x_j`` / ``x_i``),
@@ -570,8 +582,10 @@ class _Propagation:
         self.see(end, t.shape[0], what)
         _lib.require_gpu(t)
         idx = self.ends[end]
-        if lazy.ACCEL_ACTIVE and t.dim() == 2 and t.dtype == torch.float32 and idx.numel() > 0:
-            # under accel: not gathered yet -- a Linear in `message` runs the gather-fused GEMM (ops.linear_rows), anything else forms the rows
+        if lazy.ACCEL_ACTIVE and t.dtype == torch.float32 and idx.numel() > 0 and (
+                t.dim() == 2 or (ops.FUSE_LAZY_ROWS and t.dim() == 3 and node_dim == 0 and t.is_contiguous())):
+            # under accel: not gathered yet -- a Linear in `message` runs the gather-fused GEMM (ops.linear_rows), a per-edge weight and
+            # the aggregation run as one walk (ops.gather_scatter; [N, H, D] too: the heads of an attention conv), anything else forms the rows
             return lazy.LazyRows(t, idx, plan=lambda: self.plan(end))
         return ops.take_rows(t, self.plan(end))
 
@@ -601,7 +615,10 @@ class MessagePassing(nn.Module):
     raised.  ``utils.softmax(alpha, index, ptr, size_i)`` on [E, heads] scores inside ``message`` (and the ``torch_scatter`` softmax
     functions) finds the running call through ``running_plan`` and walks the target side's plan: no plan of its own, no host read.
     Under ``accel`` a lifted 2-D fp32 tensor is handed out as ``lazy.LazyRows``: ``self.lin(x_j)`` runs as the gather-fused
-    ``ops.linear_rows``.  GPU only, like every operator of the package."""
+    ``ops.linear_rows``.  With the default ``message`` and ``aggregate`` and ``aggr`` add / sum / mean, lift and aggregation are ONE walk
+    (``ops.gather_scatter``, bit-equal to the two steps); under ``accel`` so are ``edge_weight.view(-1, 1) * x_j`` and, on [N, H, D] node
+    tensors (``node_dim=0``), ``x_j * alpha.unsqueeze(-1)`` (``lazy.LazyWeightedRows``): no [E, C] tensor forward or backward.  GPU only,
+    like every operator of the package."""
 
     def __init__(self, aggr: str = "add", flow: str = "source_to_target", node_dim: int = -2):
         super().__init__()
@@ -694,6 +711,29 @@ class MessagePassing(nn.Module):
                 raise TypeError(f"MessagePassing.propagate: `{fn}` needs `{name}`, which was not given")
         return out
 
+    def _mp_default_fused(self, call: _Propagation, kwargs: dict):
+        """The default ``message`` (``x_j``) under the default ``aggregate`` with a summing ``aggr``: lift and aggregation as ONE walk
+        (``ops.gather_scatter``, bit-equal to ``ops.scatter(ops.take_rows(...))``), no [E, C] tensor.  None: the general path runs (and
+        raises what it raises for operands it does not take)."""
+        cls = type(self)
+        if not (ops.FUSE_LAZY_ROWS and cls.message is MessagePassing.message and cls.aggregate is MessagePassing.aggregate
+                and self.aggr in ("add", "sum", "mean") and "x" in kwargs):
+            return None
+        j, i = (0, 1) if self.flow == "source_to_target" else (1, 0)
+        data = kwargs["x"]
+        if isinstance(data, (tuple, list)):
+            if self.flow != "source_to_target" or len(data) != 2:
+                return None
+            data = data[0]
+        t = _lib.real(data)
+        if not (isinstance(t, Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 1 and (self.node_dim == 0 or t.dim() <= 2)):
+            return None
+        call.see(j, t.shape[0], "x")
+        for e in (0, 1):     # a side no node tensor settled: the other side's count, as PyG does for a single node set
+            if call.size[e] is None:
+                call.size[e] = call.size[1 - e]
+        return ops.gather_scatter(t, call.plan(j), call.plan(i), call.size[i], None, self.aggr)
+
     def propagate(self, edge_index, size=None, **kwargs):
         size = [None, None] if size is None else [None if s is None else int(s) for s in size]
         if len(size) != 2:
@@ -717,6 +757,9 @@ class MessagePassing(nn.Module):
         _MP_RUNNING.append((call, 1 if self.flow == "source_to_target" else 0))
         try:
             lifted: dict = {}
+            out = self._mp_default_fused(call, kwargs)
+            if out is not None:
+                return self.update(out, **self._mp_collect("update", call, kwargs, lifted))
             msg_kwargs = self._mp_collect("message", call, kwargs, lifted)
             out = self.message(**msg_kwargs)
             out = self.aggregate(out, **self._mp_collect("aggregate", call, kwargs, lifted))

@@ -709,6 +709,11 @@ def scatter(src: Tensor, index, dim_size: int, reduce: str = "sum", plan: RowsPl
     host-checked plan of ``index`` is built (cached per index tensor).  First derivatives."""
     if reduce not in _SCATTER_REDUCE:
         raise ValueError(f"reduce must be one of {sorted(_SCATTER_REDUCE)}, got {reduce!r}")
+    fused = getattr(src, "_egnn_gather_scatter", None)     # rows of lazy.py that nobody has formed yet: gather_scatter forms none
+    if fused is not None and FUSE_LAZY_ROWS and _SCATTER_REDUCE[reduce] <= 1:
+        out = fused(plan if plan is not None else index, dim_size, reduce)
+        if out is not None:
+            return (out, None) if return_arg else out
     src = _lib.real(src)
     _lib.require_gpu(src, index if isinstance(index, Tensor) else None)
     if src.dtype != torch.float32 or src.dim() < 1:
@@ -731,6 +736,127 @@ def scatter(src: Tensor, index, dim_size: int, reduce: str = "sum", plan: RowsPl
     if return_arg:
         return out, (arg.view((plan.n_rows,) + tail) if arg is not None else None)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# lift, per-edge weight and aggregation in one walk (csrc/gather_scatter.hip): no [E, C] message tensor forward or backward
+# ------------------------------------------------------------------------------------------------
+# nn.MessagePassing's default message and the unformed rows of lazy.py (accel) go to gather_scatter instead of take_rows + scatter.
+# On: DESIGN 3.5c's condition (the fused median does not exceed the unfused composition's at the two C = 256 full-graph cases) held:
+# 2.61 against 4.60 ms without and 3.37 against 8.24 ms with a weight, forward + backward (profiles/gather_scatter_bench.jsonl).
+FUSE_LAZY_ROWS = True
+
+
+def _gather_scatter_launch(out, count, keys, S, shift, frm, x, from_count, w, C, red) -> None:
+    lib = _lib.load()
+    nws = lib.egnn_gather_scatter_ws_bytes(S, C)
+    ws = torch.empty(nws, dtype=torch.uint8, device=x.device) if nws else None
+    _lib.check(lib.egnn_gather_scatter_runs_f32(_lib.ptr(out), out.stride(0), out.shape[0], _lib.ptr(count), _lib.ptr(keys), S, shift if S else 0,
+                                                _lib.ptr(frm), _lib.ptr(x), x.stride(0), x.shape[0], _lib.ptr(from_count), _lib.ptr(w),
+                                                w.stride(0) if w is not None else 0, w.shape[1] if w is not None else 1, C, red, _lib.ptr(ws), nws,
+                                                _lib.stream()), "egnn_gather_scatter_runs_f32")
+
+
+class _GatherScatter(torch.autograd.Function):
+    """out[r] = sum | mean over dst[p] == r of x[src[p]] * w[p] (egnn_gather_scatter_runs_f32 over the target plan's keys).  Backward:
+    dx by the same entry point over the source plan's keys (it gathers g by the target rows), dw by egnn_edge_dot_f32; only for the
+    operands that need one, into uninitialised gradients.  First derivatives only."""
+
+    @staticmethod
+    def forward(ctx, x, w, plan_src, plan_dst, red):
+        x = _rowmajor(x)
+        w = None if w is None else _rowmajor(w)
+        S, n, C = plan_dst.S, plan_dst.n_rows, x.shape[1]
+        out = torch.empty((n, C), dtype=torch.float32, device=x.device)
+        count = torch.empty(n, dtype=torch.int32, device=x.device) if red == 1 else None
+        _gather_scatter_launch(out, count, plan_dst.all_keys, S, plan_dst.shift, plan_src.idx, x, None, w, C, red)
+        ctx.plans, ctx.count = (plan_src, plan_dst), count
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _rowmajor(g)
+        x, w = ctx.saved_tensors
+        plan_src, plan_dst = ctx.plans
+        S, C = plan_dst.S, x.shape[1]
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((plan_src.n_rows, C), dtype=torch.float32, device=g.device)
+            _gather_scatter_launch(dx, None, plan_src.all_keys, S, plan_src.shift, plan_dst.rows, g, ctx.count, w, C, 0)
+        if w is not None and ctx.needs_input_grad[1]:
+            dw = torch.empty(w.shape, dtype=torch.float32, device=g.device)
+            _lib.check(_lib.load().egnn_edge_dot_f32(_lib.ptr(dw), dw.stride(0), S, w.shape[1], C, _lib.ptr(plan_dst.rows), _lib.ptr(g), g.stride(0),
+                                                     g.shape[0], _lib.ptr(plan_src.idx), _lib.ptr(x), x.stride(0), x.shape[0],
+                                                     _lib.ptr(ctx.count), _lib.stream()), "egnn_edge_dot_f32")
+        return dx, dw, None, None, None
+
+
+def _endpoint_plan(end, n_rows: int, what: str) -> RowsPlan:
+    """One endpoint of ``gather_scatter`` as a plan: a ready ``RowsPlan``, the plan the running ``propagate`` call holds for this very
+    tensor (``nn.running_end_plan``), or the host-checked plan of the tensor."""
+    if not isinstance(end, RowsPlan):
+        if not (isinstance(end, Tensor) and end.dtype == torch.int64 and end.dim() == 1):
+            raise TypeError(f"gather_scatter: `{what}` must be a 1-D int64 tensor or a RowsPlan")
+        from . import nn as _nn
+        running = _nn.running_end_plan(end, n_rows, what)
+        if running is not None:
+            return running
+    return _plan_for(end, n_rows, f"gather_scatter ({what})")
+
+
+def gather_scatter(x: Tensor, src, dst, dim_size: int, weight: Tensor | None = None, reduce: str = "sum") -> Tensor:
+    """``out[r] = reduce over the edges p with dst[p] == r of x[src[p]] * weight[p]`` -> [dim_size, ...]: the lift, the per-edge weight
+    and the aggregation of a message-passing layer in ONE kernel walk, forward and backward, without an [E, C] tensor.  ``x`` float32
+    GPU [N_src, ...] (trailing dims are flattened for the kernel); ``src`` / ``dst`` each a 1-D int64 tensor [E] (any order, repeats,
+    negative ids) or a ready ``RowsPlan`` (over N_src / ``dim_size`` rows); ``weight`` None, [E], [E, 1], [E, H] or [E, H, 1] with H
+    dividing the flattened width (head h weighs the h-th block of C / H columns; for ``x`` [N, H, D], H is ``x.shape[1]``);
+    ``reduce`` in sum | add | mean.  The value and every gradient except ``weight``'s are bit-equal to
+    ``scatter(take_rows(x, plan_src) * weight, None, dim_size, reduce, plan=plan_dst)`` -- the same order of additions, and with
+    deferred plans the same treatment of ids out of range (a dropped source id reads row 0 and gets no gradient, a dropped target id
+    is left out and its weight gets gradient 0).  ``weight``'s gradient is the per-edge dot of ``egnn_edge_dot_f32`` (a fixed order
+    of its own).  Each plan is built at most once (cached per index tensor; inside a running ``propagate`` the call's own plans are
+    taken).  First derivatives."""
+    if reduce not in _SCATTER_REDUCE:
+        raise ValueError(f"reduce must be one of ['add', 'mean', 'sum'], got {reduce!r}")
+    if _SCATTER_REDUCE[reduce] > 1:
+        raise ValueError(f"gather_scatter: reduce must be sum, add or mean; {reduce!r} keeps an argument per element: use ops.scatter")
+    x = _lib.real(x)
+    if not isinstance(x, Tensor) or x.dtype != torch.float32 or x.dim() < 1:
+        raise TypeError("gather_scatter: `x` must be a float32 tensor [N, ...]")
+    dim_size = int(dim_size)
+    C = 1
+    for d in x.shape[1:]:
+        C *= d
+    E = src.S if isinstance(src, RowsPlan) else (src.numel() if isinstance(src, Tensor) else None)
+    E_dst = dst.S if isinstance(dst, RowsPlan) else (dst.numel() if isinstance(dst, Tensor) else None)
+    if E is not None and E_dst is not None and E != E_dst:
+        raise ValueError(f"gather_scatter: {E} source ids, {E_dst} target ids")
+    for end, n, what in ((src, x.shape[0], "src"), (dst, dim_size, "dst")):
+        if isinstance(end, RowsPlan) and end.n_rows != n:
+            raise ValueError(f"gather_scatter ({what}): the plan was built for {end.n_rows} rows, the operand has {n}")
+    w2 = None
+    if weight is not None:
+        weight = _lib.real(weight)
+        if not isinstance(weight, Tensor) or weight.dtype != torch.float32:
+            raise TypeError("gather_scatter: `weight` must be a float32 tensor")
+        if weight.dim() not in (1, 2, 3) or (weight.dim() == 3 and weight.shape[2] != 1):
+            raise ValueError(f"gather_scatter: `weight` is [E], [E, 1], [E, H] or [E, H, 1], got {list(weight.shape)}")
+        if E is not None and weight.shape[0] != E:
+            raise ValueError(f"gather_scatter: {weight.shape[0]} weights for {E} edges")
+        H = weight.shape[1] if weight.dim() > 1 else 1
+        if H < 1 or (H > 1 and (C % H != 0 or (x.dim() == 3 and H != x.shape[1]))):
+            raise ValueError(f"gather_scatter: {H} weight columns do not divide x's {list(x.shape[1:])} into heads")
+        w2 = weight.reshape(weight.shape[0], H)
+    _lib.require_gpu(x, w2, src if isinstance(src, Tensor) else None, dst if isinstance(dst, Tensor) else None)
+    plan_src = _endpoint_plan(src, x.shape[0], "src")
+    plan_dst = _endpoint_plan(dst, dim_size, "dst")
+    if plan_src.S != plan_dst.S:
+        raise ValueError(f"gather_scatter: {plan_src.S} source ids, {plan_dst.S} target ids")
+    if C == 0 or dim_size == 0:
+        return x.new_zeros((dim_size,) + tuple(x.shape[1:]))
+    out = _GatherScatter.apply(x.reshape(x.shape[0], C), w2, plan_src, plan_dst, _SCATTER_REDUCE[reduce])
+    return out.view((dim_size,) + tuple(x.shape[1:]))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1048,6 +1048,52 @@ int egnn_adam_rows_step_sum_f32(const egnn_adam_rows_t* a, int type_id, const in
 int egnn_probe_gather_lines_f32(const float* X, int64_t ldx, int64_t n_src, int64_t K, const int32_t* col, int64_t nnz,
                                 int blocks_per_slice, int loads_in_flight, float* sink, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Gather, weight and aggregate in one walk (csrc/gather_scatter.hip): the lift, the per-edge weight and the aggregation of a
+ * message-passing layer without the [S, C] message tensor, and the per-edge dot that is the weights' gradient.  No float atomics, no
+ * integer atomics; first derivatives only.
+ *
+ * egnn_gather_scatter_runs_f32   for every row r < n_rows, over the positions p of r's run in keys_sorted (keys_sorted, S, shift as
+ *     egnn_rows_plan_build_i64 made them) and with D = C / H columns per head:
+ *         out[r, c] = reduce_p  m[p, c],     m[p, c] = (x[from[p], c] / (float)from_count[from[p]]) * w[p, c / D]
+ *     each step rounded to fp32 (the division only when from_count != NULL, the multiply only when w != NULL: weight 1).
+ *     from int64 [S]: addresses into x [n_x, ld_x]; an entry outside [0, n_x) reads nothing and stands for a row of zeros (it still
+ *     takes its weight, as a materialised message would).  w float [S, ld_w], H >= 1 columns, C % H == 0; w == NULL needs H == 1 (or S == 0).
+ *     reduce: 0 sum, 1 mean (anything else: EGNN_EINVAL).  count int32 [n_rows] (nullable; required for mean): the length of row
+ *     r's run, written as egnn_scatter_runs_f32 writes it; mean divides the sum by (float)count[r], one correctly rounded division
+ *     per element.  EVERY row of out [n_rows, ld_out] is written, a row that no key names gets 0 (no memset needed).
+ *     ORDER OF THE ADDITIONS: egnn_rows_add_runs_f32's, over m instead of src -- the same cut into chunks of EGNN_ROWS_SUM_CHUNK
+ *     positions read off the keys, P_j = ((m[p_(jK+1)] + m[p_(jK+2)]) + ...) in ascending position, a long run's chunks parked in
+ *     ws and merged in ascending chunk order.  The result is therefore bit-equal to egnn_scatter_runs_f32 over the materialised
+ *     messages m, for sum and mean, whatever the pitches and alignments.
+ *     The backward of x is this entry point over the SOURCE side's keys: from = the target rows (-1 for a dropped id), x = the
+ *     gradient of out, from_count = the forward's count for mean, out = dx [n_src, C].
+ *     16 bytes per lane when D % 4 == 0, ld_out and ld_x % 4 == 0 and out and x are 16-byte aligned; a scalar path with the same
+ *     arithmetic otherwise.  Four keys, then four ids and weights, then four rows are in flight per lane.
+ *     ws: egnn_gather_scatter_ws_bytes(S, C) bytes (= egnn_rows_add_runs_ws_bytes), 16-byte aligned (0 for S <= EGNN_ROWS_SUM_CHUNK);
+ *     missing or short: EGNN_EWORKSPACE; misaligned ws / keys / from / other operands: EGNN_EALIGN; S and n_rows < 2^31 - 1, C >= 1,
+ *     pitches >= C (ld_w >= H), shift = the number of bits of S - 1: else EGNN_EINVAL.  Every check happens before the first launch.
+ *     S == 0: EGNN_OK; with a non-NULL out the n_rows rows and counts are zeroed.  A key whose position or row does not fit
+ *     S / n_rows is skipped, never used as an address.
+ *
+ * egnn_edge_dot_f32   dw[p, h] = sum over the D = C / H columns c of head h of A[a_rows[p], c] * B[b_rows[p], c], p < S (a COO SDDMM
+ *     with two gathers), divided by (float)a_count[a_rows[p]] when a_count != NULL.  a_rows / b_rows int64 [S]; an entry outside
+ *     [0, n_a) / [0, n_b) gives dw[p, :] = 0 and reads nothing.  dw [S, ld_dw], ld_dw >= H; every element is written with a plain store.
+ *     ORDER OF THE ADDITIONS, a function of (C, H) only: one group of G = min(64, pow2ceil(ceil(D / 4))) lanes per (p, h); lane l
+ *     starts from 0.f and adds the products (each rounded to fp32) of the head's columns 4 (l + G t) + i, t = 0, 1, ..., i = 0 .. 3,
+ *     below D, in ascending column order; the G lane sums meet in a butterfly over xor offsets G / 2 .. 1 (egnn_group_sum).  Pitches
+ *     and alignments only decide whether the same columns are loaded 16 bytes at a time: the bits do not depend on them, two calls
+ *     are bit-equal, and head h of an H-head call equals the one-head call on that head's column block.
+ *     S < 2^31 - 1, C >= 1, H >= 1, C % H == 0, pitches >= C: else EGNN_EINVAL; misaligned pointers: EGNN_EALIGN.  S == 0: EGNN_OK.
+ * ---------------------------------------------------------------------------------------------- */
+size_t egnn_gather_scatter_ws_bytes(int64_t S, int64_t C);
+int egnn_gather_scatter_runs_f32(float* out, int64_t ld_out, int64_t n_rows, int32_t* count, const uint64_t* keys_sorted, int64_t S,
+                                 int shift, const int64_t* from, const float* x, int64_t ld_x, int64_t n_x, const int32_t* from_count,
+                                 const float* w, int64_t ld_w, int64_t H, int64_t C, int reduce, void* ws, size_t ws_bytes, void* stream);
+int egnn_edge_dot_f32(float* dw, int64_t ld_dw, int64_t S, int64_t H, int64_t C, const int64_t* a_rows, const float* A, int64_t ld_a,
+                      int64_t n_a, const int64_t* b_rows, const float* B, int64_t ld_b, int64_t n_b, const int32_t* a_count,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
