@@ -211,6 +211,10 @@ SIGNATURES = {
     "egnn_adam_rows_step_sum_ws_bytes": (_sz, [_i64, _i64]),
     "egnn_adam_rows_step_sum_f32": (_i32, [_p, _i32, _p, _p, _i64, _p, _i64, _f32, _p, _sz, _p]),
     "egnn_probe_gather_lines_f32":(_i32, [_p, _i64, _i64, _i64, _p, _i64, _i32, _i32, _p, _p]),
+    "egnn_gather_edge_scatter_ws_bytes": (_sz, [_i64, _i64]),
+    "egnn_gather_edge_scatter_runs_f32": (_i32, [_p, _i64, _i64, _p, _p, _i64, _i32, _p, _p, _i64, _i64, _p, _p, _i64, _p, _i64, _i32, _i64, _i32,
+                                                 _p, _sz, _p]),
+    "egnn_edge_gate_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _p, _p, _i64, _i64, _p, _i32, _p]),
     "egnn_gather_scatter_ws_bytes": (_sz, [_i64, _i64]),
     "egnn_gather_scatter_runs_f32": (_i32, [_p, _i64, _i64, _p, _p, _i64, _i32, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p]),
     "egnn_edge_dot_f32": (_i32, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _p]),

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libegnn_hip.so")
 SOURCES = ["api.hip", "spmm.hip", "spmm_blk.hip", "graph.hip", "losses.hip", "gemm.hip", "gemm_skinny.hip", "nce.hip", "pairwise.hip", "edge_softmax.hip", "gat.hip",
            "fused_bn.hip", "graph_build.hip", "probe.hip", "feature_losses.hip", "saint.hip", "sign.hip", "similarity.hip", "adam_rows.hip", "rows_sum.hip", "sddmm.hip", "scatter.hip",
-           "scatter_softmax.hip", "gather_scatter.hip"]
+           "scatter_softmax.hip", "gather_scatter.hip", "gather_edge_scatter.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"] + os.environ.get("EGNN_EXTRA_FLAGS", "").split()
 
 

@@ -8,6 +8,7 @@ network).  Integer / host-side generation only -- tensors are move
   * ``ppi_like``    PPI: 20+2+2 graphs, x [n,50], 121 labels (/root/reference/ppi_pyg/gnn.py:301-310)
   * ``mag_like``    ogbn-mag grouped homogeneous graph (/root/reference/mag_pyg/gnn.py:322-346)
   * ``mag_hetero_like``  ogbn-mag as the heterogeneous dataset the script loads (/root/reference/mag_pyg/gnn.py:308-320)
+  * ``molhiv_like``  ogbg-molhiv-shaped molecules for graph classification (the public dataset card; mol_pyg holds a README only)
 """
 from __future__ import annotations
 
@@ -192,6 +193,47 @@ def ppi_like(seed: int = 0, n_train: int = 20, total_train_nodes: int = 44_906, 
         d.num_nodes = n
         graphs.append(d)
     return graphs[:n_train], graphs[n_train:n_train + 2], graphs[n_train + 2:]
+
+
+MOLHIV = dict(num_graphs=41_127, mean_nodes=25.5, mean_degree=2.2, node_columns=9, edge_columns=3, min_nodes=6, max_nodes=50)
+
+
+def molhiv_like(num_graphs: int = 512, seed: int = 0, atom_dims=None, bond_dims=None):
+    """Synthetic molecule-shaped graphs for graph classification (a list of ``saint.Data``, CPU tensors; ``Batch.from_data_list``
+    batches them).  Shapes from the public ogbg-molhiv dataset card: 41 127 molecules, 25.5 nodes and 27.5 bonds on average (mean
+    degree ~2.2, both directions of every bond stored), 9 categorical atom columns, 3 categorical bond columns, one binary label;
+    the reference's mol_pyg holds a README only.  Each graph: 6 .. 50 nodes, a random spanning tree whose new node attaches to one
+    of the last three (chains with short branches) plus ring-closing bonds between nodes at most five apart until the graph has
+    round(1.1 n) bonds; ``x`` [n, 9] and ``edge_attr`` [E, 3] int64 uniform below ``atom_dims`` / ``bond_dims`` (default
+    ``nn.ATOM_DIMS`` / ``nn.BOND_DIMS``; the two directions of a bond carry the same attributes), ``y`` [1, 1] float32 in {0, 1}."""
+    from .saint import Data
+    if atom_dims is None or bond_dims is None:
+        from .nn import ATOM_DIMS, BOND_DIMS
+        atom_dims = ATOM_DIMS if atom_dims is None else atom_dims
+        bond_dims = BOND_DIMS if bond_dims is None else bond_dims
+    if len(atom_dims) != MOLHIV["node_columns"] or len(bond_dims) != MOLHIV["edge_columns"]:
+        raise ValueError(f"molhiv_like: {MOLHIV['node_columns']} atom and {MOLHIV['edge_columns']} bond columns")
+    rng = np.random.default_rng(seed)
+    graphs = []
+    for _ in range(int(num_graphs)):
+        n = int(rng.integers(MOLHIV["min_nodes"], MOLHIV["max_nodes"] + 1))
+        bonds = {(int(v - 1 - rng.integers(0, min(3, v))), v) for v in range(1, n)}
+        want = int(round(n * MOLHIV["mean_degree"] / 2))
+        tries = 0
+        while len(bonds) < want and tries < 8 * n:
+            a = int(rng.integers(0, n))
+            b = a + int(rng.integers(2, 6))
+            if b < n:
+                bonds.add((a, b))
+            tries += 1
+        pairs = np.array(sorted(bonds), dtype=np.int64).reshape(-1, 2)
+        attr = np.stack([rng.integers(0, d, size=len(pairs)) for d in bond_dims], axis=1).astype(np.int64)
+        edge_index = np.concatenate([pairs.T, pairs.T[::-1]], axis=1)
+        x = np.stack([rng.integers(0, d, size=n) for d in atom_dims], axis=1).astype(np.int64)
+        graphs.append(Data(x=torch.from_numpy(x), edge_index=torch.from_numpy(np.ascontiguousarray(edge_index)),
+                           edge_attr=torch.from_numpy(np.concatenate([attr, attr], axis=0)),
+                           y=torch.tensor([[float(rng.random() < 0.5)]], dtype=torch.float32), num_nodes=n))
+    return graphs
 
 
 def mag_like(scale: float = 1.0, seed: int = 0, feats: int = 128):

@@ -17,7 +17,8 @@ module's running-statistics update) and returns a ``LazyBnAct``: a tensor-like o
     (``ops.linear_rows``: no ``[N_tr, 256]`` copy forward, no zero-fill + scatter backward).
 
 ``nn.MessagePassing`` hands out a lifted ``x_j`` as a ``LazyRows`` too; times a per-edge weight it becomes a ``LazyWeightedRows``, which
-``ops.scatter`` (sum / add / mean) runs as ONE ``ops.gather_scatter`` -- lift, weight and aggregation without an [E, C] tensor.
+``ops.scatter`` (sum / add / mean) runs as ONE ``ops.gather_scatter`` -- lift, weight and aggregation without an [E, C] tensor.  Plus a
+per-edge ROW (``x_j + edge_attr``, then ``relu``) it becomes a ``LazyEdgeRows``, which ``ops.scatter`` runs as ONE ``ops.gather_add_scatter``.
 
 Inference (``model.eval()`` under ``no_grad``): a ``GCNConv`` that has been SEEN feeding a ``BatchNorm1d`` (``accel`` learns the association
 from the first forward; it only decides what is deferred) hands out a ``LazyConv``; the eval-mode BatchNorm turns it into a ``LazyFold``
@@ -37,6 +38,8 @@ from . import _cache, ops
 
 ACCEL_ACTIVE = False   # set by dropin/accel.py's enable() / disable(): torch.nn.Linear.forward consumes a LazyRows
 _MUL_FUNCS = (torch.mul, torch.multiply, torch.Tensor.mul, torch.Tensor.multiply, torch.Tensor.__mul__, torch.Tensor.__rmul__)
+_ADD_FUNCS = (torch.add, torch.Tensor.add, torch.Tensor.__add__, torch.Tensor.__radd__)
+_RELU_FUNCS = (F.relu, torch.relu, torch.Tensor.relu)
 
 
 def _on_gpu(t) -> bool:
@@ -301,8 +304,30 @@ class LazyRows(_TensorLike):
 
     __rmul__ = __mul__
 
+    def _edge_rows(self, other):
+        """True when ``rows + other`` is the per-edge row ``ops.gather_add_scatter`` takes: unformed 2-D rows and a float32 GPU tensor
+        of exactly their shape [E, C] (anything torch would broadcast, a scalar or another dtype forms the rows)."""
+        if self._value is not None or not (ops.FUSE_EDGE_ROWS and ops.FUSE_LAZY_ROWS) or not isinstance(self._base, torch.Tensor):
+            return False
+        if self._base.dim() != 2 or type(other) not in (torch.Tensor, torch.nn.Parameter):
+            return False
+        return other.dtype == torch.float32 and _on_gpu(other) and _on_gpu(self._base) and tuple(other.shape) == tuple(self.shape)
+
+    def __add__(self, other):
+        if self._edge_rows(other):
+            return LazyEdgeRows(self, other)
+        return self._egnn_materialise() + materialise(other)
+
+    __radd__ = __add__
+
     @classmethod
     def _absorb(cls, func, args, kwargs):
+        if func in _ADD_FUNCS and len(args) == 2 and not kwargs:
+            a, b = args
+            if isinstance(b, LazyRows) and not isinstance(a, _TensorLike):
+                a, b = b, a
+            if isinstance(a, LazyRows) and not isinstance(b, _TensorLike) and a._edge_rows(b):
+                return LazyEdgeRows(a, b)
         if func in _MUL_FUNCS and len(args) == 2 and not kwargs:
             a, b = args
             if isinstance(b, LazyRows) and not isinstance(a, _TensorLike):
@@ -370,6 +395,62 @@ class LazyWeightedRows(_TensorLike):
         if self._value is not None:
             return None
         return self._rows._egnn_gather_scatter(dst, dim_size, reduce, self._weight)
+
+    def __getitem__(self, idx):
+        return self._egnn_materialise()[idx]
+
+
+class LazyEdgeRows(_TensorLike):
+    """``rows + edge`` (then ``relu``) for an unformed 2-D ``LazyRows`` and a per-edge row tensor of its shape (``LazyRows._edge_rows``),
+    not added yet: the message ``F.relu(x_j + edge_attr)`` of an edge-feature conv.  ``ops.scatter`` with a summing reduce consumes it
+    as ONE ``ops.gather_add_scatter`` -- no [E, C] tensor forward, ``edge``'s gradient the only one backward; every other consumer (a
+    second add, a second relu, an in-place relu included) gets exactly ``take_rows(...) + edge`` (then ``relu``).  ``edge`` is read
+    when the rows are consumed: its version is recorded, and an ``edge`` changed in place in between raises, as a changed base does."""
+
+    def __init__(self, rows, edge, act=None, edge_version=None):
+        self._rows, self._edge, self._act, self._value = rows, edge, act, None
+        self._edge_version = edge._version if edge_version is None else edge_version
+
+    def _current_edge(self):
+        edge = self._edge
+        if edge._version != self._edge_version:
+            raise RuntimeError(f"one of the variables needed for a deferred message has been modified by an inplace operation: the edge "
+                               f"rows {list(edge.shape)} are at version {edge._version}; expected version {self._edge_version} instead "
+                               f"(x_j + edge_attr under accel is formed by its first consumer: clone edge_attr before changing it in place)")
+        return edge
+
+    shape = property(lambda self: self._rows.shape)
+    device = property(lambda self: self._rows.device)
+
+    @classmethod
+    def _absorb(cls, func, args, kwargs):
+        x = args[0] if args else None
+        if (isinstance(x, LazyEdgeRows) and x._value is None and x._act is None and func in _RELU_FUNCS and len(args) == 1
+                and not kwargs.get("inplace", False) and not (set(kwargs) - {"inplace"})):
+            return LazyEdgeRows(x._rows, x._edge, "relu", x._edge_version)
+        return NotImplemented
+
+    def relu(self):
+        if self._value is None and self._act is None:
+            return LazyEdgeRows(self._rows, self._edge, "relu", self._edge_version)
+        return self._egnn_materialise().relu()
+
+    def _egnn_materialise(self, pick=None):
+        if self._value is None:
+            v = self._rows._egnn_materialise() + self._current_edge()
+            self._value = torch.relu(v) if self._act == "relu" else v
+        return self._value if pick is None else self._value[pick]
+
+    def _egnn_gather_scatter(self, dst, dim_size, reduce):
+        rows = self._rows
+        if self._value is not None or rows._value is not None or not (ops.FUSE_EDGE_ROWS and ops.FUSE_LAZY_ROWS):
+            return None
+        if not (isinstance(rows._idx, torch.Tensor) and _on_gpu(rows._idx)):
+            return None
+        base = rows._formed_base()
+        if not (isinstance(base, torch.Tensor) and _on_gpu(base) and base.dtype == torch.float32 and base.dim() == 2):
+            return None
+        return ops.gather_add_scatter(base, rows._idx if rows._plan is None else rows._plan(), dst, dim_size, self._current_edge(), self._act, reduce)
 
     def __getitem__(self, idx):
         return self._egnn_materialise()[idx]

@@ -18,7 +18,8 @@ from torch import nn
 from . import _cache, _lib
 from . import criterion as C
 from . import ops
-from .nn import DGLGATConv, GATConv, GCNConv, RGCNConv, SAGEConv
+from .nn import (ATOM_DIMS, BOND_DIMS, CategoricalEncoder, DGLGATConv, GATConv, GCNConv, GINConv, GINEConv, RGCNConv, SAGEConv,
+                 global_add_pool, global_max_pool, global_mean_pool)
 from .sparse import SparseTensor
 
 
@@ -1205,3 +1206,77 @@ def sign_test(model, feats, labels, eval_batches, train_nid, val_nid, test_nid):
     split = {"train": train_nid.to(dev), "valid": val_nid.to(dev), "test": test_nid.to(dev)}
     accs = ops.split_accuracy(logits, labels.view(-1), split)
     return logits, tuple(accs.tolist())
+
+
+# ------------------------------------------------------------------------------------------------
+# graph classification on batches of molecule-sized graphs (the README's fourth benchmark; mol_pyg holds a README only, so the
+# layer stack restates OGB's public mol example [ext])
+# ------------------------------------------------------------------------------------------------
+MOL_MODES = ("supervised", "kd")
+_MOL_POOLS = {"mean": global_mean_pool, "add": global_add_pool, "sum": global_add_pool, "max": global_max_pool}
+
+
+class MolGNN(nn.Module):
+    """GIN / GIN-E student for molecule batches [ext]: an atom encoder, ``num_layers`` x (conv -> BatchNorm1d -> relu (not after the last
+    layer) -> dropout), a graph-level pool and ``Linear(emb_dim, 1)``.  ``conv="gine"``: ``nn.GINEConv`` on a per-layer bond
+    embedding (one fused gather-add-relu-aggregate walk per layer); ``conv="gin"``: ``nn.GINConv``, the bonds' attributes unread.
+    Each conv's MLP is Linear(emb, 2 emb) -> BatchNorm1d -> ReLU -> Linear(2 emb, emb).  State_dict keys: ``atom_encoder.*``,
+    ``bond_encoders.l.*`` (gine), ``convs.l.nn.*`` / ``convs.l.eps``, ``bns.l.*``, ``graph_pred_linear.*``.  ``forward(batch)`` takes a
+    ``saint.Batch`` (x [N, 9] and edge_attr [E, 3] int64, edge_index, batch, num_graphs) and returns logits [G, 1]; the pooled graph
+    embedding stays in ``out_feat``, the side channel the criteria read."""
+
+    def __init__(self, conv: str = "gin", num_layers: int = 5, emb_dim: int = 300, dropout: float = 0.5, pool: str = "mean",
+                 atom_dims=ATOM_DIMS, bond_dims=BOND_DIMS):
+        super().__init__()
+        if conv not in ("gin", "gine"):
+            raise ValueError(f"MolGNN: conv must be 'gin' or 'gine', got {conv!r}")
+        if pool not in _MOL_POOLS:
+            raise ValueError(f"MolGNN: pool must be one of {sorted(_MOL_POOLS)}, got {pool!r}")
+        if num_layers < 1:
+            raise ValueError("MolGNN: num_layers must be at least 1")
+        self.conv, self.num_layers, self.emb_dim, self.dropout, self.pool = conv, int(num_layers), int(emb_dim), float(dropout), pool
+        self.atom_encoder = CategoricalEncoder(atom_dims, emb_dim)
+        if conv == "gine":
+            self.bond_encoders = nn.ModuleList(CategoricalEncoder(bond_dims, emb_dim) for _ in range(num_layers))
+        mlp = lambda: nn.Sequential(nn.Linear(emb_dim, 2 * emb_dim), nn.BatchNorm1d(2 * emb_dim), nn.ReLU(),   # noqa: E731
+                                    nn.Linear(2 * emb_dim, emb_dim))
+        layer = GINEConv if conv == "gine" else GINConv
+        self.convs = nn.ModuleList(layer(mlp()) for _ in range(num_layers))
+        self.bns = nn.ModuleList(nn.BatchNorm1d(emb_dim) for _ in range(num_layers))
+        self.graph_pred_linear = nn.Linear(emb_dim, 1)
+        self.out_feat = None
+
+    def reset_parameters(self):
+        self.atom_encoder.reset_parameters()
+        for m in list(getattr(self, "bond_encoders", [])) + list(self.convs) + list(self.bns) + [self.graph_pred_linear]:
+            m.reset_parameters()
+
+    def forward(self, batch):
+        h = self.atom_encoder(batch.x)
+        for l, (conv, bn) in enumerate(zip(self.convs, self.bns)):
+            if self.conv == "gine":
+                h = conv(h, batch.edge_index, self.bond_encoders[l](batch.edge_attr))
+            else:
+                h = conv(h, batch.edge_index)
+            h = bn(h)
+            if l != self.num_layers - 1:
+                h = F.relu(h)
+            h = F.dropout(h, p=self.dropout, training=self.training)
+        self.out_feat = _MOL_POOLS[self.pool](h, batch.batch, batch.num_graphs)
+        return self.graph_pred_linear(self.out_feat)
+
+
+def mol_batch_loss(model, batch, mode, hp, teacher_logits=None):
+    """``(loss, loss_cls, loss_aux)`` of one batch of graphs: ``supervised`` (mean BCE-with-logits on ``batch.y`` [G, 1]) and ``kd``
+    (the multi-label KD of ``dropin/ppi_pyg/criterion.py``: ``hp`` alpha / kd_T, ``teacher_logits`` [G, 1]).  Other modes:
+    ``NotImplementedError(mode)``."""
+    if mode not in MOL_MODES:
+        raise NotImplementedError(mode)
+    if mode == "kd" and teacher_logits is None:
+        raise ValueError("mol_batch_loss: mode 'kd' needs `teacher_logits`")
+    out = model(batch)
+    y = batch.y.to(out.dtype).view(out.shape)
+    if mode == "supervised":
+        loss = F.binary_cross_entropy_with_logits(out, y)
+        return loss, loss, loss * 0
+    return C.ppi_kd_criterion(out, y, teacher_logits.view(out.shape), hp["alpha"], hp["kd_T"])

@@ -770,3 +770,190 @@ class MessagePassing(nn.Module):
 
     def __repr__(self):
         return f"{type(self).__name__}()"
+
+
+# ------------------------------------------------------------------------------------------------
+# graph classification: GIN / GINE convs, categorical encoders, graph-level readout (PyG <= 1.7 definitions [ext]: the reference's
+# mol_pyg holds a README only)
+# ------------------------------------------------------------------------------------------------
+def _reset(module) -> None:
+    """PyG's ``inits.reset``, with a module's own ``reset_parameters`` preferred at every level: a module that has one resets itself
+    (and whatever it holds, by its own rule); a plain container hands the call to its children."""
+    if hasattr(module, "reset_parameters"):
+        module.reset_parameters()
+    else:
+        for child in module.children():
+            _reset(child)
+
+
+class _GINBase(MessagePassing):
+    """What ``GINConv`` and ``GINEConv`` share: ``nn`` (the MLP applied to the combined row), ``eps`` (a buffer, or a ``Parameter``
+    with ``train_eps``) and ``out = nn((1 + eps) * x_r + aggregated messages)``; state_dict keys ``nn.*`` and ``eps``."""
+
+    def __init__(self, nn_module, eps: float = 0.0, train_eps: bool = False, **kwargs):
+        kwargs.setdefault("aggr", "add")
+        super().__init__(**kwargs)
+        self.nn = nn_module
+        self.initial_eps = float(eps)
+        if train_eps:
+            self.eps = nn.Parameter(torch.empty(1))
+        else:
+            self.register_buffer("eps", torch.empty(1))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _reset(self.nn)
+        with torch.no_grad():
+            self.eps.fill_(self.initial_eps)
+
+    @staticmethod
+    def _node_pair(x, who: str):
+        """``x`` as a ``(source, target)`` pair of REAL tensors: a deferred activation (``lazy.py``: what a ``BatchNorm1d`` hands out
+        under ``accel``) is formed first -- it is no ``Tensor``, and indexing it like a pair would pick rows 0 and 1."""
+        if isinstance(x, (tuple, list)):
+            if len(x) != 2:
+                raise ValueError(f"{who}: `x` must be a tensor or a (source, target) pair")
+            pair = tuple(None if t is None else _lib.real(t) for t in x)
+        else:
+            x = _lib.real(x)
+            pair = (x, x)
+        if not isinstance(pair[0], Tensor) or not (pair[1] is None or isinstance(pair[1], Tensor)):
+            raise TypeError(f"{who}: `x` must be a tensor or a (source, target) pair of tensors")
+        return pair
+
+    def _combine(self, out: Tensor, x_r) -> Tensor:
+        if x_r is not None:
+            out = out + (1 + self.eps) * x_r
+        return self.nn(out)
+
+    def __repr__(self):
+        return f"{type(self).__name__}(nn={self.nn})"
+
+
+class GINConv(_GINBase):
+    """``torch_geometric.nn.GINConv`` (PyG <= 1.7 [ext]): ``out = nn((1 + eps) * x_r + sum_j x_j)``.  The default ``message`` under
+    ``aggr="add"``: lift and sum are one walk (``ops.gather_scatter``).  ``x`` may be a ``(source, target)`` pair."""
+
+    def forward(self, x, edge_index, size=None) -> Tensor:
+        x = self._node_pair(x, "GINConv")
+        return self._combine(self.propagate(edge_index, x=x, size=size), x[1])
+
+
+class GINEConv(_GINBase):
+    """``torch_geometric.nn.GINEConv`` (PyG <= 1.7 [ext]): ``out = nn((1 + eps) * x_r + sum_j relu(x_j + edge_attr_j))``;
+    ``edge_attr`` [E, C] has the width of ``x``.  While ``message`` and ``aggregate`` are the class's own, lift, add, relu and sum are
+    ONE walk over the call's two deferred plans (``ops.gather_add_scatter``: no [E, C] message tensor); a subclass that overrides
+    ``message`` takes ``propagate``'s general path."""
+
+    def forward(self, x, edge_index, edge_attr, size=None) -> Tensor:
+        x = self._node_pair(x, "GINEConv")
+        edge_attr = _lib.real(edge_attr)
+        if not isinstance(edge_attr, Tensor):
+            raise TypeError("GINEConv: `edge_attr` must be a tensor [E, C]")
+        if edge_attr.dim() != 2 or edge_attr.shape[1] != x[0].shape[-1]:
+            raise ValueError(f"GINEConv: node and edge feature widths do not match: x has {x[0].shape[-1]} columns, edge_attr is "
+                             f"{list(edge_attr.shape)}")
+        out = self._fused(x[0], x[1], edge_index, edge_attr, size)
+        if out is None:
+            out = self.propagate(edge_index, x=x, edge_attr=edge_attr, size=size)
+        return self._combine(out, x[1])
+
+    def message(self, x_j, edge_attr):
+        return (x_j + edge_attr).relu()
+
+    def _fused(self, x_src, x_dst, edge_index, edge_attr, size):
+        """The class's own message and aggregation as one ``ops.gather_add_scatter`` (``_mp_default_fused``'s shape); None: the
+        general path runs (and raises what it raises for operands it does not take)."""
+        cls = type(self)
+        if not (ops.FUSE_EDGE_ROWS and cls.message is GINEConv.message and cls.aggregate is MessagePassing.aggregate
+                and cls.update is MessagePassing.update and self.aggr in ("add", "sum", "mean")
+                and isinstance(edge_index, Tensor) and edge_index.dtype == torch.int64 and edge_index.dim() == 2 and edge_index.shape[0] == 2
+                and edge_index.is_cuda and isinstance(x_src, Tensor) and x_src.is_cuda and x_src.dtype == torch.float32 and x_src.dim() == 2
+                and isinstance(edge_attr, Tensor) and edge_attr.is_cuda and edge_attr.dtype == torch.float32
+                and edge_attr.shape[0] == edge_index.shape[1]):
+            return None
+        j, i = (0, 1) if self.flow == "source_to_target" else (1, 0)
+        if j != 0 and x_dst is not x_src:
+            return None
+        size = [None, None] if size is None else [None if s is None else int(s) for s in size]
+        if len(size) != 2:
+            return None
+        call = _Propagation((edge_index[0], edge_index[1]), size, None, edge_index, None)
+        call.see(j, x_src.shape[0], "x")
+        if x_dst is not None:
+            call.see(i, x_dst.shape[0], "x")
+        for e in (0, 1):
+            if call.size[e] is None:
+                call.size[e] = call.size[1 - e]
+        return ops.gather_add_scatter(x_src, call.plan(j), call.plan(i), call.size[i], edge_attr, "relu", self.aggr)
+
+
+ATOM_DIMS = (119, 4, 12, 12, 10, 6, 6, 2, 2)     # [ext] the cardinalities of OGB's nine atom feature columns (ogb.utils.features)
+BOND_DIMS = (5, 6, 2)                             # [ext] and of its three bond feature columns
+
+
+class CategoricalEncoder(nn.Module):
+    """``out = sum_k table_k[attr[:, k]]`` for integer attributes ``attr`` [n, K]: what OGB's ``AtomEncoder`` / ``BondEncoder`` compute
+    [ext], with the cardinalities as arguments (``ATOM_DIMS`` / ``BOND_DIMS``).  Tables ``embeddings.k.weight`` [cardinality, emb_dim],
+    xavier-uniform.  Each lookup is ``ops.take_rows(..., duplicates="sum")``: a table row named by many nodes gets the deterministic
+    run-sum as its gradient, and an id outside its table raises ``IndexError``."""
+
+    def __init__(self, cardinalities, emb_dim: int):
+        super().__init__()
+        cards = [int(c) for c in cardinalities]
+        if not cards or any(c < 1 for c in cards):
+            raise ValueError(f"CategoricalEncoder: cardinalities must be a non-empty list of positive sizes, got {list(cardinalities)!r}")
+        if int(emb_dim) < 1:
+            raise ValueError(f"CategoricalEncoder: emb_dim must be positive, got {emb_dim!r}")
+        self.cardinalities, self.emb_dim = tuple(cards), int(emb_dim)
+        self.embeddings = nn.ModuleList(nn.Embedding(c, self.emb_dim) for c in cards)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for emb in self.embeddings:
+            nn.init.xavier_uniform_(emb.weight.data)
+
+    def forward(self, attr: Tensor) -> Tensor:
+        if not isinstance(attr, Tensor) or attr.dtype != torch.int64 or attr.dim() != 2 or attr.shape[1] != len(self.cardinalities):
+            raise ValueError(f"CategoricalEncoder: `attr` must be an int64 tensor [n, {len(self.cardinalities)}]")
+        _lib.require_gpu(attr, self.embeddings[0].weight)
+        if attr.shape[0] == 0:
+            return self.embeddings[0].weight.new_zeros((0, self.emb_dim))
+        out = None
+        for k, emb in enumerate(self.embeddings):
+            rows = ops.take_rows(emb.weight, attr[:, k].contiguous(), duplicates="sum")
+            out = rows if out is None else out + rows
+        return out
+
+
+def _global_pool(x: Tensor, batch: Tensor, size, reduce: str) -> Tensor:
+    x = _lib.real(x)
+    if not (isinstance(batch, Tensor) and batch.dtype == torch.int64 and batch.dim() == 1):
+        raise TypeError("global pool: `batch` must be a 1-D int64 tensor with the graph id of every node")
+    if not isinstance(x, Tensor) or x.dim() < 1 or x.shape[0] != batch.numel():
+        raise ValueError("global pool: `x` needs one row per entry of `batch`")
+    _lib.require_gpu(x, batch)
+    if size is None:
+        size = int(batch.max()) + 1 if batch.numel() else 0          # (one host read, as PyG)
+        return ops.scatter(x, batch, size, reduce)
+    size = int(size)
+    if size == 0 or batch.numel() == 0:
+        return x.new_zeros((size,) + tuple(x.shape[1:]))
+    return ops.scatter(x, None, size, reduce, plan=ops.rows_plan(batch.contiguous(), size, check="deferred"))
+
+
+def global_add_pool(x: Tensor, batch: Tensor, size=None) -> Tensor:
+    """``torch_geometric.nn.global_add_pool``: ``out[g] = sum of x[n] over batch[n] == g`` -> [size, ...] (``ops.scatter``: no float
+    atomics).  ``size`` given: a deferred plan, no host read; None: ``batch.max() + 1`` is read once, as PyG does.  A graph id that
+    owns no node gives a zero row."""
+    return _global_pool(x, batch, size, "sum")
+
+
+def global_mean_pool(x: Tensor, batch: Tensor, size=None) -> Tensor:
+    """``torch_geometric.nn.global_mean_pool``; see ``global_add_pool``."""
+    return _global_pool(x, batch, size, "mean")
+
+
+def global_max_pool(x: Tensor, batch: Tensor, size=None) -> Tensor:
+    """``torch_geometric.nn.global_max_pool``; see ``global_add_pool`` (a graph id that owns no node gives a zero row)."""
+    return _global_pool(x, batch, size, "max")

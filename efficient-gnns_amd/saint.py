@@ -36,6 +36,49 @@ class Data:
         return self
 
 
+class Batch(Data):
+    """``torch_geometric.data.Batch`` for graph-level tasks: many small graphs as ONE disconnected graph."""
+
+    @classmethod
+    def from_data_list(cls, graphs):
+        """``x`` / ``edge_attr`` / ``y`` concatenated, every graph's ``edge_index`` offset by the nodes before it, ``batch`` [N] int64
+        (the graph id of every node, ascending), ``ptr`` [G + 1] (node offsets) and ``num_graphs``.  Plain torch ops on whatever
+        device the graphs are on; a graph without edges or without nodes is legal (its id then owns no node).  A graph's node count is
+        ``x.shape[0]``, else its ``num_nodes``.  An attribute is kept only when every graph has it."""
+        graphs = list(graphs)
+        if not graphs:
+            raise ValueError("Batch.from_data_list: an empty list of graphs")
+
+        def nodes(g):
+            x = getattr(g, "x", None)
+            if isinstance(x, Tensor):
+                return int(x.shape[0])
+            n = getattr(g, "num_nodes", None)
+            if n is None:
+                raise ValueError("Batch.from_data_list: a graph has neither `x` nor `num_nodes`")
+            return int(n)
+
+        sizes = [nodes(g) for g in graphs]
+        offsets = [0]
+        for n in sizes:
+            offsets.append(offsets[-1] + n)
+        first = next((getattr(g, k) for g in graphs for k in ("edge_index", "x", "y") if isinstance(getattr(g, k, None), Tensor)), None)
+        device = first.device if first is not None else torch.device("cpu")
+        out = cls()
+        for key in ("x", "edge_attr", "y"):
+            parts = [getattr(g, key, None) for g in graphs]
+            if all(isinstance(p, Tensor) for p in parts):
+                setattr(out, key, torch.cat(parts, dim=0))
+        edges = [getattr(g, "edge_index", None) for g in graphs]
+        if all(isinstance(e, Tensor) for e in edges):
+            out.edge_index = torch.cat([e + off for e, off in zip(edges, offsets)], dim=1)
+        out.ptr = torch.tensor(offsets, dtype=torch.int64, device=device)
+        out.batch = torch.repeat_interleave(torch.arange(len(graphs), dtype=torch.int64, device=device),
+                                            torch.tensor(sizes, dtype=torch.int64, device=device), output_size=offsets[-1])
+        out.num_graphs, out.num_nodes = len(graphs), offsets[-1]
+        return out
+
+
 class SaintBatch:
     """One sampled subgraph: the fields ``train()`` of the reference reads (mag_pyg/gnn.py:187-192) plus ``node_idx`` / ``edge_idx``
     (ids in the parent graph) and ``relations`` (what ``RGCNConv._relations`` returns for this batch; None when the parent has

@@ -1049,6 +1049,54 @@ int egnn_probe_gather_lines_f32(const float* X, int64_t ldx, int64_t n_src, int6
                                 int blocks_per_slice, int loads_in_flight, float* sink, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Gather, add the edge's own row, activate and aggregate in one walk (csrc/gather_edge_scatter.hip): the message relu(x_j + edge_attr)
+ * of the convs that read edge features (PyG's GINEConv [ext]; the reference's mol_pyg is a README only) without an [S, C] tensor.  No
+ * float atomics, no integer atomics; first derivatives only.
+ *
+ * egnn_gather_edge_scatter_runs_f32   replaces ops.scatter(relu(ops.take_rows(x, src) + e), dst): a gather that writes [S, C], an add,
+ *     a relu that writes [S, C] again and the run-sum that reads it.  For every row r < n_rows, over the positions p of r's run in
+ *     keys_sorted (keys_sorted, S, shift, from, x, n_x, from_count, count, reduce, ws: as egnn_gather_scatter_runs_f32 below):
+ *         out[r, c] = reduce_p  m[p, c],     v[p, c] = x[from[p], c] / (float)from_count[from[p]]   (the division only when from_count != NULL)
+ *         mode 0 (ADD):       m = v + e[p, c]                     (e == NULL: m = v)
+ *         mode 1 (ADD_RELU):  m = max(v + e[p, c], 0)             (the sum rounded to fp32 first; a sum that is not > 0 gives +0)
+ *         mode 2 (GATE):      m = own[r, c] + e[p, c] > 0 ? v : 0
+ *     GATE is the backward of ADD_RELU for the gathered-from side: walked over the SOURCE side's keys with from = the target rows
+ *     (-1 for a dropped id), x = the gradient of out, from_count = the forward's count for mean and own = the forward's x, whose row r
+ *     every position of r's run read.  The backward of ADD is ADD with e == NULL.
+ *     e float [S, ld_e], ld_e >= C: the row of position p; own float [n_rows, ld_own], ld_own >= C (read in GATE only).  A from entry
+ *     outside [0, n_x) reads nothing and stands for a row of zeros (m = e[p], max(e[p], 0), 0): what the materialised messages hold
+ *     for a target id a deferred plan dropped.  EVERY row of out [n_rows, ld_out] is written, a row that no key names gets 0; count
+ *     and mean's division as egnn_gather_scatter_runs_f32.
+ *     ORDER OF THE ADDITIONS: egnn_rows_add_runs_f32's over m -- the first message of a chunk of EGNN_ROWS_SUM_CHUNK positions is taken
+ *     as it is, the others are added in ascending position, a long run's chunks are parked in ws and merged in ascending chunk order.
+ *     The result is bit-equal to egnn_scatter_runs_f32 over the materialised messages, whatever the pitches and alignments.
+ *     16 bytes per lane when C % 4 == 0, every pitch % 4 == 0 and out, x, e and own are 16-byte aligned; a scalar path with the same
+ *     arithmetic otherwise.  Four keys, then four ids and four rows of e, then four rows of x are in flight per lane.
+ *     Occupancy as egnn_gather_scatter_runs_f32 (8 waves per SIMD) except on the 16-byte path for mode 0 / 1 WITH from_count, which
+ *     holds four rows of e, four rows of x and four divisors: 7 waves (no scratch anywhere; profiles/gather_edge_scatter_resources.txt).
+ *     ws: egnn_gather_edge_scatter_ws_bytes(S, C) bytes (= egnn_rows_add_runs_ws_bytes), 16-byte aligned; missing or short:
+ *     EGNN_EWORKSPACE; misaligned pointers: EGNN_EALIGN; mode outside 0 .. 2, mode 1 / 2 without e, mode 2 without own, sizes and
+ *     pitches as egnn_gather_scatter_runs_f32: EGNN_EINVAL.  Every check happens before the first launch.  S == 0: EGNN_OK; with a
+ *     non-NULL out the n_rows rows and counts are zeroed.
+ *
+ * egnn_edge_gate_f32   replaces the relu and scatter backward passes over [S, C]: the gradient of the edge rows,
+ *         de[p, c] = gate ? g[b_rows[p], c] / (float)b_count[b_rows[p]] : 0,    gate = mode == 0 || x[a_rows[p], c] + e[p, c] > 0
+ *     for p < S (the division only when b_count != NULL), mode 0 or 1.  a_rows / b_rows int64 [S]: the rows of x [n_x, ld_x] and of the
+ *     gradient g [n_g, ld_g] that position p names; a b_rows entry outside [0, n_g) gives de[p, :] = 0 and reads nothing, an a_rows
+ *     entry outside [0, n_x) stands for a row of zeros.  mode 0 reads neither a_rows, x nor e.  Elementwise: no reduction, every
+ *     element of de [S, ld_de] is written with a plain store, one lane group per position.  S < 2^31 - 1, C >= 1, pitches >= C: else
+ *     EGNN_EINVAL; misaligned pointers: EGNN_EALIGN.  S == 0: EGNN_OK.
+ * ---------------------------------------------------------------------------------------------- */
+size_t egnn_gather_edge_scatter_ws_bytes(int64_t S, int64_t C);
+int egnn_gather_edge_scatter_runs_f32(float* out, int64_t ld_out, int64_t n_rows, int32_t* count, const uint64_t* keys_sorted, int64_t S,
+                                      int shift, const int64_t* from, const float* x, int64_t ld_x, int64_t n_x, const int32_t* from_count,
+                                      const float* e, int64_t ld_e, const float* own, int64_t ld_own, int mode, int64_t C, int reduce,
+                                      void* ws, size_t ws_bytes, void* stream);
+int egnn_edge_gate_f32(float* de, int64_t ld_de, int64_t S, int64_t C, const int64_t* a_rows, const float* x, int64_t ld_x, int64_t n_x,
+                       const float* e, int64_t ld_e, const int64_t* b_rows, const float* g, int64_t ld_g, int64_t n_g,
+                       const int32_t* b_count, int mode, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Gather, weight and aggregate in one walk (csrc/gather_scatter.hip): the lift, the per-edge weight and the aggregation of a
  * message-passing layer without the [S, C] message tensor, and the per-edge dot that is the weights' gradient.  No float atomics, no
  * integer atomics; first derivatives only.
