@@ -462,6 +462,144 @@ int launch_blk(const BlkArgs& a, unsigned grid, size_t shm, hipStream_t st) {
   return egnn_launch_status();
 }
 
+// ---- class-width form: 32 < K < 64 (the 40-class output layer) -------------------------------------------------------------------
+// The gather machinery above (int32 indices, premultiplied byte offsets, one buffer descriptor, out-of-range offsets for padded slots
+// and dead lanes, swizzle broadcasts) with a 16-lane sub-group per row, so that col / val are read once per entry for the whole row
+// (the 8-lane slices above read them once per 128-byte slice: 113 us against 92 us of the first-generation 16-lane kernel at K = 40).
+// The 16 lanes hold 16 entries per step (one col / val read), gathered as two batches of 8.
+// Rows of at most seg_max entries are written completely; longer rows go through the hub segments and egnn_spmm_combine_f32 with the
+// cuts of the other schedules.  One fmaf chain per output element in ascending entry order, padded slots add an exact 0 * 0: the
+// result is bit-equal to egnn_spmm_csr_seg_f32 on the same data.
+// Measured and dropped (profiles/spmm_class_width.json): the source split into a [n_src, 32] and a [n_src, 8] piece gathered by 8-lane
+// sub-groups (81.2 us against 80.0 us per call: the 160-byte row's second line is not what bounds the kernel), and 2 / 4 / 8 rows per
+// sub-group with the next row's col / val requested ahead of the gathers (80.6 / 83.3 / 88.5 us against 79.5 us).
+struct CwArgs {
+  int64_t n_rows;
+  int K;
+  const int32_t* rowptr;
+  const int32_t* col;
+  const float* val;
+  const float* src_scale;
+  const float* bias;
+  const float* X;
+  uint32_t row_bytes, x_bytes;
+  float* Y;
+  int64_t ldy;
+  int mean, seg_max;
+  const int32_t* hseg;
+  int64_t n_hseg;
+  float* P;
+  const float* addend;
+  int64_t ld_add;
+  int flags;
+};
+
+// broadcast lane J of every 16-lane group to the group (bit-mask swizzle inside each half-wave)
+template <int J>
+__device__ __forceinline__ uint32_t bcast16(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x10 | (J << 5));
+}
+
+// lane li's entry of the 16-entry step starting at e (weight 0, offset 0 past the end)
+__device__ __forceinline__ void cw_entries(const CwArgs& a, int e, int end, int li, uint32_t& off_l, float& v_l) {
+  off_l = 0;
+  v_l = 0.f;
+  if (e + li < end) {
+    const int c = a.col[e + li];
+    off_l = (uint32_t)c * a.row_bytes;
+    v_l = a.val ? a.val[e + li] : 1.f;
+    if (a.src_scale) v_l *= a.src_scale[c];
+  }
+}
+
+template <int J>
+__device__ __forceinline__ void cw_one(rsrc_t rsrc, uint32_t off_l, float v_l, int n, uint32_t lane_off, float4& x, float& v) {
+  const uint32_t o = bcast16<J>(off_l);
+  v = __uint_as_float(bcast16<J>(__float_as_uint(v_l)));
+  x = buf_load4(rsrc, J < n ? o + lane_off : kOob);   // lane_off is kOob itself for lanes past K
+}
+
+// entries 8 B .. 8 B + 7 of a step of n entries
+template <int B>
+__device__ __forceinline__ void cw_batch(rsrc_t rsrc, uint32_t off_l, float v_l, int n, uint32_t lane_off, float (&acc)[4]) {
+  float4 x0, x1, x2, x3, x4, x5, x6, x7;
+  float v0, v1, v2, v3, v4, v5, v6, v7;
+  cw_one<8 * B + 0>(rsrc, off_l, v_l, n, lane_off, x0, v0);
+  cw_one<8 * B + 1>(rsrc, off_l, v_l, n, lane_off, x1, v1);
+  cw_one<8 * B + 2>(rsrc, off_l, v_l, n, lane_off, x2, v2);
+  cw_one<8 * B + 3>(rsrc, off_l, v_l, n, lane_off, x3, v3);
+  cw_one<8 * B + 4>(rsrc, off_l, v_l, n, lane_off, x4, v4);
+  cw_one<8 * B + 5>(rsrc, off_l, v_l, n, lane_off, x5, v5);
+  cw_one<8 * B + 6>(rsrc, off_l, v_l, n, lane_off, x6, v6);
+  cw_one<8 * B + 7>(rsrc, off_l, v_l, n, lane_off, x7, v7);
+  fma4(v0, x0, acc); fma4(v1, x1, acc); fma4(v2, x2, acc); fma4(v3, x3, acc);
+  fma4(v4, x4, acc); fma4(v5, x5, acc); fma4(v6, x6, acc); fma4(v7, x7, acc);
+}
+
+// entries [start, end) of one row (or hub segment) gathered into acc
+__device__ __forceinline__ void cw_range(const CwArgs& a, rsrc_t rsrc, int start, int end, int li, uint32_t lane_off, float (&acc)[4]) {
+  for (int e = start; e < end; e += 16) {
+    uint32_t off_l;
+    float v_l;
+    cw_entries(a, e, end, li, off_l, v_l);
+    const int n = end - e < 16 ? end - e : 16;
+    cw_batch<0>(rsrc, off_l, v_l, n, lane_off, acc);
+    if (n > 8) cw_batch<1>(rsrc, off_l, v_l, n, lane_off, acc);
+  }
+}
+
+__global__ __launch_bounds__(256) void spmm_cw_kernel(const CwArgs a) {
+  constexpr int NSUB = 16;   // 16-lane sub-groups per workgroup: one hub segment or one row each
+  const int lane = egnn_lane();
+  const int li = lane & 15;
+  const int subw = egnn_wave_id() * 4 + (lane >> 4);
+  const int n_hgrp = (int)((a.n_hseg + NSUB - 1) / NSUB);
+  const int item = (int)blockIdx.x;   // one workgroup per item: the hub-segment groups first, then the row blocks
+  const int col0 = li * 4;
+  const bool colok = col0 < a.K;
+  const uint32_t lane_off = colok ? (uint32_t)li * 16u : kOob;
+  const rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.X), 0, (int)a.x_bytes, 0x00020000);
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  if (item < n_hgrp) {  // ---- hub segments: raw partial sums ----------------------------------------------------------------
+    const int64_t s = (int64_t)item * NSUB + subw;
+    if (s < a.n_hseg) {
+      const int start = a.hseg[4 * s], end = a.hseg[4 * s + 1], slot = a.hseg[4 * s + 2];
+      cw_range(a, rsrc, start, end, li, lane_off, acc);
+      if (colok) *reinterpret_cast<float4*>(a.P + (int64_t)slot * a.K + col0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    }
+    return;
+  }
+  const int64_t row = (int64_t)(item - n_hgrp) * NSUB + subw;
+  if (row >= a.n_rows) return;
+  const int start = a.rowptr[row], end = a.rowptr[row + 1];
+  const int cnt = end - start;
+  if (cnt > a.seg_max) return;  // hub row: written by the combine kernel
+  cw_range(a, rsrc, start, end, li, lane_off, acc);
+  if (colok) {
+    float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.bias) bias = *reinterpret_cast<const float4*>(a.bias + col0);
+    const float inv = a.mean ? 1.f / (float)(cnt > 0 ? cnt : 1) : 1.f;
+    float4 y = make_float4(acc[0] * inv + bias.x, acc[1] * inv + bias.y, acc[2] * inv + bias.z, acc[3] * inv + bias.w);
+    if (a.addend) { const float4 ad = *reinterpret_cast<const float4*>(a.addend + row * a.ld_add + col0); y.x += ad.x; y.y += ad.y; y.z += ad.z; y.w += ad.w; }
+    store_row4(a.Y + row * a.ldy + col0, y, a.flags);
+  }
+}
+
+// the class-width form of egnn_spmm_csr_blk_f32 (its checks have passed)
+int launch_cw(const egnn_spmm_t* op, int seg_max, const int32_t* hub_seg, int64_t n_hub_seg, float* partial, uint32_t x_bytes,
+              hipStream_t st) {
+  CwArgs a{};
+  a.n_rows = op->n_rows; a.K = (int)op->K; a.rowptr = (const int32_t*)op->rowptr; a.col = (const int32_t*)op->col;
+  a.val = op->val; a.src_scale = op->src_scale; a.bias = op->bias;
+  a.X = op->X; a.row_bytes = (uint32_t)op->ldx * 4u; a.x_bytes = x_bytes;
+  a.Y = op->Y; a.ldy = op->ldy; a.mean = op->reduce == EGNN_MEAN; a.seg_max = seg_max;
+  a.hseg = hub_seg; a.n_hseg = n_hub_seg; a.P = partial; a.addend = op->addend; a.ld_add = op->ld_addend; a.flags = op->flags;
+  const int64_t grid = (n_hub_seg + 15) / 16 + (op->n_rows + 15) / 16;
+  if (grid > 0x7fffffffLL) return EGNN_EINVAL;
+  hipLaunchKernelGGL(spmm_cw_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+  return egnn_launch_status();
+}
+
 }  // namespace
 
 extern "C" int64_t egnn_spmm_blk_stat_rows(int64_t n_rows, int rows_per_blk, int lds) {
@@ -494,6 +632,8 @@ extern "C" int egnn_spmm_csr_blk_f32(const egnn_spmm_t* op, int seg_max, int row
     return EGNN_EALIGN;
   const uint64_t xb = (uint64_t)op->n_src * (uint64_t)op->ldx * 4ull;
   if (xb > 0x7FFFFFFFull) return EGNN_EALIGN;  // 32-bit descriptor offsets: the host uses the 64-bit kernels of spmm.hip
+  if (K > 32 && K < 64 && win == nullptr && blk_ptr == nullptr && op->stat_part == nullptr)
+    return launch_cw(op, seg_max, hub_seg, n_hub_seg, partial, (uint32_t)xb, (hipStream_t)stream);   // class widths: 16-lane sub-groups, rows_per_blk is not read
   if (blk_ptr == nullptr) n_blk = (n_rows + rows_per_blk - 1) / rows_per_blk;
   EGNN_CHECK_ARG(n_blk > 0);
   const bool lds = win != nullptr;

@@ -37,7 +37,7 @@ def _rowmajor(x: Tensor) -> Tensor:
 # SpMM
 # ------------------------------------------------------------------------------------------------
 # 'blocks' (default): egnn_spmm_csr_blk_f32; 'segments': egnn_spmm_csr_seg_f32; 'classes': short / mid / long row classes
-_SPMM_SCHEDULE = "blocks"   # "blocks" (row blocks, K >= 64) -> "segments" (K < 64) -> "classes" (max / unaligned); tests pin one by setting the attribute
+_SPMM_SCHEDULE = "blocks"   # "blocks" (row blocks, K >= 64; class widths 32 < K < 64) -> "segments" (K <= 32) -> "classes" (max / unaligned); tests pin one by setting the attribute
 
 
 class HipStatsUnavailable(RuntimeError):
@@ -51,6 +51,12 @@ def _spmm_desc(adj, rowptr, col, bits, x, y, red, src_scale, bias) -> ctypes.Str
     n_rows, n_src = adj.sparse_sizes()
     return _lib.Spmm(n_rows, n_src, x.shape[1], _lib.ptr(rowptr), _lib.ptr(col), bits, _lib.ptr(adj._value), _lib.ptr(src_scale),
                      _lib.ptr(bias), _lib.ptr(x), x.stride(0), _lib.ptr(y), y.stride(0), red)
+
+
+def class_width_enabled() -> bool:
+    """False when EGNN_SPMM_CLASS_WIDTH=0 sends the class widths (32 < K < 64) back to the
+    segment schedule they ran on before the block entry point had a form for them."""
+    return os.environ.get("EGNN_SPMM_CLASS_WIDTH", "1") != "0"
 
 
 def spmm_raw(adj, x: Tensor, reduce: str = "sum", src_scale: Tensor | None = None, use_plan: bool = True,
@@ -114,9 +120,11 @@ def _spmm_raw(adj, x: Tensor, reduce: str = "sum", src_scale: Tensor | None = No
                  and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0 and (bias is None or bias.data_ptr() % 16 == 0))
     add_fused = addend is not None and addend.stride(0) % 4 == 0 and addend.data_ptr() % 16 == 0
     # the block schedule wins from two 128-byte column slices up (K = 256: 343 vs 385 us, K = 128: 167 vs 186 us on the
-    # arxiv-shaped graph); below that (the 40-class output layer) the 16-lane form of the segment kernel is faster (92 vs 113 us)
-    if (float4_ok and _SPMM_SCHEDULE == "blocks" and bits == 32 and K >= 64 and n_src * x.stride(0) * 4 < 2 ** 31 and n_rows > 0
-            and (addend is None or add_fused)):
+    # arxiv-shaped graph); below that its 8-lane slices lose to the 16-lane form of the segment kernel (113 vs 92 us at the 40-class
+    # output layer), but the class widths have a 16-lane form of their own behind the same entry point (csrc/spmm_blk.hip)
+    class_width = 32 < K < 64 and not want_stats and class_width_enabled()
+    if (float4_ok and _SPMM_SCHEDULE == "blocks" and bits == 32 and (K >= 64 or class_width) and n_src * x.stride(0) * 4 < 2 ** 31
+            and n_rows > 0 and (addend is None or add_fused)):
         from .sparse import BLK_ROWS, SEG_MAX
         hseg, crow, cptr, slots = adj._blk_plan()
         partial = adj._scratch("partial", (max(slots, 1), K))
@@ -125,7 +133,8 @@ def _spmm_raw(adj, x: Tensor, reduce: str = "sum", src_scale: Tensor | None = No
         rows_blk = loc[0] if use_lds else BLK_ROWS
         n_blk = (n_rows + rows_blk - 1) // rows_blk
         # Y rows are stored write-through (dropped from L2: they are not re-read here and would only evict gathered X lines)
-        flags = 4 | (8 if (relu and not want_stats) else 0)
+        # (the class widths keep the plain stores of the segment schedule they ran on: their Y is the next kernel's input)
+        flags = (0 if K < 64 else 4) | (8 if (relu and not want_stats) else 0)
         n_stat = lib.egnn_spmm_blk_stat_rows(n_rows, rows_blk, int(use_lds)) if want_stats else 0
         n_hub = crow.numel()
         stat_part = adj._scratch("stat", (n_stat + n_hub, 2, K)) if want_stats else None   # one partial row per wave + per hub row

@@ -133,7 +133,10 @@ int egnn_spmm_csr_seg_f32(const egnn_spmm_t* op, const int64_t* seg, int64_t n_s
  *              of 128, <= 512) the block's X rows are streamed into LDS (LDS-DMA) while the out-of-block entries are
  *              gathered, and the in-block entries read LDS instead of L2 (graphs in a locality order).
  *   stat_part  here [egnn_spmm_blk_stat_rows(n_rows, rows_per_blk, win != NULL), 2, K]: one partial row per WAVE of every row
- *              block, over the rows that wave stored (egnn_bn_stats_merge_f32's n_blk = that row count) */
+ *              block, over the rows that wave stored (egnn_bn_stats_merge_f32's n_blk = that row count)
+ * CLASS WIDTHS (32 < K < 64: the 40-class output layer) without blk_ptr, win and stat_part take a form of their own: a 16-lane
+ * sub-group per row (col / val read once per entry, not once per 128-byte slice), 16 rows per workgroup; rows_per_blk is not read.  Same hub_seg / partial / combine
+ * contract, same summation order: bit-equal to egnn_spmm_csr_seg_f32 with cuts at seg_max. */
 int egnn_spmm_csr_blk_f32(const egnn_spmm_t* op, int seg_max, int rows_per_blk, const int32_t* blk_ptr, int64_t n_blk,
                           const int32_t* win, const int32_t* hub_seg, int64_t n_hub_seg, float* partial, void* stream);
 int64_t egnn_spmm_blk_stat_rows(int64_t n_rows, int rows_per_blk, int lds);
